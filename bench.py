@@ -2,33 +2,46 @@
 """Headline benchmark: env-steps/sec of the post-physics hot path for 4096 UnitreeH1.walk
 environments per GPU (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 --config 2 (default, the BASELINE metric): one "step" = one launch of the fused K1+K5 kernel (obs
     build + has-fallen + previous-obs reward + action scale/clamp) over one [T=400, N=4096] block of
     synthetic qpos/qvel/action already resident in HBM = 1 638 400 env-steps.  Launch regime: [T,N]
     block per launch.  Environments shard across ranks with no data-path collective (weak scaling);
-    the barriers bracketing the timed region are the only communication.  The line also carries a
-    `per_step` block: the single-vec-step regime (one launch / one HIP graph per env.step()).
+    the barriers bracketing the timed region are the only communication.
 --config 5 (BASELINE.json configs[4]): one "step" = one PPO iteration tail per rank on a
     [T=400, N=4096] shard: K6 return scan (advantage statistics fused into the same pass) -> ONE
     all-gather of (count, sum, sumsq) = 24 B per rank (RCCL over xGMI) -> K7 normalisation that adds
     the rank triples on the device (rl/algos/ppo.py:200-230 merge + :335-336).
 
-The default (config 2) line also carries, measured OUTSIDE the headline's timed region and each wrapped so that
-it can never cost the headline:
-  world 1:  `configs` = BASELINE configs 3, 4 and 5 on one GPU, each with its own roofline and an oracle
-            `cpu_baseline` (config 3: the rollout's kernels K13 / K11 / K10; config 4: the fused VAIL reward K12;
-            config 5: the iteration tail at world 1);
+A plain run does only what the headline needs: set up, wake the device (`prewarm`), W warm-up steps, the K timed
+steps, the outputs (--dump-outputs) and the line.  Its roofline is derived from the timed steps' own HIP events.
+
+--full adds everything that takes runs of its own, measured OUTSIDE the headline's timed region and each wrapped so
+that it can never cost the headline:
+  config 2:  the measured device-copy bandwidth of the roofline; `cpu_baseline` (the oracle on a slice of the block);
+  world 1:   `per_step` (the single-vec-step regime: one launch / one HIP graph per env.step()) and `configs` =
+             BASELINE configs 3, 4 and 5 on one GPU, each with its own roofline and an oracle `cpu_baseline` (config 3:
+             the rollout's kernels K13 / K11 / K10; config 4: the fused VAIL reward K12; config 5: the iteration tail
+             at world 1);
   world > 1: `config5_tail` = the iteration tail run in these same rank processes, so that a `--gpus 8` run
-            records that the process group saw 8 ranks and what the one collective of the design costs.
+             records that the process group saw 8 ranks and what the one collective of the design costs;
+  config 5:  the per-stage times and the roofline of scan + normalise, and `cpu_baseline`.
+--no-cpu-baseline / --no-per-step / --no-configs leave single blocks of --full out.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed on rank 0 as DIR/<name>.npy
+(float32 / float64; integer outputs widened exactly): config 2: obs, reward, absorbing, ctrl (fall_code with
+--fall-code) on a fixed seeded sample of the [T,N] rows (`sample_rows`, the flat row t * N + n) and the carried reward
+state `prev` of every environment; config 5: the returns, the normalised advantages and the shard's statistics.
+The inputs are seeded: the same arguments give the same inputs on every run.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this script starts the N rank processes
 itself (the parent never touches a GPU), relays rank 0's JSON line and fails if any rank fails.
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import functools
 import json
 import os
 import subprocess
@@ -52,9 +65,14 @@ def parse_args(argv=None):
     ap.add_argument("--config", type=int, default=2, choices=[2, 5])
     ap.add_argument("--T", type=int, default=400)
     ap.add_argument("--N", type=int, default=4096, help="environments per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-per-step", action="store_true", help="skip the single-vec-step block of config 2")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs 3 / 4 / 5 block of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary blocks (copy bandwidth, per_step, configs 3 / 4 / 5, config5_tail, "
+                         "stage times, CPU baselines); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the oracle CPU baselines")
+    ap.add_argument("--no-per-step", action="store_true", help="--full without the single-vec-step block of config 2")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the configs 3 / 4 / 5 block")
     ap.add_argument("--fall-code", action="store_true", help="also write the fall-code byte")
     ap.add_argument("--robot", default="h1", choices=["h1", "atlas", "talos", "h1_arms", "h1_ff"],
                     help="h1 is the BASELINE config; the others exercise the same kernel on other tables")
@@ -223,6 +241,50 @@ def prewarm(rk, step, seconds=0.25):
     torch.cuda.synchronize(rk.dev)
     PREWARM.update({"launches": n, "seconds_estimated": elapsed,
                     "why": "device clocks ramp from idle over tens of ms on this pool; untimed, before the W warm-up steps"})
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 131072          # rows of a [T,N] output that --dump-outputs writes (a fixed, seeded sample)
+
+
+def dump_row_sample(rows, seed=2024):
+    """The flat rows of a [T,N] output that --dump-outputs writes: all of them when they fit, else a fixed, seeded,
+    sorted sample of DUMP_SAMPLE_ROWS."""
+    import numpy as np
+    if rows <= DUMP_SAMPLE_ROWS:
+        return np.arange(rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(rows, DUMP_SAMPLE_ROWS, replace=False))
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: each array (torch tensor or numpy) as <path>/<name>.npy in float32 or float64.  Floating arrays
+    keep their type; integer and boolean ones are widened exactly (up to 16 bits -> float32, wider -> float64).
+    Writes nothing if the whole would exceed `max_bytes`.  Returns the bytes written."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        host[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in host.values())
+    if total > max_bytes:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the budget of {max_bytes}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
+def sampled_rows(arrays, T, N, dev):
+    """{name: [T,N] or [T,N,k] tensor} -> the same outputs on the rows of dump_row_sample, plus `sample_rows`."""
+    import torch
+    idx = dump_row_sample(T * N)
+    ix = torch.as_tensor(idx, device=dev)
+    out = {"sample_rows": idx}
+    for k, v in arrays.items():
+        out[k] = v.reshape(T * N, -1)[ix] if v.dim() == 3 else v.reshape(T * N)[ix]
+    return out
 
 
 def event_ms(stream, reps, fn, wake_s=0.08):
@@ -898,7 +960,7 @@ def config5_world1_block(rk, args):
     """BASELINE config 5's iteration tail on ONE GPU (its 8-GPU form is `bench.py --config 5 --gpus 8`; under a
     multi-rank default run the same tail is measured as `config5_tail`)."""
     from olympic_hip.engine import Engine
-    m = measure_config5_tail(rk, Engine(rk.local_rank), 400, args.N, 100, 10)
+    m = measure_config5_tail(rk, Engine(rk.local_rank), 400, args.N, 100, 10, full=True)
     out = {"workload": "PPO iteration tail on one [400,4096] shard: K6 scan (statistics fused, f64 rewards) -> "
                        "(world 1: the all-gather is a view) -> K7 normalise", "value": m["value"], "unit": m["unit"],
            "ms_per_step": m["ms_per_step"], "stages_ms": m["stages_ms"], "roofline": m["roofline"]}
@@ -942,6 +1004,7 @@ def bench_config2(args, rk):
                ctrl=torch.empty((T, N, spec.nu), dtype=torch.float32, device=dev))
     if args.fall_code:
         out["fall_code"] = torch.empty((T, N), dtype=torch.uint8, device=dev)
+    # the device's default generator starts from torch's fixed default seed in every process: reproducible inputs
     grf = (torch.empty((T, N, spec.n_grf), dtype=torch.float64, device=dev).normal_(0, 300) if spec.n_grf else None)
 
     def step(i):
@@ -949,20 +1012,23 @@ def bench_config2(args, rk):
                     want_fall_code=args.fall_code)
 
     wall, kern_ms = timed_region(rk, eng.ctx.stream, args.warmup, args.steps, step)
+    if args.dump_outputs and rank == 0:
+        # the last step run (a timed one unless --steps 0) wrote the carried reward state into prev[(last + 1) & 1]
+        last = args.steps - 1 if args.steps else args.warmup - 1 if args.warmup else PREWARM["launches"] - 1
+        dump_outputs(args.dump_outputs, dict(sampled_rows(out, T, N, dev), prev=prev[(last + 1) & 1]))
     rows = T * N
     fallen = float(out["absorbing"].float().mean().item())
-    # N > 1: the design's ONE exchange step (rl/algos/ppo.py:200-230,335-336) measured in these same rank processes,
-    # so that a driver --gpus N run of the default command records that the process group saw N ranks and what the
-    # all-gather costs (config 2 itself has no data-path collective).  Every rank takes part.
+    # --full, N > 1: the design's ONE exchange step (rl/algos/ppo.py:200-230,335-336) measured in these same rank
+    # processes, so that a driver --gpus N run of the default command records that the process group saw N ranks and
+    # what the all-gather costs (config 2 itself has no data-path collective).  Every rank takes part.
     tail = None
-    if world > 1 and not args.no_configs:
+    if args.full and world > 1 and not args.no_configs:
         try:
-            tail = measure_config5_tail(rk, eng, 400, N, 50, 5)
+            tail = measure_config5_tail(rk, eng, 400, N, 50, 5, full=True)
         except Exception as e:     # noqa: BLE001  (never costs the headline line)
             tail = {"error": f"{type(e).__name__}: {e}"[:300]}
     if rank != 0:
         return None
-    copy_gbps = copy_bandwidth(rk, eng.ctx.stream)
     bpr = alg_bytes_per_row(spec, args.fall_code)
     achieved = bpr * rows / (kern_ms * 1e-3) / 1e9
     traffic, traffic_round = None, None
@@ -997,12 +1063,16 @@ def bench_config2(args, rk):
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "traffic_source": (f"profiles/traffic_k1.json (rocprofv3 PMC passes of round {traffic_round}, FETCH_SIZE x 2 "
                                         "+ WRITE_SIZE; read from the file, not measured in this run)" if traffic else None),
-                     "measured_copy_GBps": copy_gbps, "frac_of_measured_copy": achieved / copy_gbps,
-                     "measured_copy_note": "torch's device-to-device copy_ of 404 MB timed the same way; it is slower than "
-                                           "the guide's float4 copy (6.29 TB/s), so a ratio above 1 only says that",
                      "kernel": "il_tile_kernel<128,%s>" % args.robot, "kernel_ms": kern_ms,
                      "alg_bytes_per_env_step": bpr, "env_steps_per_launch": rows},
     }
+    if not args.full:
+        return line
+    copy_gbps = copy_bandwidth(rk, eng.ctx.stream)
+    line["roofline"].update({
+        "measured_copy_GBps": copy_gbps, "frac_of_measured_copy": achieved / copy_gbps,
+        "measured_copy_note": "torch's device-to-device copy_ of 404 MB timed the same way; it is slower than "
+                              "the guide's float4 copy (6.29 TB/s), so a ratio above 1 only says that"})
     if tail is not None:
         tail.pop("wall_s", None)
         tail["workload"] = ("config-5 iteration tail per rank on its own [400,N] shard: K6 scan (statistics fused) -> ONE "
@@ -1048,10 +1118,11 @@ def cpu_baseline_config5(T, N, seconds=9.0):
                       f"shared-statistics run), ~{seconds * 0.65:.0f} s; 1 thread: the whole shard"}
 
 
-def measure_config5_tail(rk, eng, T, N, steps, warmup):
+def measure_config5_tail(rk, eng, T, N, steps, warmup, full=False, dump=None):
     """K6 (+ fused statistics) -> all-gather of 3 doubles per rank -> K7 normalise, per rank on its own
     [T,N] shard of the N*world environments (rl/algos/ppo.py:200-230,335-336).  Returns a dict with the timed
-    region's wall time, the per-stage times and the roofline of scan + normalise; every rank must call it."""
+    region's wall time and, with `full`, the per-stage times and the roofline of scan + normalise; every rank must
+    call it.  `dump(arrays)` receives the last timed step's outputs (this rank's shard) before anything else runs."""
     import torch
     from olympic_hip import _abi, dist as odist
     dev, rank, world = rk.dev, rk.rank, rk.world
@@ -1077,6 +1148,14 @@ def measure_config5_tail(rk, eng, T, N, steps, warmup):
         eng.adv_normalize(adv, gather(), 1, 1e-5)
 
     wall, ms_step = timed_region(rk, eng.ctx.stream, warmup, steps, step)
+    if dump is not None:
+        dump(dict(sampled_rows(dict(ret=ret, adv=adv), T, N, dev), stats=st))
+    ranks_seen = rk.dist.get_world_size() if rk.dist is not None else 1
+    res = {"wall_s": wall, "steps": steps, "value": world * T * N * steps / wall, "unit": "env-steps/s",
+           "ms_per_step": 1e3 * wall / max(steps, 1), "ranks_seen": ranks_seen,
+           "backend": rk.backend if rk.dist is not None else None, "T": T, "envs_per_gpu": N}
+    if not full:
+        return res
     # stage breakdown, outside the timed region: each stage alone, back to back, HIP events
     reps = max(20, min(steps, 200))
     ms_scan = event_ms(eng.ctx.stream, reps, scan)
@@ -1094,11 +1173,8 @@ def measure_config5_tail(rk, eng, T, N, steps, warmup):
     assert float(tot[0]) == float(T * N * world), (float(tot[0]), T * N * world)
     elems = T * N
     b_scan, b_norm = 21, 8         # f64 reward 8 + value 4 + next value 4 + flag 1 in, ret 4 + adv 4 out | adv in + out
-    ranks_seen = rk.dist.get_world_size() if rk.dist is not None else 1
-    return {
-        "wall_s": wall, "steps": steps, "value": world * elems * steps / wall, "unit": "env-steps/s",
-        "ms_per_step": 1e3 * wall / max(steps, 1), "ranks_seen": ranks_seen, "gathered_rows": int(parts.shape[0]),
-        "backend": rk.backend if rk.dist is not None else None, "T": T, "envs_per_gpu": N,
+    return dict(res, **{
+        "gathered_rows": int(parts.shape[0]),
         "stages_ms": {"scan_with_fused_stats": ms_scan, "all_gather_host_wall": ms_gather, "normalise": ms_norm,
                       "whole_step_hip_events": ms_step},
         "roofline": {"bound": "hbm", "achieved": (b_scan + b_norm) * elems / ((ms_scan + ms_norm) * 1e-3) / 1e9,
@@ -1113,7 +1189,7 @@ def measure_config5_tail(rk, eng, T, N, steps, warmup):
                      "elements_per_launch": elems,
                      "note": "the [400,4096] tail is bound by the 400-step dependent fp64 chain and launch latency, "
                              "not by its 48 MB (DESIGN 4, K6)"},
-    }
+    })
 
 
 def bench_config5(args, rk):
@@ -1121,7 +1197,8 @@ def bench_config5(args, rk):
     world = rk.world
     eng = Engine(rk.local_rank)
     T, N = args.T, args.N
-    m = measure_config5_tail(rk, eng, T, N, args.steps, args.warmup)
+    dump = functools.partial(dump_outputs, args.dump_outputs) if args.dump_outputs and rk.rank == 0 else None
+    m = measure_config5_tail(rk, eng, T, N, args.steps, args.warmup, full=args.full, dump=dump)
     if rk.rank != 0:
         return None
     line = {
@@ -1145,9 +1222,10 @@ def bench_config5(args, rk):
                    "ranks_seen": m["ranks_seen"],
                    "rewards": "f64 (un-narrowed, as env.step returns them)",
                    "parallelism": f"env-sharded x{world}, one all-gather of 3 doubles per rank per step"},
-        "stages_ms": m["stages_ms"],
-        "roofline": m["roofline"],
     }
+    if not args.full:
+        return line
+    line.update(stages_ms=m["stages_ms"], roofline=m["roofline"])
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_config5(T, N)
     return line

@@ -74,12 +74,12 @@ def test_ppo_train_two_ranks_share_one_gpu(tmp_path, n0, n1):
 
 @pytest.mark.parametrize("config", [5, 2])
 def test_bench_starts_its_own_ranks(config):
-    """`python bench.py --gpus 2` with no WORLD_SIZE starts two rank processes itself and reports
+    """`python bench.py --gpus 2 --full` with no WORLD_SIZE starts two rank processes itself and reports
     n_gpus = 2 (here both on cuda:0 over gloo; on an 8-GPU node one per GPU over RCCL)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
                           "--share-device", "--config", str(config), "--steps", "5", "--warmup", "2",
-                          "--T", "100", "--no-cpu-baseline"],
+                          "--T", "100", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -104,12 +104,12 @@ def test_bench_five_ranks_in_the_drivers_command_shape(config):
     """The driver's multi-GPU command shape with as many ranks as one box may put on its GPU next to the test process
     itself (the pool admits six processes on a GPU: this pytest process, whose earlier tests hold a context, + five
     ranks; the 8-rank all-gather / tree sum itself runs on the CPU in
-    test_host_cpu.py::test_adv_stats_allgather_two_ranks_gloo[8]): `bench.py --gpus 5` starts five ranks, the process
-    group sees five, the ONE all-gather returns five triples, the default command's line carries config5_tail."""
+    test_host_cpu.py::test_adv_stats_allgather_two_ranks_gloo[8]): `bench.py --gpus 5 --full` starts five ranks, the
+    process group sees five, the ONE all-gather returns five triples, the default command's line carries config5_tail."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--backend", "gloo",
                           "--share-device", "--config", str(config), "--steps", "3", "--warmup", "1",
-                          "--T", "50", "--N", "1024", "--no-cpu-baseline"],
+                          "--T", "50", "--N", "1024", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -138,11 +138,12 @@ def test_bench_launcher_ends_when_a_rank_dies_before_the_rendezvous():
 
 
 def test_bench_default_line_carries_every_baseline_config():
-    """One GPU, the driver's command shape: the config-2 headline plus `configs` = BASELINE configs 3 / 4 / 5, each
-    with its own roofline (and, without --no-cpu-baseline, an oracle cpu_baseline), none of them an error."""
+    """One GPU, the driver's command shape with --full: the config-2 headline plus `configs` = BASELINE configs
+    3 / 4 / 5, each with its own roofline (and, without --no-cpu-baseline, an oracle cpu_baseline), none of them an
+    error."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["roofline"]["traffic_source"].startswith("profiles/traffic_k1.json")
@@ -167,6 +168,60 @@ def test_bench_default_line_carries_every_baseline_config():
     assert set(pipe["stages_us"]) >= {"reward_step", "gae_scan_with_statistics", "normalise"} and pipe["us"] < 200
     assert set(c["config5_tail_world1"]["stages_ms"]) >= {"scan_with_fused_stats", "normalise"}
     assert line["per_step"]["config3_a3_ppo_sampling"] == c3["sampling"]
+
+
+def _bench_plain(args, timeout=300):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args],
+                         capture_output=True, text=True, timeout=timeout, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def _load_dump(d):
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain config-2 run (no --full) times exactly --steps steps and carries none of the secondary blocks;
+    --dump-outputs writes what the last timed step computed, in float32 / float64: the oracle's step on the same seeded
+    inputs, with the reward state carried in from the step before."""
+    from olympic_hip import specs
+    from olympic_hip.synthetic import h1_synthetic_block
+    from oracle import oracle as orc
+    T, N = 20, 512
+    line = _bench_plain(["--steps", "3", "--warmup", "1", "--T", str(T), "--N", str(N), "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "env-steps/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["metric"].startswith("env-steps/sec")
+    assert not {"configs", "per_step", "cpu_baseline", "config5_tail"} & set(line)
+    assert line["roofline"]["bound"] == "hbm" and "measured_copy_GBps" not in line["roofline"]
+    d = _load_dump(tmp_path)
+    assert set(d) == {"sample_rows", "obs", "reward", "absorbing", "ctrl", "prev"}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    spec = specs.unitree_h1("walk")
+    qpos, qvel, act = h1_synthetic_block(spec, T, N, seed=1234)
+    ref = orc.il_step(spec, qpos, qvel, act, orc.il_step(spec, qpos, qvel, act, np.full(N, 1.25))["prev"])
+    assert np.array_equal(d["sample_rows"], np.arange(T * N))             # [T,N] small enough: every row
+    assert np.array_equal(d["obs"], ref["obs"].reshape(T * N, -1))
+    assert np.array_equal(d["ctrl"], ref["ctrl"].reshape(T * N, -1))
+    assert np.array_equal(d["absorbing"], ref["absorbing"].reshape(-1))
+    assert np.abs(d["reward"] - ref["reward"].reshape(-1)).max() <= 1.2e-7
+    assert np.array_equal(d["prev"], ref["prev"])
+
+
+def test_bench_config5_plain_dumps_are_reproducible(tmp_path):
+    """Config 5 without --full: no stage times, no roofline, no CPU baseline; two runs with the same arguments dump the
+    same returns, normalised advantages and statistics bit for bit (seeded inputs)."""
+    args = ["--config", "5", "--steps", "3", "--warmup", "1", "--T", "50", "--N", "1024", "--dump-outputs"]
+    lines = [_bench_plain(args + [str(tmp_path / str(i))]) for i in range(2)]
+    assert all(not {"stages_ms", "roofline", "cpu_baseline"} & set(ln) and ln["steps"] == 3 for ln in lines)
+    a, b = _load_dump(tmp_path / "0"), _load_dump(tmp_path / "1")
+    assert set(a) == set(b) == {"sample_rows", "ret", "adv", "stats"}
+    assert all(a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes() for k in a)
+    assert a["stats"][0] == 50 * 1024 and a["ret"].shape == a["adv"].shape == (50 * 1024,)
+    adv = a["adv"].astype(np.float64)
+    assert abs(adv.mean()) < 1e-5 and abs(adv.std(ddof=1) - 1) < 1e-4
 
 
 def test_bench_fails_loudly_when_a_rank_fails():

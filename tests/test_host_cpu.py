@@ -14,7 +14,8 @@ from olympic_hip import _abi, specs
 from olympic_hip.trajectory import Trajectory
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_H1_XML = "/root/reference/olympic_mujoco/environments/data/unitree_h1/h1.xml"
+# the reference's UnitreeH1 MJCF, stored as a fixture (a scene file: no meshes are read)
+REF_H1_XML = os.path.join(ROOT, "tests", "golden", "h1.xml")
 
 
 # ------------------------------------------------------------------------------ specs
@@ -50,7 +51,6 @@ def test_h1_fall_thresholds_are_the_reference_doubles():
         specs.unitree_h1("walk", reward_type="bogus")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_H1_XML), reason="reference MJCF not present (GPU box)")
 def test_tables_rederived_from_mjcf():
     from olympic_hip.mjcf_tables import tables_from_mjcf
     arms = specs._H1_ARM_JOINTS
@@ -457,3 +457,24 @@ def test_reset_records_follow_walking_task_reset():
         seq = rr._sequence(r["phase"], 88, step_size=0.3, step_gap=0.15, step_height=step_h, num_steps=20, lateral=False)
         np.testing.assert_allclose(np.array(seq)[:, :2], r["seq"][:, :2], rtol=0, atol=0)
         np.testing.assert_allclose(np.array(seq)[:, 2], zs, rtol=1e-12, atol=1e-15)
+
+
+# ------------------------------------------------------------------------------ bench.py --dump-outputs
+def test_bench_dump_outputs_float_arrays_seeded_sample_and_budget(tmp_path):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32 / float64 (integers widened exactly); a
+    large [T,N] output is written on a fixed, seeded, sorted row sample; past the 64 MB budget nothing is written."""
+    import bench
+    arrays = {"u8": np.array([0, 3, 255], np.uint8), "i32": np.array([-7, 2 ** 31 - 1], np.int32),
+              "f32": np.array([1.5], np.float32), "f64": np.array([np.pi])}
+    assert bench.dump_outputs(str(tmp_path / "d"), arrays) == 3 * 4 + 2 * 8 + 4 + 8
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "d" / f"{k}.npy")
+        assert b.dtype == {"u8": np.float32, "i32": np.float64, "f32": np.float32, "f64": np.float64}[k]
+        assert np.array_equal(b, a)
+    s = bench.dump_row_sample(400 * 4096)
+    assert len(s) == bench.DUMP_SAMPLE_ROWS and np.array_equal(s, bench.dump_row_sample(400 * 4096))
+    assert (np.diff(s) > 0).all() and 0 <= s[0] and s[-1] < 400 * 4096
+    assert np.array_equal(bench.dump_row_sample(1000), np.arange(1000))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1)})
+    assert not os.path.exists(tmp_path / "big")

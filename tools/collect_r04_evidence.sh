@@ -5,8 +5,8 @@ O=$R/gpurun_out/r04
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. the driver's command, un-profiled and under rocprofv3 (kernel trace + stats)
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2>/tmp/bench.err || tail -5 /tmp/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o b -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_cmd_under_rocprof.json 2>/tmp/prof.err || tail -5 /tmp/prof.err
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2>/tmp/bench.err || tail -5 /tmp/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o b -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_driver_cmd_under_rocprof.json 2>/tmp/prof.err || tail -5 /tmp/prof.err
 cp $(find /tmp/prof -name "*kernel_stats.csv" | head -1) $O/bench_default_cmd_kernel_stats.csv
 python3 $R/tools/trace_summary.py $(find /tmp/prof -name "*kernel_trace.csv" | head -1) > $O/bench_default_cmd_kernel_summary.csv
 # 2. whole config-3 iterations with the kernel update, under rocprofv3
