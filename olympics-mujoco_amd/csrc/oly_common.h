@@ -74,6 +74,7 @@ struct oly_ctx {
   bool roll_attr_done = false;  // same for the persistent rollout kernel (K13)
   unsigned upd_attr_done = 0;   // same for the update kernel's instantiations (K14)
   unsigned scan_attr_done = 0;  // dynamic-LDS limit of the pipelined scan kernels raised on this device
+  unsigned ilmlp_attr_done = 0; // same for the imitation-MLP forward's instantiations (K16)
   int num_cu;
 };
 

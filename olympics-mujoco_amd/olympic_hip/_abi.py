@@ -116,7 +116,7 @@ A3_PHYSICS_FN = C.CFUNCTYPE(None, C.c_int, C.POINTER(C.c_double), C.POINTER(A3Re
 
 # name -> (restype, argtypes); device/host pointers are void*.
 STD_SCALAR, STD_PER_DIM, STD_FULL = 0, 1, 2
-ABI_VERSION = 7          # OLY_ABI_VERSION of include/olympic_hip.h this table mirrors
+ABI_VERSION = 8          # OLY_ABI_VERSION of include/olympic_hip.h this table mirrors
 
 
 class AdamNet(C.Structure):
@@ -142,6 +142,17 @@ class PPOUpdate(C.Structure):
                 ("act_src", vp), ("act_sign", vp),
                 ("clip", C.c_float), ("vf_coeff", C.c_float), ("mirror_coeff", C.c_float), ("pad1", C.c_int32),
                 ("grad_actor", vp), ("grad_critic", vp), ("scal_out", vp), ("ws", vp), ("ws_floats", C.c_int64), ("gnorm_ws", vp)]
+
+ACT_IDENTITY, ACT_TANH = 0, 1
+
+
+class ILCriticFit(C.Structure):
+    """oly_il_critic_fit (K16): the imitation critic's fit state for oly_il_critic_fit_epoch."""
+    _fields_ = [("in_dim", C.c_int32), ("step", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("x", vp), ("v_target", vp), ("colstats", vp),
+                ("param", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("packed", vp), ("ws", vp),
+                ("ws_floats", C.c_int64), ("loss_out", vp)]
+
 
 SIGNATURES = {
     "oly_strerror": (C.c_char_p, [C.c_int]),
@@ -225,6 +236,11 @@ SIGNATURES = {
     "oly_ppo_update_grads": (C.c_int, [vp, C.POINTER(PPOUpdate), vp]),
     "oly_ppo_adam_step": (C.c_int, [vp, C.POINTER(PPOAdam), vp]),
     "oly_ppo_update_epoch": (C.c_int, [vp, C.POINTER(PPOUpdate), C.POINTER(PPOAdam), vp, C.c_int, vp, vp]),
+    "oly_ilmlp_packed_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "oly_ilmlp_pack": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 8),
+    "oly_ilmlp_forward": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int] + [vp] * 7),
+    "oly_il_critic_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "oly_il_critic_fit_epoch": (C.c_int, [vp, C.POINTER(ILCriticFit), vp, C.c_int, C.c_int, vp]),
     "oly_event_create": (C.c_int, [C.POINTER(vp)]),
     "oly_event_destroy": (C.c_int, [vp]),
     "oly_event_record": (C.c_int, [vp, vp]),

@@ -72,6 +72,8 @@ class Context:
         self.device = torch.device("cuda", int(device) if not isinstance(device, torch.device)
                                    else (device.index or 0))
         self._h = C.c_void_p()
+        if _DEFERRED and not _capturing():
+            _flush_deferred()
         check(None, lib().oly_create(C.byref(self._h), self.device.index), "oly_create")
         self._keep = []
 
@@ -97,7 +99,13 @@ class Context:
 
     def close(self):
         if self._h:
-            lib().oly_destroy(self._h)
+            if _capturing():
+                # oly_destroy frees device tables (hipFree), which would invalidate a graph capture in progress on this
+                # thread: a context dropped inside `torch.cuda.graph` (e.g. by the cycle collector) is freed later
+                _DEFERRED.append(self._h)
+            else:
+                _flush_deferred()
+                lib().oly_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -105,6 +113,19 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+_DEFERRED = []        # contexts released during a stream capture, destroyed at the next close() outside one
+
+
+def _capturing():
+    import torch
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def _flush_deferred():
+    while _DEFERRED:
+        lib().oly_destroy(_DEFERRED.pop())
 
 
 class HipTimer:

@@ -602,6 +602,96 @@ class Engine:
         a.step = int(first_step)
         self.ctx.call("oly_ppo_update_epoch", C.byref(u), C.byref(a), ptr(perm), n_batches, ptr(scal_out), self._s())
 
+    # -------------------------------------------------------------- K16 (imitation MLP forward, critic fit)
+    def ilmlp_pack(self, w1, b1, w2, b2, w3, b3, packed=None):
+        """torch Linear parameters of the relu MLP in -> 512 -> 256 -> out -> packed operand stream."""
+        from ._ffi import lib
+        f32, dv = torch.float32, self.device
+        if w1.dim() != 2 or w2.dim() != 2 or w3.dim() != 2:
+            raise OlyError("ilmlp_pack: weights must be 2-D")
+        h1, in_dim = (int(v) for v in w1.shape)
+        h2, out_dim = int(w2.shape[0]), int(w3.shape[0])
+        n = int(lib().oly_ilmlp_packed_floats(in_dim, h1, h2, out_dim))
+        if n < 0 or int(w2.shape[1]) != h1 or int(w3.shape[1]) != h2:
+            raise OlyError(f"ilmlp_pack: unsupported MLP shape {in_dim} -> {h1} -> {tuple(w2.shape)} -> {tuple(w3.shape)}")
+        for t, name, shape in ((w1, "w1", (h1, in_dim)), (b1, "b1", (h1,)), (w2, "w2", (h2, h1)), (b2, "b2", (h2,)),
+                               (w3, "w3", (out_dim, h2)), (b3, "b3", (out_dim,))):
+            _req(t, name, shape, f32, dv)
+        packed = _req(packed if packed is not None else self._new((n,), f32), "packed", (n,), f32, dv)
+        self.ctx.call("oly_ilmlp_pack", in_dim, h1, h2, out_dim, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
+                      ptr(packed), self._s())
+        return packed
+
+    def ilmlp_forward(self, x, packed, out_dim, act="identity", colstats=None, mean=None, std=None, y=None):
+        """y [N,out] = net(standardise(x)); x [N,in] f32; standardisation from colstats [3,in] f64, or mean / std [in]
+        f64, or none.  act: "identity" or "tanh" (the last activation)."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [N,in] tensor")
+        N, in_dim = (int(v) for v in x.shape)
+        out_dim = int(out_dim)
+        n = int(lib().oly_ilmlp_packed_floats(in_dim, 512, 256, out_dim))
+        if n < 0:
+            raise OlyError(f"ilmlp_forward: unsupported shape in={in_dim} out={out_dim}")
+        if act not in ("identity", "tanh"):
+            raise OlyError(f"ilmlp_forward: last activation {act!r} is not identity or tanh")
+        if (mean is None) != (std is None) or (mean is not None and colstats is not None):
+            raise OlyError("ilmlp_forward: give colstats, or mean and std, or neither")
+        _req(x, "x", (N, in_dim), f32, dv)
+        _req(packed, "packed", (n,), f32, dv)
+        _req(colstats, "colstats", (3, in_dim), f64, dv, optional=True)
+        _req(mean, "mean", (in_dim,), f64, dv, optional=True)
+        _req(std, "std", (in_dim,), f64, dv, optional=True)
+        y = _req(y if y is not None else self._new((N, out_dim), f32), "y", (N, out_dim), f32, dv)
+        self.ctx.call("oly_ilmlp_forward", N, in_dim, out_dim, _abi.ACT_TANH if act == "tanh" else _abi.ACT_IDENTITY,
+                      ptr(x), ptr(mean), ptr(std), ptr(colstats), ptr(packed), ptr(y), self._s())
+        return y
+
+    def il_critic_fit_ws(self, batch, in_dim):
+        """A workspace for il_critic_fit_epoch with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_il_critic_fit_ws_floats(int(batch), int(in_dim)))
+        if n < 0:
+            raise OlyError(f"il_critic_fit: unsupported batch={batch} in={in_dim} (0 < batch <= 256, in <= 64)")
+        return self._new((n,), torch.float32)
+
+    def il_critic_fit_epoch(self, x, v_target, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed, ws, step,
+                            lr, beta1=0.9, beta2=0.999, eps=1e-8, loss_out=None):
+        """oly_il_critic_fit_epoch: one epoch of the critic's minibatch loop in one call.  x [n,in] f32 raw rows,
+        v_target [n] (or [n,1]) f32, perm [n] int32, param / exp_avg / exp_avg_sq flat in torch order, packed the
+        ilmlp_pack stream of param; step = Adam steps taken before.  Returns loss_out [n_batches] f64."""
+        from ._ffi import lib
+        f32, dv = torch.float32, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [n,in] tensor")
+        n, in_dim = (int(v) for v in x.shape)
+        batch = int(batch)
+        nws = int(lib().oly_il_critic_fit_ws_floats(batch, in_dim))
+        if nws < 0:
+            raise OlyError(f"il_critic_fit_epoch: unsupported batch={batch} in={in_dim} (0 < batch <= 256, in <= 64)")
+        nb = (n + batch - 1) // batch
+        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 256 + 1
+        _req(x, "x", (n, in_dim), f32, dv)
+        _req(v_target, "v_target", tuple(v_target.shape) if v_target.dim() == 2 and int(v_target.shape[-1]) == 1
+             else (n,), f32, dv)
+        if v_target.numel() != n:
+            raise OlyError(f"v_target: {v_target.numel()} values for {n} rows")
+        _req(perm, "perm", (n,), torch.int32, dv)
+        _req(colstats, "colstats", (3, in_dim), torch.float64, dv)
+        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (int(lib().oly_ilmlp_packed_floats(in_dim, 512, 256, 1)),), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), torch.float64), "loss_out", (nb,),
+                        torch.float64, dv)
+        f = _abi.ILCriticFit(in_dim=in_dim, step=int(step), lr=float(lr), beta1=float(beta1), beta2=float(beta2),
+                             eps=float(eps), x=x.data_ptr(), v_target=v_target.data_ptr(), colstats=colstats.data_ptr(),
+                             param=param.data_ptr(), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(),
+                             packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr())
+        self.ctx.call("oly_il_critic_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
+        return loss_out
+
     # -------------------------------------------------------------- K6
     def return_scan(self, mode, gamma, lam, rew, val, next_val, flags, ret=None, adv=None, stats3=None):
         """rew [T,N] float32, or float64 (RETURN mode: the un-narrowed reward of env.step).  With
