@@ -4,7 +4,7 @@ discriminator reward (K12), GAE + advantage normalisation (K6 + K7) and the crit
 GPU.  The policy step is the caller's: here a stand-in that only reports the advantages it was handed (TRPO itself is
 not part of this repository).  The policy is a random one on the kinematic stand-in physics.
 
-    python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3
+    python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device]
 """
 import argparse
 import os
@@ -16,7 +16,7 @@ import torch  # noqa: E402
 from olympic_hip.envs import LocoEnvBase  # noqa: E402
 from olympic_hip.gail import (DeviceStandardizer, DiscriminatorReward, DiscriminatorTrainer,  # noqa: E402
                               VariationalDiscriminator, VDBLoss)
-from olympic_hip.il_agent import DeviceILCritic, VAILAgent  # noqa: E402
+from olympic_hip.il_agent import DeviceDiscriminatorTrainer, DeviceILCritic, VAILAgent  # noqa: E402
 
 
 def policy_step(obs, act, adv, agent):
@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--disc-fit", choices=("torch", "device"), default="torch",
+                    help="the discriminator's training: DiscriminatorTrainer (torch) or DeviceDiscriminatorTrainer (K15)")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
@@ -38,7 +40,11 @@ def main():
     n_obs, n_act = vec.spec.n_obs, vec.spec.n_act
     demo = env.create_dataset()["states"]
     disc = DiscriminatorReward(eng, VariationalDiscriminator(n_obs).cuda(), state_mask=vec.get_kinematic_obs_mask())
-    trainer = DiscriminatorTrainer(disc, demo, VDBLoss(info_constraint=0.1, lr_beta=1e-5), lr=5e-5)
+    if args.disc_fit == "device":     # the reference's minibatch loop, disc_batch_size 2048 (confs.yaml)
+        trainer = DeviceDiscriminatorTrainer(disc, demo, VDBLoss(info_constraint=0.1, lr_beta=1e-5), lr=5e-5,
+                                             batch_size=2048)
+    else:
+        trainer = DiscriminatorTrainer(disc, demo, VDBLoss(info_constraint=0.1, lr_beta=1e-5), lr=5e-5)
     # the critic of examples/imitation_learning/utils.py:136-149: obs -> [512, 256] -> 1, the policy's standardizer
     lins = [torch.nn.Linear(n_obs, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
     trpo_standardizer = DeviceStandardizer(eng, n_obs)

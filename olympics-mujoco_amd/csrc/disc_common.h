@@ -1,0 +1,67 @@
+// Pieces of the fused discriminator forward (K12, csrc/k12_disc_forward.hip) that the discriminator's fit (K15,
+// csrc/k15_disc_fit.hip) shares: the packed operand stream's layout and the float32 exp of the reparameterisation.
+#pragma once
+#include "oly_common.h"
+
+namespace oly_disc {
+constexpr int H1 = 256;          // encoder hidden width
+constexpr int H2 = 128;          // encoder output width
+constexpr int ZD = 128;          // latent width
+constexpr int MAX_IN = 64;
+
+struct DiscLayout {
+  int in_dim, g1;                // g1: groups of four k-steps (8 k values) in layer 1: 4 (in <= 32) or 8
+  size_t w0, b0, w1, b1, wmu, bmu, wlv, blv, wd, bd;
+  // the same matrices as 16-column-tile streams (mlp_tiles.h: P16[tile][group of 16 k][lane][4]) for the 16-row
+  // kernel that small batches take
+  size_t w0n, w1n, wmun, wlvn;
+  size_t total;
+};
+constexpr int G1N16 = MAX_IN / 16;   // 16-wide layout, layer 1: 4 groups of 16 k (zero beyond in_dim)
+
+__host__ __device__ inline DiscLayout disc_layout(int in_dim) {
+  DiscLayout L;
+  L.in_dim = in_dim;
+  L.g1 = in_dim <= 32 ? 4 : 8;
+  L.w0 = 0;
+  L.b0 = L.w0 + (size_t)(H1 / 32) * L.g1 * 256;
+  L.w1 = L.b0 + H1;
+  L.b1 = L.w1 + (size_t)(H2 / 32) * (H1 / 8) * 256;
+  L.wmu = L.b1 + H2;
+  L.bmu = L.wmu + (size_t)(ZD / 32) * (H2 / 8) * 256;
+  L.wlv = L.bmu + ZD;
+  L.blv = L.wlv + (size_t)(ZD / 32) * (H2 / 8) * 256;
+  L.wd = L.blv + ZD;
+  L.bd = L.wd + ZD;
+  L.w0n = L.bd + 4;
+  L.w1n = L.w0n + (size_t)(H1 / 16) * G1N16 * 256;
+  L.wmun = L.w1n + (size_t)(H2 / 16) * (H1 / 16) * 256;
+  L.wlvn = L.wmun + (size_t)(ZD / 16) * (H2 / 16) * 256;
+  L.total = L.wlvn + (size_t)(ZD / 16) * (H2 / 16) * 256;
+  return L;
+}
+
+// exp in float32 from fma / rint / exponent arithmetic only, so that the oracle's copy returns the same bits:
+// n = rint(x log2 e), r = x - n ln2 (two-constant Cody-Waite), e^r = 1 + (r + r^2 P(r)) with a degree-5 minimax
+// P, result scaled by 2^n in two exact steps.  Within 1 ulp of exp over the whole float range (checked
+// against fp64 exp by tests/test_oracle_golden.py), the error class of torch's own float32 exp.
+__device__ __forceinline__ float pow2i(int e) { return __int_as_float((e + 127) << 23); }
+__device__ __forceinline__ float exp32(float x) {
+  if (x != x) return x;
+  if (x > 88.72283935546875f) return __int_as_float(0x7f800000);
+  if (x < -103.97208404541016f) return 0.f;
+  const float n = rintf(x * 1.4426950408889634f);
+  float r = fmaf(n, -0.693145751953125f, x);
+  r = fmaf(n, -1.428606765330187045e-06f, r);
+  float u = 0.000198527617612853646278381f;
+  u = fmaf(u, r, 0.00139304355252534151077271f);
+  u = fmaf(u, r, 0.00833336077630519866943359f);
+  u = fmaf(u, r, 0.0416664853692054748535156f);
+  u = fmaf(u, r, 0.166666671633720397949219f);
+  u = fmaf(u, r, 0.5f);
+  u = 1.0f + fmaf(r * r, u, r);
+  const int q = (int)n, q1 = q >> 1;
+  return (u * pow2i(q1)) * pow2i(q - q1);
+}
+
+}  // namespace oly_disc

@@ -75,6 +75,7 @@ struct oly_ctx {
   unsigned upd_attr_done = 0;   // same for the update kernel's instantiations (K14)
   unsigned scan_attr_done = 0;  // dynamic-LDS limit of the pipelined scan kernels raised on this device
   unsigned ilmlp_attr_done = 0; // same for the imitation-MLP forward's instantiations (K16)
+  unsigned discfit_attr_done = 0;  // same for the discriminator fit's row kernels (K15)
   int num_cu;
 };
 

@@ -154,6 +154,16 @@ class ILCriticFit(C.Structure):
                 ("ws_floats", C.c_int64), ("loss_out", vp)]
 
 
+class DiscFit(C.Structure):
+    """oly_disc_fit (K15): the VAIL discriminator's fit state for oly_disc_fit_epoch."""
+    _fields_ = [("in_dim", C.c_int32), ("n_plcy", C.c_int32), ("step", C.c_int32), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("weight_decay", C.c_float),
+                ("info_constraint", C.c_float), ("lr_beta", C.c_float), ("x", vp), ("targets", vp), ("eps", vp),
+                ("colstats", vp), ("param", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("packed", vp), ("beta", vp),
+                ("ws", vp), ("ws_floats", C.c_int64), ("loss_out", vp), ("bce_out", vp), ("kl_out", vp),
+                ("beta_out", vp)]
+
+
 SIGNATURES = {
     "oly_strerror": (C.c_char_p, [C.c_int]),
     "oly_last_error": (C.c_char_p, [vp]),
@@ -241,6 +251,8 @@ SIGNATURES = {
     "oly_ilmlp_forward": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int] + [vp] * 7),
     "oly_il_critic_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "oly_il_critic_fit_epoch": (C.c_int, [vp, C.POINTER(ILCriticFit), vp, C.c_int, C.c_int, vp]),
+    "oly_disc_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "oly_disc_fit_epoch": (C.c_int, [vp, C.POINTER(DiscFit), vp, C.c_int, C.c_int, vp]),
     "oly_event_create": (C.c_int, [C.POINTER(vp)]),
     "oly_event_destroy": (C.c_int, [vp]),
     "oly_event_record": (C.c_int, [vp, vp]),

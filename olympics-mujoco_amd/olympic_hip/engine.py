@@ -692,6 +692,61 @@ class Engine:
         self.ctx.call("oly_il_critic_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
         return loss_out
 
+    # -------------------------------------------------------------- K15 (VAIL discriminator fit)
+    def disc_fit_ws(self, batch, in_dim):
+        """A workspace for disc_fit_epoch with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_disc_fit_ws_floats(int(batch), int(in_dim)))
+        if n < 0:
+            raise OlyError(f"disc_fit: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
+        return self._new((n,), torch.float32)
+
+    def disc_fit_epoch(self, x, n_plcy, eps, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed, beta, ws, step,
+                       lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0, info_constraint=0.1, lr_beta=1e-5,
+                       targets=None, loss_out=None, bce_out=None, kl_out=None, beta_out=None):
+        """oly_disc_fit_epoch: one epoch of the discriminator's minibatch loop in one call.  x [n,in] f32 the masked
+        concatenated rows (policy rows first, n_plcy of them), eps [n,128] f32 noise in minibatch order, perm [n] int32,
+        param / exp_avg / exp_avg_sq flat in oly_disc_pack's order, packed the disc_pack stream (re-packed from param,
+        then kept current), beta [1] f32 VDBLoss's beta (read and written), targets [n] f32 or None (0 / 1); step =
+        Adam steps taken before.  Returns loss_out [n_batches] f64 (bce_out, kl_out f64 and beta_out f32 likewise
+        when given)."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [n,in] tensor")
+        n, in_dim = (int(v) for v in x.shape)
+        batch = int(batch)
+        nws = int(lib().oly_disc_fit_ws_floats(batch, in_dim))
+        if nws < 0:
+            raise OlyError(f"disc_fit_epoch: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
+        if not 0 <= int(n_plcy) <= n:
+            raise OlyError(f"disc_fit_epoch: n_plcy={n_plcy} outside [0, {n}]")
+        nb = (n + batch - 1) // batch
+        n_par = 256 * in_dim + 256 + 128 * 256 + 128 + 2 * (128 * 128 + 128) + 128 + 1
+        _req(x, "x", (n, in_dim), f32, dv)
+        _req(eps, "eps", (n, 128), f32, dv)
+        _req(perm, "perm", (n,), torch.int32, dv)
+        _req(targets, "targets", (n,), f32, dv, optional=True)
+        _req(colstats, "colstats", (3, in_dim), f64, dv)
+        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (int(lib().oly_disc_packed_floats(in_dim, 256, 128, 128)),), f32, dv)
+        _req(beta, "beta", (1,), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
+        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
+        _req(kl_out, "kl_out", (nb,), f64, dv, optional=True)
+        _req(beta_out, "beta_out", (nb,), f32, dv, optional=True)
+        f = _abi.DiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
+                         beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
+                         info_constraint=float(info_constraint), lr_beta=float(lr_beta), x=x.data_ptr(),
+                         targets=ptr(targets), eps=eps.data_ptr(), colstats=colstats.data_ptr(), param=param.data_ptr(),
+                         exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), packed=packed.data_ptr(),
+                         beta=beta.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
+                         bce_out=ptr(bce_out), kl_out=ptr(kl_out), beta_out=ptr(beta_out))
+        self.ctx.call("oly_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
+        return loss_out
+
     # -------------------------------------------------------------- K6
     def return_scan(self, mode, gamma, lam, rew, val, next_val, flags, ret=None, adv=None, stats3=None):
         """rew [T,N] float32, or float64 (RETURN mode: the un-narrowed reward of env.step).  With

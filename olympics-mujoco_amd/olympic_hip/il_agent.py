@@ -4,12 +4,15 @@
       evaluation                                          -> DeviceILCritic.__call__ (K16, oly_ilmlp_forward)
       Regressor.fit (mushroom's minibatch loop + Adam)    -> DeviceILCritic.fit (K16, oly_il_critic_fit_epoch)
   discriminator reward, GAE, advantage normalisation      -> DiscriminatorReward (K12), GAERollout (K6 + K7)
-  discriminator training                                  -> the caller's DiscriminatorTrainer (torch)
+  discriminator training (_fit_discriminator, :167-220)   -> DeviceDiscriminatorTrainer (K15, oly_disc_fit_epoch), or
+                                                             the caller's DiscriminatorTrainer (torch, a different
+                                                             reading: one Adam step per epoch on the whole batch)
   TRPO's policy step                                      -> the caller's policy_step
 
 The critic shares the policy's running Standardizer (trpo_standardizer, utils.py:123); every evaluation and every
 fit minibatch adds its rows to it, as Standardizer.forward does (networks.py:68-81).
 """
+import numpy as np
 import torch
 
 from ._ffi import OlyError
@@ -195,3 +198,124 @@ class VAILAgent:
         self.iter += 1
         return dict(reward=r, v_target=v_target, adv=adv, critic_loss=critic_loss, disc_loss=disc_loss,
                     disc_trained=trained)
+
+
+class DeviceDiscriminatorTrainer:
+    """_fit_discriminator (gail_TRPO.py:167-220) for VAIL, states only, on K15.  Per epoch:
+
+        plcy = plcy_obs[:, state_mask] (n rows); demo = the first m = min(n, rows) rows of a shuffle of the
+        demonstration states (minibatch_generator, :198-200); concat = [plcy; demo]; targets 0 / 1, or
+        U(0.01, 0.10) / U(0.80, 0.99) with use_noisy_targets
+        D_standardizer.update_mean_std(concat)                                       (:206, oly_col_stats)
+        mushroom's Regressor.fit over concat: a permutation cut into minibatches of batch_size, each
+        Standardizer.forward, VariationalNet.forward, VDBLoss (beta's dual update), backward, Adam     (K15)
+
+    Differences from the reference, all stated: the demo draw, the permutation, the noise and the noisy targets come
+    from the caller's torch.Generator (the reference uses np.random and torch's global generator), drawn in that
+    order per epoch; _discriminator_logging's extra forwards (:222-250), which update the statistics only when a
+    SummaryWriter is attached, are not replayed.
+
+    reward: the DiscriminatorReward whose network (VariationalDiscriminator, the K12 shape) and standardizer are
+    fitted; demo: an ExpertDataset (mask folded in) or an array of full observations; loss: a VDBLoss, whose
+    _beta is read at the start of every fit and written back once at its end.  Every fit starts from the module's
+    current parameters and writes the stepped ones back in place (the pointers DiscriminatorReward.prepared()
+    captured stay valid); the reward's packed stream is left current.  The optimiser's moments and step count
+    persist across fits."""
+
+    def __init__(self, reward, demo, loss, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, batch_size=2048,
+                 n_epochs=1, use_noisy_targets=False):
+        from .gail import ExpertDataset, VariationalDiscriminator, VDBLoss
+        if not isinstance(loss, VDBLoss):
+            raise OlyError("DeviceDiscriminatorTrainer: loss must be a VDBLoss (the VAIL discriminator)")
+        if loss._use_bernoulli_ent:
+            raise OlyError("DeviceDiscriminatorTrainer: use_bernoulli_ent=True is refused: the reference adds an "
+                           "unreduced tensor to the loss there (utils/math.py:64-68) and cannot run backward")
+        if not isinstance(reward.net, VariationalDiscriminator) or not reward.fused:
+            raise OlyError("DeviceDiscriminatorTrainer: supported network is VariationalDiscriminator "
+                           "in <= 64 -> 256 -> 128 -> (mu, logvar) 128 -> 1")
+        self.r, self.loss, self.eng = reward, loss, reward.eng
+        self.in_dim = int(reward.net.encoder[0].in_features)
+        self._mask_max = None if reward.mask is None else int(reward.mask.max())
+        self.batch = int(batch_size)
+        self._ws = self.eng.disc_fit_ws(self.batch, self.in_dim)
+        self.lr, self.betas, self.eps, self.wd = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
+        dev = self.eng.device
+        self.expert = demo if isinstance(demo, ExpertDataset) else None
+        self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
+                                                                         device=dev)
+        n_par = sum(int(p.numel()) for p in reward._params())
+        self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros_like(self.param)
+        self.exp_avg_sq = torch.zeros_like(self.param)
+        self.beta = torch.empty(1, dtype=torch.float32, device=dev)
+        self.step = 0
+
+    def _demo_rows(self, n, generator):
+        rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
+        idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
+        if self.expert is not None:
+            return self.expert.minibatch(idx)
+        d = self.demo[idx]
+        return d if self.r.mask is None else d[:, self.r.mask.long()]
+
+    @torch.no_grad()
+    def fit(self, plcy_obs, generator=None, eps=None):
+        """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations).  eps: the reparameterisation
+        noise, [n_epochs, n + m, 128] (or [n + m, 128] for one epoch) in minibatch order, or None (drawn from
+        `generator`).  Returns the per-minibatch losses, [n_epochs, n_batches] f64 on the device."""
+        r, eng, dev = self.r, self.eng, self.eng.device
+        plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
+        if self._mask_max is not None and int(plcy.shape[1]) <= self._mask_max:
+            raise OlyError(f"DeviceDiscriminatorTrainer.fit: {plcy.shape[1]} columns, the state mask reads column "
+                           f"{self._mask_max}")
+        if r.mask is not None:
+            plcy = plcy[:, r.mask.long()]
+        plcy = plcy.contiguous()
+        n = int(plcy.shape[0])
+        if n == 0:
+            raise OlyError("DeviceDiscriminatorTrainer.fit: no policy rows")
+        if int(plcy.shape[1]) != self.in_dim:
+            raise OlyError(f"DeviceDiscriminatorTrainer.fit: {plcy.shape[1]} masked columns, the network takes {self.in_dim}")
+        ps = r._params()
+        torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=self.param)
+        self.beta.fill_(float(self.loss._beta))
+        if r._packed is None:
+            r.packed()
+        st = r.stand
+        if getattr(st, "_fresh", False):     # the running sums start from zero; the fit adds to them in place
+            st.colstats.zero_()
+            st._fresh = False
+        losses = None
+        for e in range(self.n_epochs):
+            demo = self._demo_rows(n, generator)
+            x = torch.cat([plcy, demo]).contiguous()
+            rows = int(x.shape[0])
+            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206
+            targets = None
+            if self.noisy:                                          # :209-211: demo targets drawn first
+                demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
+                plcy_t = torch.empty(n, device=dev).uniform_(0.01, 0.10, generator=generator)
+                targets = torch.cat([plcy_t, demo_t[:rows - n]]).contiguous()
+            perm = torch.randperm(rows, generator=generator, device=dev).to(torch.int32)
+            if eps is None:
+                noise = torch.randn((rows, 128), device=dev, generator=generator)
+            else:
+                noise = eps[e] if eps.dim() == 3 else eps
+            nb = (rows + self.batch - 1) // self.batch
+            if losses is None:
+                losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
+            eng.disc_fit_epoch(x, n, noise.to(torch.float32).contiguous(), perm, self.batch, st.colstats, self.param,
+                               self.exp_avg, self.exp_avg_sq, r._packed, self.beta, self._ws, self.step, self.lr,
+                               beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps, weight_decay=self.wd,
+                               info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta, targets=targets,
+                               loss_out=losses[e])
+            self.step += nb
+        o = 0
+        for p in ps:                                                # in place: captured pointers stay valid
+            k = int(p.numel())
+            p.data.copy_(self.param[o:o + k].view_as(p))
+            o += k
+        r.invalidate()
+        self.loss._beta = float(self.beta)                           # the one host read-back of the call
+        return losses

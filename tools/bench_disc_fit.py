@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""K15 measurements, one JSON line: the discriminator-fit epoch call per minibatch of 2048 at the H1 kinematic width
+(32) against the same loop in torch on the same GPU, written as the reference runs it (Standardizer update, forward,
+VDBLoss with beta's Python max, backward, torch.optim.Adam, loss.item()); DeviceDiscriminatorTrainer.fit at the
+reference launcher's size (n = 1000: one minibatch of 2000 rows) and at [100, 4096] (400 minibatches); VAILAgent.fit
+on [100, 4096] with and without a discriminator call.  HIP events on the stream; every shape is warmed up first.
+
+    python tools/bench_disc_fit.py [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "olympics-mujoco_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+IN, BATCH = 32, 2048
+FLOP_PER_ROW = 3 * 2 * (IN * 256 + 256 * 128 + 2 * 128 * 128 + 128) - 2 * IN * 256   # forward, weight and data grads
+
+
+def timed(fn, reps, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def wall(fn, reps, warmup=1):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from olympic_hip.engine import Engine
+    from olympic_hip.gail import DeviceStandardizer, DiscriminatorReward, VariationalDiscriminator, VDBLoss
+    from olympic_hip.il_agent import DeviceDiscriminatorTrainer, DeviceILCritic, VAILAgent
+    eng = Engine(0)
+    torch.manual_seed(0)
+    res = {"device": torch.cuda.get_device_name(0)}
+
+    # ---- the epoch call: 131 072 rows, 64 minibatches of 2048
+    n = 131072
+    nb = n // BATCH
+    net = VariationalDiscriminator(in_dim=IN).cuda()
+    x = (torch.randn((n, IN), device="cuda") * 1.3 + 0.2).contiguous()
+    eps = torch.randn((n, 128), device="cuda")
+    perm = torch.randperm(n, device="cuda").to(torch.int32)
+    flat = torch.cat([p.detach().reshape(-1) for p in (net.encoder[0].weight, net.encoder[0].bias, net.encoder[1].weight,
+                                                        net.encoder[1].bias, net.mu_out.weight, net.mu_out.bias,
+                                                        net.logvar_out.weight, net.logvar_out.bias, net.decoder.weight,
+                                                        net.decoder.bias)]).contiguous()
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+    packed = eng.disc_pack(*[p.detach().contiguous() for p in DiscriminatorReward(eng, net)._params()])
+    beta = torch.full((1,), 0.1, device="cuda")
+    cs = eng.col_stats(x)
+    ws = eng.disc_fit_ws(BATCH, IN)
+    step = [0]
+
+    def epoch():
+        eng.disc_fit_epoch(x, n // 2, eps, perm, BATCH, cs, flat, m, v, packed, beta, ws, step[0], 5e-5,
+                           info_constraint=0.1, lr_beta=1e-5)
+        step[0] += nb
+    ms = timed(epoch, 5)
+    res["fit_us_per_minibatch_2048"] = ms * 1e3 / nb
+    res["fit_tflops"] = FLOP_PER_ROW * n / (ms * 1e-3) / 1e12
+
+    # torch: the reference's loop on the same GPU (statistics on the device instead of numpy)
+    tnet = VariationalDiscriminator(in_dim=IN).cuda()
+    opt = torch.optim.Adam(tnet.parameters(), lr=5e-5, weight_decay=0.0)
+    loss_fn = VDBLoss(info_constraint=0.1, lr_beta=1e-5)
+    tcs = torch.zeros((3, IN), dtype=torch.float64, device="cuda")
+    p64 = perm.long()
+    target = (torch.arange(n, device="cuda") >= n // 2).float()
+    n_torch = 32
+
+    def torch_loop():
+        for b in range(n_torch):
+            idx = p64[b * BATCH:(b + 1) * BATCH]
+            xd = x[idx].double()
+            tcs[0] += BATCH
+            tcs[1] += xd.sum(0)
+            tcs[2] += (xd * xd).sum(0)
+            cnt = tcs[0] + 1e-2
+            mean = tcs[1] / cnt
+            sd = torch.sqrt(torch.clamp((tcs[2] + 1e-2) / cnt - mean * mean, min=1e-2))
+            mu, logvar = tnet.encode(((xd - mean) / sd).float())
+            z = mu + torch.exp(logvar / 2) * torch.randn_like(mu)
+            loss = loss_fn((tnet.decoder(z), mu, logvar), target[idx])      # beta's Python max: a host round trip
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            loss.item()
+    ms_t = timed(torch_loop, 3, warmup=1)
+    res["torch_us_per_minibatch_2048"] = ms_t * 1e3 / n_torch
+    res["fit_speedup"] = res["torch_us_per_minibatch_2048"] / res["fit_us_per_minibatch_2048"]
+
+    # ---- DeviceDiscriminatorTrainer.fit: n = 1000 (one minibatch of 2000) and [100, 4096] (400 minibatches)
+    # as many demonstration rows as policy rows at [100, 4096], so that every fit draws m = n of them
+    demo = np.random.default_rng(0).normal(0.2, 1.0, (100 * 4096, IN)).astype(np.float32)
+    r = DiscriminatorReward(eng, VariationalDiscriminator(in_dim=IN).cuda())
+    tr = DeviceDiscriminatorTrainer(r, demo, VDBLoss(info_constraint=0.1, lr_beta=1e-5))
+    g = torch.Generator(device="cuda").manual_seed(0)
+    small = torch.randn((1000, IN), device="cuda")
+    res["trainer_fit_n1000_ms"] = wall(lambda: tr.fit(small, generator=g), 20, warmup=3)
+    big = torch.randn((100 * 4096, IN), device="cuda")
+    res["trainer_fit_100x4096_ms"] = wall(lambda: tr.fit(big, generator=g), 3)
+    res["trainer_fit_100x4096_minibatches"] = (2 * 100 * 4096 + BATCH - 1) // BATCH
+
+    # ---- VAILAgent.fit, [T=100, N=4096], no-op policy step, with and without the discriminator's fit
+    T, N = 100, 4096
+    s = torch.randn((T + 1, N, IN), device="cuda")
+    last = torch.zeros((T, N), dtype=torch.bool, device="cuda")
+    last[-1] = True
+    ds = dict(state=s[:-1], action=torch.randn((T, N, 11), device="cuda"), reward=torch.randn((T, N), device="cuda"),
+              next_state=s[1:], absorbing=torch.zeros((T, N), dtype=torch.bool, device="cuda"), last=last)
+    for key, every in (("vail_fit_100x4096_with_disc_ms", 1), ("vail_fit_100x4096_without_disc_ms", 10 ** 9)):
+        lins = [torch.nn.Linear(IN, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
+        rr = DiscriminatorReward(eng, VariationalDiscriminator(in_dim=IN).cuda())
+        agent = VAILAgent(eng, rr, DeviceDiscriminatorTrainer(rr, demo, VDBLoss(0.1, 1e-5)),
+                          DeviceILCritic(eng, lins, DeviceStandardizer(eng, IN)), lambda o, a, adv, ag: None,
+                          train_D_n_th_epoch=every)
+        res[key] = wall(lambda: agent.fit(ds, generator=g), 2)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
