@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """VAILAgent.fit on UnitreeH1: one GAIL_TRPO.fit (imitation_lib/imitation/gail_TRPO.py:105-165) per call with the
 discriminator reward (K12), GAE + advantage normalisation (K6 + K7) and the critic's evaluation and fit (K16) on the
-GPU.  The policy step is the caller's: here a stand-in that only reports the advantages it was handed (TRPO itself is
-not part of this repository).  The policy is a random one on the kinematic stand-in physics.
+GPU.  The policy step is the caller's.  By default it is a stand-in that only reports the advantages it was handed, and
+the policy is a random one on the kinematic stand-in physics.  With --policy device the actions come from a
+DeviceGaussianPolicy (obs -> [512, 256] -> act, std_0 0.5) and DeviceTRPO (K17) trains it with UnitreeH1's confs.yaml
+values (max_kl 5e-3, ent_coeff 1e-3, n_epochs_cg 25).
 
-    python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device]
+    python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device]
 """
 import argparse
 import os
@@ -16,7 +18,8 @@ import torch  # noqa: E402
 from olympic_hip.envs import LocoEnvBase  # noqa: E402
 from olympic_hip.gail import (DeviceStandardizer, DiscriminatorReward, DiscriminatorTrainer,  # noqa: E402
                               VariationalDiscriminator, VDBLoss)
-from olympic_hip.il_agent import DeviceDiscriminatorTrainer, DeviceILCritic, VAILAgent  # noqa: E402
+from olympic_hip.il_agent import (DeviceDiscriminatorTrainer, DeviceGaussianPolicy, DeviceILCritic,  # noqa: E402
+                                  DeviceTRPO, VAILAgent)
 
 
 def policy_step(obs, act, adv, agent):
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--disc-fit", choices=("torch", "device"), default="torch",
                     help="the discriminator's training: DiscriminatorTrainer (torch) or DeviceDiscriminatorTrainer (K15)")
+    ap.add_argument("--policy", choices=("random", "device"), default="random",
+                    help="random actions and a stand-in policy step, or DeviceGaussianPolicy trained by DeviceTRPO (K17)")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
@@ -49,7 +54,12 @@ def main():
     lins = [torch.nn.Linear(n_obs, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
     trpo_standardizer = DeviceStandardizer(eng, n_obs)
     critic = DeviceILCritic(eng, lins, trpo_standardizer, lr=1e-4)
-    agent = VAILAgent(eng, disc, trainer, critic, policy_step, gamma=0.99, lam=0.97, env_reward_frac=0.0,
+    step, policy = policy_step, None
+    if args.policy == "device":     # the policy of utils.py:126-134 with UnitreeH1's confs.yaml values
+        pol_lins = [torch.nn.Linear(n_obs, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, n_act)]
+        policy = DeviceGaussianPolicy(eng, pol_lins, trpo_standardizer, std_0=0.5)
+        step = DeviceTRPO(policy, max_kl=5e-3, ent_coeff=1e-3, n_epochs_cg=25)
+    agent = VAILAgent(eng, disc, trainer, critic, step, gamma=0.99, lam=0.97, env_reward_frac=0.0,
                       train_D_n_th_epoch=3, critic_fit_params=dict(n_epochs=3, batch_size=256))
     T, N = args.steps, args.num_envs
     x = torch.empty((T + 1, N, n_obs), dtype=torch.float32, device="cuda")
@@ -60,7 +70,10 @@ def main():
     x[0] = vec.reset().to(torch.float32)
     for it in range(args.iters):
         for t in range(T):
-            act[t].uniform_(-1, 1, generator=gen)
+            if policy is None:
+                act[t].uniform_(-1, 1, generator=gen)
+            else:
+                act[t] = policy.draw_action(x[t], generator=gen)
             o, r, a, info = vec.step(act[t])
             x[t + 1], r_env[t], absorbing[t], last[t] = o.to(torch.float32), r, a, info["last"]
         last[-1] = True
@@ -69,8 +82,16 @@ def main():
         loss = out["critic_loss"]
         print(f"iter {it}: reward mean {float(out['reward'].mean()):.4f}; critic loss {float(loss[0, 0]):.4f} -> "
               f"{float(loss[-1, -1]):.4f} over {loss.numel()} minibatches; discriminator trained: {out['disc_trained']}")
+        if policy is not None:
+            sc = step.scalars()
+            improve = sc["J"] - sc["prev_loss"]
+            ok = sc["kl"] <= 1.5 * 5e-3 or improve >= 0
+            print(f"  TRPO: CG iterations {sc['cg_iters']:.0f}, accepted j {sc['accepted_j']:.0f}, kl {sc['kl']:.3e}, "
+                  f"improvement {improve:+.3e}" + ("" if sc["accepted_j"] < 0 or ok else "  (acceptance rule violated)"))
         x[0] = x[-1]
     critic.sync_to_torch()
+    if policy is not None:
+        policy.sync_to_torch()
 
 
 if __name__ == "__main__":

@@ -164,6 +164,19 @@ class DiscFit(C.Structure):
                 ("beta_out", vp)]
 
 
+OLY_TRPO_ACCEPT_OR, OLY_TRPO_ACCEPT_AND, OLY_TRPO_SCALARS = 0, 1, 8
+
+
+class TRPOStep(C.Structure):
+    """oly_trpo_step_args (K17): one TRPO policy step, or the gradient / FVP pieces."""
+    _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32),
+                ("out_dim", C.c_int32), ("last_act", C.c_int32), ("n_epochs_cg", C.c_int32),
+                ("n_epochs_line_search", C.c_int32), ("accept_rule", C.c_int32), ("max_kl", C.c_float),
+                ("ent_coeff", C.c_float), ("cg_damping", C.c_float), ("cg_residual_tol", C.c_float),
+                ("obs", vp), ("act", vp), ("adv", vp), ("colstats", vp), ("theta", vp), ("packed", vp), ("ws", vp),
+                ("ws_floats", C.c_int64), ("stepdir_out", vp), ("full_step_out", vp), ("scal_out", vp)]
+
+
 SIGNATURES = {
     "oly_strerror": (C.c_char_p, [C.c_int]),
     "oly_last_error": (C.c_char_p, [vp]),
@@ -253,6 +266,11 @@ SIGNATURES = {
     "oly_il_critic_fit_epoch": (C.c_int, [vp, C.POINTER(ILCriticFit), vp, C.c_int, C.c_int, vp]),
     "oly_disc_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "oly_disc_fit_epoch": (C.c_int, [vp, C.POINTER(DiscFit), vp, C.c_int, C.c_int, vp]),
+    "oly_trpo_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "oly_trpo_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
+    "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
+    "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),
     "oly_event_create": (C.c_int, [C.POINTER(vp)]),
     "oly_event_destroy": (C.c_int, [vp]),
     "oly_event_record": (C.c_int, [vp, vp]),

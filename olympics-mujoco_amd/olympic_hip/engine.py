@@ -748,6 +748,91 @@ class Engine:
         return loss_out
 
     # -------------------------------------------------------------- K6
+    # -------------------------------------------------------------- K17 (TRPO's policy step)
+    def trpo_args(self, obs, act, adv, colstats, theta, max_kl=0.01, ent_coeff=0.0, n_epochs_cg=10, cg_damping=1e-1,
+                  cg_residual_tol=1e-10, n_epochs_line_search=10, accept_rule="or", ws=None, packed=None,
+                  stepdir_out=None, full_step_out=None, scal_out=None, last_act="identity", hidden=(512, 256)):
+        """The oly_trpo_step_args block for obs [n,in] f32, act [n,out] f32, adv [n] (or [n,1]) f32, colstats [3,in]
+        f64 (the live Standardizer) and theta [n_par] f32 (W1|b1|W2|b2|W3|b3|log_sigma).  Every shape is checked
+        here, before anything can launch.  Returns (args, keep): keep holds the tensors the block points into."""
+        from ._ffi import lib
+        f32, dv = torch.float32, self.device
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or not isinstance(act, torch.Tensor) or act.dim() != 2:
+            raise OlyError("trpo: obs [n,in] and act [n,out] must be 2-D tensors")
+        n, in_dim = (int(v) for v in obs.shape)
+        out_dim = int(act.shape[1])
+        if last_act != "identity":
+            raise OlyError(f"trpo: the last activation must be identity (got {last_act!r}); a tanh mean is not supported")
+        h1, h2 = (int(v) for v in hidden)
+        n_par = int(lib().oly_trpo_param_count(in_dim, h1, h2, out_dim))
+        if n_par < 0:
+            raise OlyError(f"trpo: unsupported policy {in_dim} -> {h1} -> {h2} -> {out_dim} (in <= 64 -> 512 -> 256 -> out <= 32)")
+        if n <= 0:
+            raise OlyError("trpo: no rows")
+        if accept_rule not in ("or", "and"):
+            raise OlyError(f"trpo: accept_rule must be 'or' or 'and' (got {accept_rule!r})")
+        if int(n_epochs_cg) < 1 or int(n_epochs_line_search) < 0:
+            raise OlyError("trpo: n_epochs_cg >= 1 and n_epochs_line_search >= 0")
+        nws = int(lib().oly_trpo_ws_floats(n, in_dim, h1, h2, out_dim))
+        _req(obs, "obs", (n, in_dim), f32, dv)
+        _req(act, "act", (n, out_dim), f32, dv)
+        _req(adv, "adv", tuple(adv.shape) if adv.dim() == 2 and int(adv.shape[-1]) == 1 else (n,), f32, dv)
+        if adv.numel() != n:
+            raise OlyError(f"adv: {adv.numel()} values for {n} rows")
+        _req(colstats, "colstats", (3, in_dim), torch.float64, dv)
+        _req(theta, "theta", (n_par,), f32, dv)
+        ws = _req(ws if ws is not None else self._new((nws,), f32), "ws", (nws,), f32, dv)
+        _req(packed, "packed", (int(lib().oly_ilmlp_packed_floats(in_dim, h1, h2, out_dim)),), f32, dv, optional=True)
+        _req(stepdir_out, "stepdir_out", (n_par,), f32, dv, optional=True)
+        _req(full_step_out, "full_step_out", (n_par,), f32, dv, optional=True)
+        scal_out = _req(scal_out if scal_out is not None else torch.zeros(_abi.OLY_TRPO_SCALARS, dtype=torch.float64,
+                                                                          device=dv),
+                        "scal_out", (_abi.OLY_TRPO_SCALARS,), torch.float64, dv)
+        a = _abi.TRPOStep(n=n, in_dim=in_dim, hidden1=h1, hidden2=h2, out_dim=out_dim, last_act=_abi.ACT_IDENTITY,
+                          n_epochs_cg=int(n_epochs_cg), n_epochs_line_search=int(n_epochs_line_search),
+                          accept_rule=_abi.OLY_TRPO_ACCEPT_AND if accept_rule == "and" else _abi.OLY_TRPO_ACCEPT_OR,
+                          max_kl=float(max_kl), ent_coeff=float(ent_coeff), cg_damping=float(cg_damping),
+                          cg_residual_tol=float(cg_residual_tol), obs=obs.data_ptr(), act=act.data_ptr(),
+                          adv=adv.data_ptr(), colstats=colstats.data_ptr(), theta=theta.data_ptr(),
+                          packed=None if packed is None else packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws,
+                          stepdir_out=None if stepdir_out is None else stepdir_out.data_ptr(),
+                          full_step_out=None if full_step_out is None else full_step_out.data_ptr(),
+                          scal_out=scal_out.data_ptr())
+        return a, dict(ws=ws, scal=scal_out, n_par=n_par, n=n, out_dim=out_dim)
+
+    def trpo_grad(self, obs, act, adv, colstats, theta, logp_old, k_stats=1, ent_coeff=0.0, grad_out=None, ws=None):
+        """oly_trpo_grad: (grad [n_par] f32, J [1] f64) of TRPO's surrogate at colstats + k_stats c."""
+        a, keep = self.trpo_args(obs, act, adv, colstats, theta, ent_coeff=ent_coeff, ws=ws)
+        _req(logp_old, "logp_old", (keep["n"],), torch.float32, self.device)
+        g = _req(grad_out if grad_out is not None else self._new((keep["n_par"],), torch.float32), "grad_out",
+                 (keep["n_par"],), torch.float32, self.device)
+        j = torch.zeros(1, dtype=torch.float64, device=self.device)
+        self.ctx.call("oly_trpo_grad", C.byref(a), int(k_stats), ptr(logp_old), ptr(g), ptr(j), self._s())
+        return g, j
+
+    def trpo_fvp(self, obs, colstats, theta, mu_old, log_sigma_old, p, k_stats=1, cg_damping=1e-1, out=None, ws=None):
+        """oly_trpo_fvp: Fvp(p) + cg_damping p [n_par] f32 at colstats + k_stats c against N(mu_old, exp(log_sigma_old)^2)."""
+        n, out_dim = (int(v) for v in mu_old.shape)
+        act = torch.zeros((n, out_dim), dtype=torch.float32, device=self.device)   # not read by the product
+        adv = torch.zeros(n, dtype=torch.float32, device=self.device)
+        a, keep = self.trpo_args(obs, act, adv, colstats, theta, cg_damping=cg_damping, ws=ws)
+        _req(mu_old, "mu_old", (n, out_dim), torch.float32, self.device)
+        _req(log_sigma_old, "log_sigma_old", (out_dim,), torch.float32, self.device)
+        _req(p, "p", (keep["n_par"],), torch.float32, self.device)
+        out = _req(out if out is not None else self._new((keep["n_par"],), torch.float32), "out", (keep["n_par"],),
+                   torch.float32, self.device)
+        self.ctx.call("oly_trpo_fvp", C.byref(a), int(k_stats), ptr(mu_old), ptr(log_sigma_old), ptr(p), ptr(out),
+                      self._s())
+        return out
+
+    def trpo_step(self, obs, act, adv, colstats, theta, **kw):
+        """oly_trpo_step: one TRPO policy step in one call (theta and colstats updated in place).  Returns the scalars
+        [8] f64 on the device: prev_loss, CG iterations run, shs, accepted j (-1: restored), kl, J, line-search
+        iterations run, last r.r."""
+        a, keep = self.trpo_args(obs, act, adv, colstats, theta, **kw)
+        self.ctx.call("oly_trpo_step", C.byref(a), self._s())
+        return keep["scal"]
+
     def return_scan(self, mode, gamma, lam, rew, val, next_val, flags, ret=None, adv=None, stats3=None):
         """rew [T,N] float32, or float64 (RETURN mode: the un-narrowed reward of env.step).  With
         `stats3` ([3] f64 device tensor) the same pass also leaves (T*N, sum adv, sum adv^2) there."""

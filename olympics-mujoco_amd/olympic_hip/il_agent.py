@@ -7,7 +7,8 @@
   discriminator training (_fit_discriminator, :167-220)   -> DeviceDiscriminatorTrainer (K15, oly_disc_fit_epoch), or
                                                              the caller's DiscriminatorTrainer (torch, a different
                                                              reading: one Adam step per epoch on the whole batch)
-  TRPO's policy step                                      -> the caller's policy_step
+  TRPO's policy step (:131-149)                           -> the caller's policy_step, e.g. DeviceTRPO (K17,
+                                                             oly_trpo_step) on a DeviceGaussianPolicy
 
 The critic shares the policy's running Standardizer (trpo_standardizer, utils.py:123); every evaluation and every
 fit minibatch adds its rows to it, as Standardizer.forward does (networks.py:68-81).
@@ -319,3 +320,163 @@ class DeviceDiscriminatorTrainer:
         r.invalidate()
         self.loss._beta = float(self.beta)                           # the one host read-back of the call
         return losses
+
+
+class DeviceGaussianPolicy:
+    """GaussianTorchPolicy(FullyConnectedNetwork(in -> 512 -> 256 -> out, relu, relu, identity), std_0,
+    standardizer=trpo_standardizer) (examples/imitation_learning/utils.py:126-134) held on the device: flat
+    parameters theta in mushroom's order W1 | b1 | W2 | b2 | W3 | b3 | log_sigma and K16's packed stream of the mean
+    network.  mushroom-rl's GaussianTorchPolicy is not part of the reference; this is a reading of mushroom-rl >= 1.10:
+    log_sigma is state-independent, initialised to log(std_0), and distribution_t(s) = N(mu(s),
+    diag(exp(log_sigma))^2).
+
+    net: the reference's FullyConnectedNetwork (its `_linears`) or a list of its three nn.Linear layers; standardizer:
+    the DeviceStandardizer shared with the critic.  Every forward that the reference runs through
+    FullyConnectedNetwork.forward adds the rows to the statistics first (networks.py:68-81): draw_action and
+    log_prob do; predict does not."""
+
+    def __init__(self, engine, net, standardizer, std_0=1.0, log_sigma=None):
+        lins = list(getattr(net, "_linears", net))
+        if len(lins) != 3:
+            raise OlyError(f"DeviceGaussianPolicy: expected three Linear layers, got {len(lins)}")
+        self.eng, self.net, self.lins, self.stand = engine, net, lins, standardizer
+        self.in_dim, self.out_dim = int(lins[0].in_features), int(lins[2].out_features)
+        if (int(lins[0].out_features), int(lins[1].in_features), int(lins[1].out_features),
+                int(lins[2].in_features)) != (_H1, _H1, _H2, _H2) or not 0 < self.in_dim <= 64 or not 0 < self.out_dim <= 32:
+            raise OlyError("DeviceGaussianPolicy: supported shape is in <= 64 -> 512 -> 256 -> out <= 32")
+        dev = engine.device
+        if log_sigma is None:
+            log_sigma = torch.full((self.out_dim,), float(np.log(std_0)), dtype=torch.float32)
+        log_sigma = torch.as_tensor(log_sigma, dtype=torch.float32).reshape(-1)
+        if int(log_sigma.numel()) != self.out_dim:
+            raise OlyError(f"DeviceGaussianPolicy: log_sigma has {log_sigma.numel()} values for {self.out_dim} actions")
+        with torch.no_grad():
+            self.theta = torch.cat([t.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+                                    for lin in lins for t in (lin.weight, lin.bias)]
+                                   + [log_sigma.to(dev)]).contiguous()
+        self.packed = engine.ilmlp_pack(*self._views()[:6])
+
+    def _views(self):
+        shapes = [(_H1, self.in_dim), (_H1,), (_H2, _H1), (_H2,), (self.out_dim, _H2), (self.out_dim,), (self.out_dim,)]
+        out, o = [], 0
+        for s in shapes:
+            n = int(np.prod(s))
+            out.append(self.theta[o:o + n].view(s))
+            o += n
+        return out
+
+    @property
+    def log_sigma(self):
+        return self._views()[6]
+
+    @property
+    def n_par(self):
+        return int(self.theta.numel())
+
+    def repack(self):
+        """Re-pack the mean network after theta was written (set_weights does this)."""
+        self.eng.ilmlp_pack(*self._views()[:6], packed=self.packed)
+
+    @torch.no_grad()
+    def predict(self, obs):
+        """mu(obs) with the current statistics, without updating them (K16's forward)."""
+        x = obs.reshape(-1, self.in_dim).to(torch.float32).contiguous()
+        return self.eng.ilmlp_forward(x, self.packed, self.out_dim, "identity", colstats=self.stand.colstats)
+
+    @torch.no_grad()
+    def draw_action(self, obs, generator=None):
+        """distribution_t(obs).sample(): the statistics take obs's rows, then mu(obs) + exp(log_sigma) eps."""
+        x = obs.reshape(-1, self.in_dim).to(torch.float32).contiguous()
+        self.stand.update_mean_std(x)
+        mu = self.predict(x)
+        eps = torch.randn(mu.shape, dtype=torch.float32, device=mu.device, generator=generator)
+        return mu + torch.exp(self.log_sigma) * eps
+
+    @torch.no_grad()
+    def log_prob(self, obs, act):
+        """log_prob_t(obs, act) [n,1]: the statistics take obs's rows (the forward), then the diagonal Gaussian's
+        log-density as torch's MultivariateNormal forms it."""
+        x = obs.reshape(-1, self.in_dim).to(torch.float32).contiguous()
+        self.stand.update_mean_std(x)
+        mu = self.predict(x)
+        sigma = torch.exp(self.log_sigma)
+        u = (act.reshape(mu.shape).to(torch.float32) - mu) / sigma
+        lp = -0.5 * (self.out_dim * float(np.log(2 * np.pi)) + (u * u).sum(1)) - torch.log(sigma).sum()
+        return lp[:, None]
+
+    def entropy(self):
+        """entropy_t: out/2 log(2 pi e) + sum(log_sigma) (no forward), a device scalar."""
+        return 0.5 * self.out_dim * float(np.log(2 * np.pi * np.e)) + self.log_sigma.sum()
+
+    def get_weights(self):
+        """The flat parameters in mushroom's order (a device copy)."""
+        return self.theta.clone()
+
+    @torch.no_grad()
+    def set_weights(self, w):
+        w = torch.as_tensor(w, dtype=torch.float32, device=self.theta.device).reshape(-1)
+        if int(w.numel()) != self.n_par:
+            raise OlyError(f"DeviceGaussianPolicy.set_weights: {w.numel()} values for {self.n_par} parameters")
+        self.theta.copy_(w)
+        self.repack()
+
+    @torch.no_grad()
+    def sync_to_torch(self):
+        """Write theta back into the wrapped Linear layers; returns (net, log_sigma as a host tensor)."""
+        v = self._views()
+        for i, lin in enumerate(self.lins):
+            lin.weight.copy_(v[2 * i].to(lin.weight.device))
+            lin.bias.copy_(v[2 * i + 1].to(lin.bias.device))
+        return self.net, v[6].detach().cpu().clone()
+
+
+class DeviceTRPO:
+    """TRPO's policy step (GAIL_TRPO.fit, gail_TRPO.py:131-149) on K17, one oly_trpo_step call, no host
+    synchronisation.  Callable as VAILAgent's policy_step(obs, act, adv, agent).
+
+    mushroom-rl's TRPO is not part of the reference: the step restates a READING of mushroom-rl >= 1.10 (DESIGN.md
+    section 13).  cg_damping, cg_residual_tol and n_epochs_line_search default to GAIL's own defaults
+    (gail_TRPO.py:30-32); max_kl, ent_coeff and n_epochs_cg come from confs.yaml (UnitreeH1: 5e-3, 1e-3, 25).
+    accept_rule: "or" (accept when kl <= 1.5 max_kl or the surrogate did not drop, this reading of mushroom's
+    _line_search) or "and" (both, as OpenAI baselines).
+
+    After each call `last` holds the step's scalars, on the device (f64 [8]): prev_loss, CG iterations run, shs,
+    accepted j (-1: theta_0 restored), kl and J of the last candidate evaluated, line-search iterations run, r.r."""
+
+    SCALARS = ("prev_loss", "cg_iters", "shs", "accepted_j", "kl", "J", "ls_iters", "residual")
+
+    def __init__(self, policy, max_kl, ent_coeff, n_epochs_cg, cg_damping=1e-1, cg_residual_tol=1e-10,
+                 n_epochs_line_search=10, accept_rule="or"):
+        if accept_rule not in ("or", "and"):
+            raise OlyError(f"DeviceTRPO: accept_rule must be 'or' or 'and' (got {accept_rule!r})")
+        self.policy, self.eng = policy, policy.eng
+        self.kw = dict(max_kl=float(max_kl), ent_coeff=float(ent_coeff), n_epochs_cg=int(n_epochs_cg),
+                       cg_damping=float(cg_damping), cg_residual_tol=float(cg_residual_tol),
+                       n_epochs_line_search=int(n_epochs_line_search), accept_rule=accept_rule)
+        self._ws = None
+        self.last = None
+
+    def scalars(self):
+        """`last` read back to the host as a dict (one synchronisation)."""
+        v = self.last.cpu().tolist()
+        return dict(zip(self.SCALARS, v))
+
+    @torch.no_grad()
+    def __call__(self, obs, act, adv, agent=None):
+        pol, eng = self.policy, self.eng
+        x = obs.reshape(-1, pol.in_dim).to(torch.float32).contiguous()
+        n = int(x.shape[0])
+        a = act.reshape(n, -1).to(torch.float32).contiguous()
+        ad = adv.reshape(n).to(torch.float32).contiguous()
+        st = pol.stand
+        if getattr(st, "_fresh", False):     # the running sums start from zero; the step adds to them in place
+            st.colstats.zero_()
+            st._fresh = False
+        if self._ws is None or self._ws[0] != n:
+            from ._ffi import lib
+            nws = int(lib().oly_trpo_ws_floats(n, pol.in_dim, _H1, _H2, pol.out_dim))
+            if nws < 0:
+                raise OlyError(f"DeviceTRPO: unsupported n={n} / shape")
+            self._ws = (n, torch.empty(nws, dtype=torch.float32, device=eng.device))
+        self.last = eng.trpo_step(x, a, ad, st.colstats, pol.theta, packed=pol.packed, ws=self._ws[1], **self.kw)
+        return self.last
