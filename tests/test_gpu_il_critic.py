@@ -53,7 +53,7 @@ def close(y, ref, tol=1e-5):
     assert err <= tol * scale, (err, scale)
 
 
-@pytest.mark.parametrize("in_dim", [16, 32, 48, 64])
+@pytest.mark.parametrize("in_dim", [1, 16, 17, 32, 36, 45, 48, 64])
 @pytest.mark.parametrize("out_dim", [1, 11, 32])
 @pytest.mark.parametrize("act", ["identity", "tanh"])
 def test_forward_against_float64(eng, in_dim, out_dim, act):
