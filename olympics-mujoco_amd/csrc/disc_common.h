@@ -1,5 +1,6 @@
 // Pieces of the fused discriminator forward (K12, csrc/k12_disc_forward.hip) that the discriminator's fit (K15,
-// csrc/k15_disc_fit.hip) shares: the packed operand stream's layout and the float32 exp of the reparameterisation.
+// csrc/k15_disc_fit.hip) shares: the packed operand stream's layout and the float32 exp of the reparameterisation; and the pieces GAIL's
+// discriminator (K18, csrc/k18_gail_disc.hip) shares with them: the reward formula and the float32 tanh.
 #pragma once
 #include "oly_common.h"
 
@@ -62,6 +63,48 @@ __device__ __forceinline__ float exp32(float x) {
   u = 1.0f + fmaf(r * r, u, r);
   const int q = (int)n, q1 = q >> 1;
   return (u * pow2i(q1)) * pow2i(q - q1);
+}
+
+// make_discrim_reward's formula (gail_TRPO.py:320-327), -log(1 - sigmoid(d) + 1e-8), for the elementwise reward kernel
+// (K8) and the fused GAIL forward (K18).
+__device__ __forceinline__ float reward_of(float d) {
+  // numpy evaluates every step in float32 (gail_TRPO.py:320-327 on the network's float32 output), and so
+  // does this: expf / logf are the <= 1 ulp device functions, the same class of error as numpy's own
+  // float32 exp / log; the 1 - p cancellation amplifies either to the tolerance the tests state.
+  // (Round 1 took exp / log in fp64: 27 % of the HBM peak, fp64-transcendental-bound.)
+  const float e = expf(-d);
+  const float p = 1.0f / (1.0f + e);
+  const float q = 1.0f - p + 1e-8f;
+  return -logf(q);
+}
+
+// tanh in float32, the hidden activation of GAIL's discriminator (K18: the reward forward and the fit's forward both
+// call it, so they produce the same hidden values).  Branch-free, since a wave of hidden units always holds both kinds
+// of argument.  |x| < 0.25 (and NaN): the odd Taylor polynomial through x^9 (the first dropped term is below 1e-8 of
+// the result).  Otherwise 1 - 2 / (exp(2 |x|) + 1) with exp32's reduction and polynomial (no range checks are needed:
+// 2 |x| is clamped to 18.04, where the result has rounded to 1), one exact scaling by 2^n and the hardware reciprocal
+// (1 ulp); the subtraction loses at most two bits (the quotient is below 0.76).  Measured against fp64 tanh over 5e7
+// arguments in [-12, 12]: at most 5.6 ulp, at |x| just above 0.25; 0.5 ulp below 0.01.
+__device__ __forceinline__ float tanh32(float x) {
+  const float ax = fabsf(x), s = x * x;
+  float u = 62.0f / 2835.0f;
+  u = fmaf(u, s, -17.0f / 315.0f);
+  u = fmaf(u, s, 2.0f / 15.0f);
+  u = fmaf(u, s, -1.0f / 3.0f);
+  const float small = fmaf(x * s, u, x);
+  const float t = 2.0f * fminf(ax, 9.02f);
+  const float n = rintf(t * 1.4426950408889634f);
+  float r = fmaf(n, -0.693145751953125f, t);
+  r = fmaf(n, -1.428606765330187045e-06f, r);
+  float e = 0.000198527617612853646278381f;
+  e = fmaf(e, r, 0.00139304355252534151077271f);
+  e = fmaf(e, r, 0.00833336077630519866943359f);
+  e = fmaf(e, r, 0.0416664853692054748535156f);
+  e = fmaf(e, r, 0.166666671633720397949219f);
+  e = fmaf(e, r, 0.5f);
+  e = (1.0f + fmaf(r * r, e, r)) * pow2i((int)n);          // n in [0, 27]
+  const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
+  return ax >= 0.25f ? copysignf(big, x) : small;
 }
 
 }  // namespace oly_disc

@@ -5,9 +5,11 @@
 //   oly_disc_reparam      reparameterize networks.py:21-24
 //   oly_disc_reward       GAIL.make_discrim_reward gail_TRPO.py:320-327
 // Elementwise, HBM-bound: 8 B/element (standardise), 16 B (reparam), 8 B (reward).
+#include "disc_common.h"
 #include "oly_common.h"
 
 namespace {
+using oly_disc::reward_of;
 constexpr int THREADS = 256;
 
 __global__ __launch_bounds__(THREADS) void standardize_kernel(int B, int Dx, int D,
@@ -106,17 +108,6 @@ __global__ __launch_bounds__(THREADS) void reparam_kernel(long n, const float* _
   const long stride = (long)gridDim.x * THREADS;
   for (long i = (long)blockIdx.x * THREADS + threadIdx.x; i < n; i += stride)
     z[i] = mu[i] + expf(logvar[i] / 2.0f) * eps[i];
-}
-
-__device__ __forceinline__ float reward_of(float d) {
-  // numpy evaluates every step in float32 (gail_TRPO.py:320-327 on the network's float32 output), and so
-  // does this: expf / logf are the <= 1 ulp device functions, the same class of error as numpy's own
-  // float32 exp / log; the 1 - p cancellation amplifies either to the tolerance the tests state.
-  // (Round 1 took exp / log in fp64: 27 % of the HBM peak, fp64-transcendental-bound.)
-  const float e = expf(-d);
-  const float p = 1.0f / (1.0f + e);
-  const float q = 1.0f - p + 1e-8f;
-  return -logf(q);
 }
 
 // vec4: both pointers 16-byte aligned; the n % 4 tail goes through the scalar lanes of the last pass

@@ -76,6 +76,7 @@ struct oly_ctx {
   unsigned scan_attr_done = 0;  // dynamic-LDS limit of the pipelined scan kernels raised on this device
   unsigned ilmlp_attr_done = 0; // same for the imitation-MLP forward's instantiations (K16)
   unsigned discfit_attr_done = 0;  // same for the discriminator fit's row kernels (K15)
+  unsigned gail_attr_done = 0;  // same for GAIL's discriminator: the forward's instantiations and the fit's row kernels (K18)
   int num_cu;
 };
 

@@ -164,6 +164,15 @@ class DiscFit(C.Structure):
                 ("beta_out", vp)]
 
 
+class GailDiscFit(C.Structure):
+    """oly_gail_disc_fit (K18): GAIL's discriminator fit state for oly_gail_disc_fit_epoch."""
+    _fields_ = [("in_dim", C.c_int32), ("n_plcy", C.c_int32), ("step", C.c_int32), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("weight_decay", C.c_float),
+                ("entcoeff", C.c_float), ("x", vp), ("targets", vp), ("colstats", vp), ("param", vp), ("exp_avg", vp),
+                ("exp_avg_sq", vp), ("packed", vp), ("ws", vp), ("ws_floats", C.c_int64), ("loss_out", vp),
+                ("bce_out", vp), ("ent_out", vp)]
+
+
 OLY_TRPO_ACCEPT_OR, OLY_TRPO_ACCEPT_AND, OLY_TRPO_SCALARS = 0, 1, 8
 
 
@@ -266,6 +275,10 @@ SIGNATURES = {
     "oly_il_critic_fit_epoch": (C.c_int, [vp, C.POINTER(ILCriticFit), vp, C.c_int, C.c_int, vp]),
     "oly_disc_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "oly_disc_fit_epoch": (C.c_int, [vp, C.POINTER(DiscFit), vp, C.c_int, C.c_int, vp]),
+    "oly_gail_disc_forward": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int] + [vp] * 9),
+    "oly_gail_reward_step": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [vp] * 5),
+    "oly_gail_disc_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "oly_gail_disc_fit_epoch": (C.c_int, [vp, C.POINTER(GailDiscFit), vp, C.c_int, C.c_int, vp]),
     "oly_trpo_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),

@@ -747,6 +747,125 @@ class Engine:
         self.ctx.call("oly_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
         return loss_out
 
+    # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
+    def _gail_packed_floats(self, D):
+        from ._ffi import lib
+        cache = self.__dict__.setdefault("_gail_sizes", {})
+        if D not in cache:
+            cache[D] = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 1))
+        if cache[D] < 0:
+            raise OlyError(f"gail discriminator: unsupported input width {D} (0 < in <= 64)")
+        return cache[D]
+
+    def _gail_outputs(self, name, B, want, out):
+        f32, dv = torch.float32, self.device
+        if not want:
+            raise OlyError(f"{name}: no output requested")
+        out = dict(out or {})
+        for k in want:
+            if k not in ("reward", "logits"):
+                raise OlyError(f"{name}: unknown output {k!r}")
+            out[k] = _req(out.get(k) if out.get(k) is not None else self._new((B,), f32), k, (B,), f32, dv)
+        return out, (lambda k: ptr(out[k]) if k in want else None)
+
+    def gail_disc_forward(self, x, packed, mask=None, mean=None, std=None, colstats=None, want=("reward",), out=None):
+        """GAIL's make_discrim_reward for x [B,Dx] f32 in one launch (in -> 512 -> 256 -> 1, tanh, tanh, identity).
+        mask [D] int32: the state columns, gathered inside the kernel (the block is never copied to its masked
+        width).  want: any of reward / logits.  Standardisation from mean / std [D] f64, or from the running colstats
+        [3,D] of col_stats, or none.  packed: the ilmlp_pack stream of the network (out_dim 1)."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), f32, dv)
+        D = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (D,), torch.int32, dv, optional=True)
+        if (mean is None) != (std is None) or (mean is not None and colstats is not None):
+            raise OlyError("gail_disc_forward: give mean and std together, or colstats, or neither")
+        _req(colstats, "colstats", (3, D), torch.float64, dv, optional=True)
+        _req(mean, "mean", (D,), torch.float64, dv, optional=True)
+        _req(std, "std", (D,), torch.float64, dv, optional=True)
+        _req(packed, "packed", (self._gail_packed_floats(D),), f32, dv)        # the raw pointer carries no length
+        out, g = self._gail_outputs("gail_disc_forward", B, want, out)
+        self.ctx.call("oly_gail_disc_forward", C.c_int64(B), Dx, D, ptr(x), ptr(mask), ptr(mean), ptr(std),
+                      ptr(colstats), ptr(packed), g("reward"), g("logits"), self._s())
+        return out
+
+    def gail_reward_step(self, x, packed, colstats, accumulate, mask=None, want=("reward",), out=None, weights=None):
+        """oly_gail_reward_step: (re-pack of `weights`, the six parameter tensors in ilmlp_pack's order, when given,) the
+        Standardizer's running update with x's masked rows (into colstats [3,D] f64, accumulate: added to the running
+        sums) and the forward on the updated statistics, one C call.  x [B,Dx] f32; mask [D] int32 or None."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), f32, dv)
+        D = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (D,), torch.int32, dv, optional=True)
+        _req(colstats, "colstats", (3, D), torch.float64, dv)
+        _req(packed, "packed", (self._gail_packed_floats(D),), f32, dv)
+        wp = None
+        if weights is not None:
+            shapes_w = ((512, D), (512,), (256, 512), (256,), (1, 256), (1,))
+            if len(weights) != 6:
+                raise OlyError("gail_reward_step: weights = the six tensors of ilmlp_pack")
+            for i, (t, sh) in enumerate(zip(weights, shapes_w)):
+                _req(t, f"weights[{i}]", sh, f32, dv)
+            wp = (C.c_void_p * 6)(*[t.data_ptr() for t in weights])
+        out, g = self._gail_outputs("gail_reward_step", B, want, out)
+        self.ctx.call("oly_gail_reward_step", C.c_int64(B), Dx, D, ptr(x), ptr(mask), ptr(colstats),
+                      int(bool(accumulate)), wp, ptr(packed), g("reward"), g("logits"), self._s())
+        return out
+
+    def gail_disc_fit_ws(self, batch, in_dim):
+        """A workspace for gail_disc_fit_epoch with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_gail_disc_fit_ws_floats(int(batch), int(in_dim)))
+        if n < 0:
+            raise OlyError(f"gail_disc_fit: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
+        return self._new((n,), torch.float32)
+
+    def gail_disc_fit_epoch(self, x, n_plcy, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed, ws, step, lr,
+                            beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0, entcoeff=1e-3, targets=None,
+                            loss_out=None, bce_out=None, ent_out=None):
+        """oly_gail_disc_fit_epoch: one epoch of GAIL's discriminator minibatch loop in one call.  x [n,in] f32 the masked
+        concatenated rows (policy rows first, n_plcy of them), perm [n] int32, param / exp_avg / exp_avg_sq flat in torch
+        order (W1 | b1 | W2 | b2 | W3 | b3), packed the ilmlp_pack stream (re-packed from param, then kept current),
+        targets [n] f32 or None (0 / 1); step = Adam steps taken before.  Returns loss_out [n_batches] f64 (bce_out,
+        ent_out likewise when given)."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [n,in] tensor")
+        n, in_dim = (int(v) for v in x.shape)
+        batch = int(batch)
+        nws = int(lib().oly_gail_disc_fit_ws_floats(batch, in_dim))
+        if nws < 0:
+            raise OlyError(f"gail_disc_fit_epoch: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
+        if not 0 <= int(n_plcy) <= n:
+            raise OlyError(f"gail_disc_fit_epoch: n_plcy={n_plcy} outside [0, {n}]")
+        nb = (n + batch - 1) // batch
+        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 256 + 1
+        _req(x, "x", (n, in_dim), f32, dv)
+        _req(perm, "perm", (n,), torch.int32, dv)
+        _req(targets, "targets", (n,), f32, dv, optional=True)
+        _req(colstats, "colstats", (3, in_dim), f64, dv)
+        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (self._gail_packed_floats(in_dim),), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
+        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
+        _req(ent_out, "ent_out", (nb,), f64, dv, optional=True)
+        f = _abi.GailDiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
+                             beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
+                             entcoeff=float(entcoeff), x=x.data_ptr(), targets=ptr(targets), colstats=colstats.data_ptr(),
+                             param=param.data_ptr(), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(),
+                             packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
+                             bce_out=ptr(bce_out), ent_out=ptr(ent_out))
+        self.ctx.call("oly_gail_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
+        return loss_out
+
     # -------------------------------------------------------------- K6
     # -------------------------------------------------------------- K17 (TRPO's policy step)
     def trpo_args(self, obs, act, adv, colstats, theta, max_kl=0.01, ent_coeff=0.0, n_epochs_cg=10, cg_damping=1e-1,

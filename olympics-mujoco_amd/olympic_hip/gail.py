@@ -8,8 +8,10 @@
 The reward path (mask + standardise, 32->256->128->(128,128)->1 for UnitreeH1, examples/
 imitation_learning/utils.py:151-161, reparameterisation, reward formula) is ONE launch on the f32
 matrix cores (K12, oly_disc_forward) after the statistics update (oly_col_stats); the statistics
-live on the device (no CPU bounce as in networks.py:70).  The discriminator's TRAINING forward /
-backward stays in PyTorch-ROCm.  The reparameterisation noise is an INPUT so results are
+live on the device (no CPU bounce as in networks.py:70).  GAIL's own discriminator (DiscriminatorNetwork,
+networks.py:194-225: in -> 512 -> 256 -> 1, tanh) is GAILDiscriminator / GAILDiscriminatorReward on K18
+(oly_gail_reward_step).  The device fits are il_agent's trainers; DiscriminatorTrainer here is the
+torch reading.  The reparameterisation noise is an INPUT so results are
 reproducible.
 """
 import numpy as np
@@ -191,6 +193,108 @@ class DiscriminatorReward:
             return self.forward(x, eps)["reward"]
         d, _, _ = self.logits_unfused(x, eps)
         return self.eng.disc_reward(d)
+
+
+class GAILDiscriminator(nn.Module):
+    """GAIL's DiscriminatorNetwork (imitation_lib/utils/networks.py:194-225) as create_gail_agent builds it
+    (examples/imitation_learning/utils.py:79-97): in -> n_features -> 1 with tanh / tanh / identity and the default
+    initialisation (initializers=None, networks.py:133-139): xavier_uniform_ with the activation's gain (5/3 for tanh,
+    1 for identity) on every weight, nn.Linear's own draw for the biases."""
+
+    def __init__(self, in_dim, n_features=(512, 256)):
+        super().__init__()
+        dims = [int(in_dim)] + [int(f) for f in n_features] + [1]
+        self._linears = nn.ModuleList([nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)])
+        acts = ["tanh"] * len(n_features) + ["linear"]
+        for lin, act in zip(self._linears, acts):
+            nn.init.xavier_uniform_(lin.weight, gain=nn.init.calculate_gain(act))
+
+    def forward(self, xs):
+        """The logits [B, 1] of an already standardised batch."""
+        h = xs
+        for lin in self._linears[:-1]:
+            h = torch.tanh(lin(h))
+        return self._linears[-1](h)
+
+
+class GAILDiscriminatorReward:
+    """make_discrim_reward (gail_TRPO.py:320-327) for GAIL's discriminator on the device (K18): the Standardizer's
+    update with the masked rows, then in -> 512 -> 256 -> 1 (tanh, tanh, identity) and the reward formula in one launch,
+    the state mask (prepare_discrim_inputs, :297-313) applied inside the kernel.
+
+    net: any module exposing three `_linears` of widths in <= 64 -> 512 -> 256 -> 1 (GAILDiscriminator, the reference's
+    DiscriminatorNetwork); others are refused with OlyError.  standardizer: the discriminator's own DeviceStandardizer
+    (the D_standardizer), created when not given."""
+
+    def __init__(self, engine, net, state_mask=None, standardizer=None):
+        from ._ffi import OlyError
+        lins = list(getattr(net, "_linears", ()))
+        if len(lins) != 3 or not all(isinstance(l, nn.Linear) for l in lins):
+            raise OlyError("GAILDiscriminatorReward: the network must expose three Linear layers as `_linears`")
+        dim = int(lins[0].in_features)
+        if not 0 < dim <= 64 or (int(lins[0].out_features), int(lins[1].in_features), int(lins[1].out_features),
+                                 int(lins[2].in_features), int(lins[2].out_features)) != (512, 512, 256, 256, 1):
+            raise OlyError("GAILDiscriminatorReward: supported network is in <= 64 -> 512 -> 256 -> 1")
+        self.eng, self.net, self.lins, self.in_dim = engine, net, lins, dim
+        self.mask = None
+        if state_mask is not None:
+            m = np.asarray(state_mask, dtype=np.int64).reshape(-1)
+            if m.size != dim or (m.size and m.min() < 0):
+                raise OlyError(f"GAILDiscriminatorReward: the state mask has {m.size} columns, the network takes {dim}")
+            self._mask_max = int(m.max())
+            self.mask = torch.as_tensor(m.astype(np.int32), device=engine.device)
+        self.stand = standardizer or DeviceStandardizer(engine, dim)
+        self._packed = None
+
+    def _params(self):
+        return [t for lin in self.lins for t in (lin.weight, lin.bias)]
+
+    def packed(self):
+        """The MFMA operand stream of the CURRENT weights, re-packed on every call into the same buffer, for the reason
+        DiscriminatorReward.packed documents: a cache keyed on `_version` would miss writes through `.data`."""
+        self._packed = self.eng.ilmlp_pack(*[p.detach().to(torch.float32).contiguous() for p in self._params()],
+                                           packed=self._packed)
+        return self._packed
+
+    def invalidate(self):
+        """Nothing is cached: every forward re-packs."""
+
+    def _check(self, x):
+        from ._ffi import OlyError
+        if x.dim() != 2:
+            raise OlyError("GAILDiscriminatorReward: x is [B, obs]")
+        if self.mask is None and int(x.shape[1]) != self.in_dim:
+            raise OlyError(f"GAILDiscriminatorReward: {x.shape[1]} columns, the network takes {self.in_dim}")
+        if self.mask is not None and int(x.shape[1]) <= self._mask_max:
+            raise OlyError(f"GAILDiscriminatorReward: {x.shape[1]} columns, the state mask reads column {self._mask_max}")
+
+    @torch.no_grad()
+    def forward(self, x, want=("reward",), out=None):
+        """Statistics update with the masked rows + forward, one C call: any of reward / logits for x [B,obs]."""
+        self._check(x)
+        st = self.stand
+        ps = [p.detach() for p in self._params()]
+        if self._packed is None or not all(p.dtype == torch.float32 and p.is_contiguous() for p in ps):
+            packed, ps = self.packed(), None                        # separate pack call
+        else:
+            packed = self._packed                                  # re-packed from the live parameters inside the call
+        o = self.eng.gail_reward_step(x.to(torch.float32).contiguous(), packed, st.colstats, not st._fresh,
+                                      mask=self.mask, want=want, out=out, weights=ps)
+        st._fresh = False
+        return o
+
+    @torch.no_grad()
+    def predict(self, x, want=("logits",), out=None):
+        """The forward on the current statistics, without updating them."""
+        self._check(x)
+        return self.eng.gail_disc_forward(x.to(torch.float32).contiguous(), self.packed(), mask=self.mask,
+                                          colstats=self.stand.colstats, want=want, out=out)
+
+    @torch.no_grad()
+    def __call__(self, x, eps=None, generator=None):
+        """The reward [B].  eps / generator are accepted and ignored (GAIL's discriminator draws no noise), so the
+        agent's sequence can call either discriminator."""
+        return self.forward(x)["reward"]
 
 
 class GAILAdvantage:

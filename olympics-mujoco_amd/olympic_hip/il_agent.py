@@ -4,7 +4,9 @@
       evaluation                                          -> DeviceILCritic.__call__ (K16, oly_ilmlp_forward)
       Regressor.fit (mushroom's minibatch loop + Adam)    -> DeviceILCritic.fit (K16, oly_il_critic_fit_epoch)
   discriminator reward, GAE, advantage normalisation      -> DiscriminatorReward (K12), GAERollout (K6 + K7)
-  discriminator training (_fit_discriminator, :167-220)   -> DeviceDiscriminatorTrainer (K15, oly_disc_fit_epoch), or
+  discriminator training (_fit_discriminator, :167-220)   -> DeviceDiscriminatorTrainer (K15, oly_disc_fit_epoch), for
+                                                             GAIL DeviceGAILDiscriminatorTrainer (K18,
+                                                             oly_gail_disc_fit_epoch) under GAILAgent, or
                                                              the caller's DiscriminatorTrainer (torch, a different
                                                              reading: one Adam step per epoch on the whole batch)
   TRPO's policy step (:131-149)                           -> the caller's policy_step, e.g. DeviceTRPO (K17,
@@ -320,6 +322,120 @@ class DeviceDiscriminatorTrainer:
         r.invalidate()
         self.loss._beta = float(self.beta)                           # the one host read-back of the call
         return losses
+
+
+class DeviceGAILDiscriminatorTrainer:
+    """_fit_discriminator (gail_TRPO.py:167-220) for GAIL, states only, on K18: DeviceDiscriminatorTrainer's semantics
+    with GAIL's network and loss.  Per epoch:
+
+        plcy = plcy_obs[:, state_mask] (n rows); demo = the first m = min(n, rows) rows of a shuffle of the
+        demonstration states (minibatch_generator, :198-200); concat = [plcy; demo]; targets 0 / 1, or
+        U(0.01, 0.10) / U(0.80, 0.99) with use_noisy_targets
+        D_standardizer.update_mean_std(concat)                                       (:206, oly_col_stats)
+        mushroom's Regressor.fit over concat: a permutation cut into minibatches of batch_size, each
+        Standardizer.forward, DiscriminatorNetwork.forward, GailDiscriminatorLoss(entcoeff), backward, Adam   (K18)
+
+    The draws come from the caller's torch.Generator in the order demo, noisy targets (demo first), perm, per epoch;
+    _discriminator_logging's extra forwards are not replayed (as DeviceDiscriminatorTrainer).  Defaults are
+    HumanoidMuscle's of confs.yaml (lr_disc 5e-6, d_entr_coef 1e-3) and create_gail_agent's (weight_decay 0, batch 2048).
+
+    reward: the GAILDiscriminatorReward whose network and standardizer are fitted; demo: an ExpertDataset (mask folded
+    in) or an array of full observations.  Every fit starts from the module's current parameters and writes the stepped
+    ones back in place; the reward's packed stream is left current.  The optimiser's moments and step count persist
+    across fits."""
+
+    def __init__(self, reward, demo, entcoeff=1e-3, lr=5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 batch_size=2048, n_epochs=1, use_noisy_targets=False):
+        from .gail import ExpertDataset, GAILDiscriminatorReward
+        if not isinstance(reward, GAILDiscriminatorReward):
+            raise OlyError("DeviceGAILDiscriminatorTrainer: reward must be a GAILDiscriminatorReward "
+                           "(in <= 64 -> 512 -> 256 -> 1, tanh)")
+        self.r, self.eng = reward, reward.eng
+        self.in_dim = reward.in_dim
+        self.batch = int(batch_size)
+        self._ws = self.eng.gail_disc_fit_ws(self.batch, self.in_dim)
+        self.entcoeff, self.lr, self.betas = float(entcoeff), float(lr), (float(betas[0]), float(betas[1]))
+        self.eps, self.wd = float(eps), float(weight_decay)
+        self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
+        dev = self.eng.device
+        self.expert = demo if isinstance(demo, ExpertDataset) else None
+        self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
+                                                                         device=dev)
+        if self.demo is not None and (self.demo.dim() != 2 or int(self.demo.shape[1]) <=
+                                      (reward._mask_max if reward.mask is not None else self.in_dim - 1)):
+            raise OlyError("DeviceGAILDiscriminatorTrainer: the demonstrations are [rows, obs] full observations")
+        n_par = sum(int(p.numel()) for p in reward._params())
+        self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros_like(self.param)
+        self.exp_avg_sq = torch.zeros_like(self.param)
+        self.step = 0
+
+    def _demo_rows(self, n, generator):
+        rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
+        idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
+        if self.expert is not None:
+            return self.expert.minibatch(idx)
+        d = self.demo[idx]
+        return d if self.r.mask is None else d[:, self.r.mask.long()]
+
+    @torch.no_grad()
+    def fit(self, plcy_obs, generator=None):
+        """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations).  Returns the per-minibatch losses,
+        [n_epochs, n_batches] f64 on the device."""
+        r, eng, dev = self.r, self.eng, self.eng.device
+        plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
+        n = int(plcy.shape[0])
+        if n == 0:
+            raise OlyError("DeviceGAILDiscriminatorTrainer.fit: no policy rows")
+        r._check(plcy)
+        if r.mask is not None:
+            plcy = plcy[:, r.mask.long()]
+        plcy = plcy.contiguous()
+        ps = r._params()
+        torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=self.param)
+        if r._packed is None:
+            r.packed()
+        st = r.stand
+        if getattr(st, "_fresh", False):     # the running sums start from zero; the fit adds to them in place
+            st.colstats.zero_()
+            st._fresh = False
+        losses = None
+        for e in range(self.n_epochs):
+            demo = self._demo_rows(n, generator)
+            x = torch.cat([plcy, demo]).contiguous()
+            rows = int(x.shape[0])
+            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206
+            targets = None
+            if self.noisy:                                          # :209-211: demo targets drawn first
+                demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
+                plcy_t = torch.empty(n, device=dev).uniform_(0.01, 0.10, generator=generator)
+                targets = torch.cat([plcy_t, demo_t[:rows - n]]).contiguous()
+            perm = torch.randperm(rows, generator=generator, device=dev).to(torch.int32)
+            nb = (rows + self.batch - 1) // self.batch
+            if losses is None:
+                losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
+            eng.gail_disc_fit_epoch(x, n, perm, self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq,
+                                    r._packed, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
+                                    adam_eps=self.eps, weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
+                                    loss_out=losses[e])
+            self.step += nb
+        o = 0
+        for p in ps:                                                # in place: captured pointers stay valid
+            k = int(p.numel())
+            p.data.copy_(self.param[o:o + k].view_as(p))
+            o += k
+        return losses
+
+
+class GAILAgent(VAILAgent):
+    """GAIL_TRPO.fit (gail_TRPO.py:105-165) for GAIL_TRPO: VAILAgent's sequence with GAIL's discriminator, i.e.
+    disc_reward a GAILDiscriminatorReward (K18's forward) and disc_trainer a DeviceGAILDiscriminatorTrainer (K18's
+    fit).  The discriminator draws no reparameterisation noise, so fit takes no eps."""
+
+    def fit(self, dataset, generator=None):
+        """One GAIL_TRPO.fit on [T,N,...] device blocks.  Returns dict(reward, v_target, adv, critic_loss, disc_loss,
+        disc_trained)."""
+        return super().fit(dataset, eps=None, generator=generator)
 
 
 class DeviceGaussianPolicy:
