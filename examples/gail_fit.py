@@ -8,6 +8,11 @@ it was handed, and the policy is a random one on the kinematic stand-in physics.
 from a DeviceGaussianPolicy (obs -> [512, 256] -> act) and DeviceTRPO (K17) trains it.
 
     python examples/gail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device]
+                                [--disc_use_next_states] [--disc_only_states False]
+
+--disc_use_next_states gives the discriminator (state, next state) (64 columns for H1's 32-column kinematic mask),
+--disc_only_states False gives it (state, action); the agent then hands next_state or action to the reward and the
+trainer by itself.
 """
 import argparse
 import os
@@ -20,6 +25,7 @@ from olympic_hip.envs import LocoEnvBase  # noqa: E402
 from olympic_hip.gail import DeviceStandardizer, GAILDiscriminator, GAILDiscriminatorReward  # noqa: E402
 from olympic_hip.il_agent import (DeviceGAILDiscriminatorTrainer, DeviceGaussianPolicy, DeviceILCritic,  # noqa: E402
                                   DeviceTRPO, GAILAgent)
+from vail_fit import paired_inputs  # noqa: E402  (the example beside this one: the two switches mean the same there)
 
 
 def policy_step(obs, act, adv, agent):
@@ -37,15 +43,20 @@ def main():
                     help="the discriminator's training: DeviceGAILDiscriminatorTrainer (K18), or none (a frozen discriminator)")
     ap.add_argument("--policy", choices=("random", "device"), default="random",
                     help="random actions and a stand-in policy step, or DeviceGaussianPolicy trained by DeviceTRPO (K17)")
+    ap.add_argument("--disc_use_next_states", action="store_true",
+                    help="the discriminator sees (state, next state), as confs.yaml sets for UnitreeA1 (disc_use_next_states)")
+    ap.add_argument("--disc_only_states", type=lambda s: s.lower() in ("1", "true", "yes"), default=True,
+                    help="False: the discriminator sees (state, action) (disc_only_states of the reference's launcher); needs a "
+                         "dataset with `actions`, which the bundled task's trajectory does not hold")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
     vec, eng = env.vec, env.vec.eng
     gen = torch.Generator(device="cuda").manual_seed(0)
     n_obs, n_act = vec.spec.n_obs, vec.spec.n_act
-    demo = env.create_dataset()["states"]
     mask = vec.get_kinematic_obs_mask()
-    disc = GAILDiscriminatorReward(eng, GAILDiscriminator(len(mask)).cuda(), state_mask=mask)
+    pair, act_mask, demo, width = paired_inputs(args, env, mask, n_act)
+    disc = GAILDiscriminatorReward(eng, GAILDiscriminator(width).cuda(), state_mask=mask, pair=pair, act_mask=act_mask)
     # the reference's minibatch loop, disc_batch_size 2048 (confs.yaml); the trainer exists either way, "none" never calls it
     trainer = DeviceGAILDiscriminatorTrainer(disc, demo, entcoeff=1e-3, lr=5e-6, batch_size=2048)
     # the critic of examples/imitation_learning/utils.py:136-149: obs -> [512, 256] -> 1, the policy's standardizer

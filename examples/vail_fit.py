@@ -7,12 +7,18 @@ DeviceGaussianPolicy (obs -> [512, 256] -> act, std_0 0.5) and DeviceTRPO (K17) 
 values (max_kl 5e-3, ent_coeff 1e-3, n_epochs_cg 25).
 
     python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device]
+                                [--disc_use_next_states] [--disc_only_states False]
+
+--disc_use_next_states gives the discriminator (state, next state) (64 columns for H1's 32-column kinematic mask),
+--disc_only_states False gives it (state, action); both need --disc-fit device (K15), and the agent then hands
+next_state or action to the reward and the trainer by itself.
 """
 import argparse
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "olympics-mujoco_amd"))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from olympic_hip.envs import LocoEnvBase  # noqa: E402
@@ -28,6 +34,21 @@ def policy_step(obs, act, adv, agent):
           f"std {float(adv.std(unbiased=False)):.4f}")
 
 
+def paired_inputs(args, env, mask, n_act):
+    """(pair, act_mask, demonstrations, network width) for the two switches.  Both together is the reference's refused
+    three-part combination (gail_TRPO.py:195-196): the reward's constructor raises OlyError for it."""
+    pair = "next_state" if args.disc_use_next_states else (None if args.disc_only_states else "action")
+    act_mask = None if args.disc_only_states else np.arange(n_act)
+    ds = env.create_dataset()
+    if pair is None:
+        return None, None, ds["states"], len(mask)
+    key = "next_states" if pair == "next_state" else "actions"
+    if ds.get(key) is None:
+        raise SystemExit(f"the dataset of this task holds no `{key}`")
+    width = 2 * len(mask) if pair == "next_state" else len(mask) + n_act
+    return pair, act_mask, {"states": ds["states"], key: ds[key]}, width
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
@@ -37,14 +58,26 @@ def main():
                     help="the discriminator's training: DiscriminatorTrainer (torch) or DeviceDiscriminatorTrainer (K15)")
     ap.add_argument("--policy", choices=("random", "device"), default="random",
                     help="random actions and a stand-in policy step, or DeviceGaussianPolicy trained by DeviceTRPO (K17)")
+    ap.add_argument("--disc_use_next_states", action="store_true",
+                    help="the discriminator sees (state, next state), as confs.yaml sets for UnitreeA1 (disc_use_next_states)")
+    ap.add_argument("--disc_only_states", type=lambda s: s.lower() in ("1", "true", "yes"), default=True,
+                    help="False: the discriminator sees (state, action) (disc_only_states of the reference's launcher); needs a "
+                         "dataset with `actions`, which the bundled task's trajectory does not hold")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
     vec, eng = env.vec, env.vec.eng
     gen = torch.Generator(device="cuda").manual_seed(0)
     n_obs, n_act = vec.spec.n_obs, vec.spec.n_act
-    demo = env.create_dataset()["states"]
-    disc = DiscriminatorReward(eng, VariationalDiscriminator(n_obs).cuda(), state_mask=vec.get_kinematic_obs_mask())
+    mask = vec.get_kinematic_obs_mask()
+    pair, act_mask, demo, width = paired_inputs(args, env, mask, n_act)
+    if pair is None:
+        disc = DiscriminatorReward(eng, VariationalDiscriminator(n_obs).cuda(), state_mask=mask)
+    else:
+        if args.disc_fit != "device":
+            raise SystemExit("a paired discriminator input is fitted by --disc-fit device (K15)")
+        disc = DiscriminatorReward(eng, VariationalDiscriminator(width).cuda(), state_mask=mask, pair=pair,
+                                   act_mask=act_mask)
     if args.disc_fit == "device":     # the reference's minibatch loop, disc_batch_size 2048 (confs.yaml)
         trainer = DeviceDiscriminatorTrainer(disc, demo, VDBLoss(info_constraint=0.1, lr_beta=1e-5), lr=5e-5,
                                              batch_size=2048)

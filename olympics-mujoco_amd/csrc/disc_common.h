@@ -42,6 +42,16 @@ __host__ __device__ inline DiscLayout disc_layout(int in_dim) {
   return L;
 }
 
+// What every paired entry point (oly_disc_pair: the discriminator's second part) refuses before a launch, or NULL.
+// Ds: the first part's width.
+inline const char* pair_error(const oly_disc_pair* pr, int Ds) {
+  if (!pr->x2 || pr->d2 <= 0 || pr->stride2 <= 0) return "NULL x2, or d2 / stride2 not positive";
+  if (Ds + pr->d2 > MAX_IN) return "the two parts are wider than 64 columns together";
+  if (!pr->mask2 && pr->d2 > pr->stride2) return "d2 exceeds stride2 and there is no mask2";
+  if (pr->standardise && pr->d2 != Ds) return "a standardised second part (next states) has the first part's width";
+  return nullptr;
+}
+
 // exp in float32 from fma / rint / exponent arithmetic only, so that the oracle's copy returns the same bits:
 // n = rint(x log2 e), r = x - n ln2 (two-constant Cody-Waite), e^r = 1 + (r + r^2 P(r)) with a degree-5 minimax
 // P, result scaled by 2^n in two exact steps.  Within 1 ulp of exp over the whole float range (checked

@@ -85,6 +85,13 @@ struct FwdArgs {
   const float* packed;
   float* y;
   float* reward;            // [N] reward_of(y) (out_dim == 1), or NULL
+  // The discriminator's second part (DiscriminatorNetwork.preprocess_inputs, networks.py:216-234), d2 == 0: none.
+  // Columns [in_dim - d2, in_dim) of the input are x2[row, mask2[k - ds]]: next states standardised with colstats2
+  // (std2, the statistics after the Standardizer's SECOND update of the forward) or actions taken raw.
+  int d2, std2, stride2;
+  const float* x2;
+  const int* mask2;         // [d2] columns of x2, or NULL (identity)
+  const double* colstats2;  // [3, in_dim - d2], as colstats
 };
 
 template <int RS>
@@ -131,15 +138,20 @@ __global__ __launch_bounds__(FWD_THREADS) void ilmlp_forward_kernel(FwdArgs p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long row0 = (long)blockIdx.x * (16 * RS);
-  const int in_dim = p.in_dim;
+  const int in_dim = p.in_dim, ds = in_dim - p.d2;     // ds: the Standardizer's columns (the first part)
   const bool standardise = p.mean || p.colstats;
 
   if (tid < in_dim && standardise) {
     double mean, sd;
-    if (p.colstats) {           // Standardizer.update_mean_std's derivation (networks.py:54-56,76-81), as K12
-      const double cnt = p.colstats[tid] + 1e-2;
-      mean = p.colstats[in_dim + tid] / cnt;
-      sd = sqrt(fmax((p.colstats[2 * in_dim + tid] + 1e-2) / cnt - mean * mean, 1e-2));
+    if (p.colstats && tid >= ds && !p.std2) {   // actions pass through: f32((f64(a) - 0) / 1) is a
+      mean = 0.0;
+      sd = 1.0;
+    } else if (p.colstats) {    // Standardizer.update_mean_std's derivation (networks.py:54-56,76-81), as K12
+      const double* cs = tid < ds ? p.colstats : p.colstats2;
+      const int j = tid < ds ? tid : tid - ds;
+      const double cnt = cs[j] + 1e-2;
+      mean = cs[ds + j] / cnt;
+      sd = sqrt(fmax((cs[2 * ds + j] + 1e-2) / cnt - mean * mean, 1e-2));
     } else {
       mean = p.mean[tid];
       sd = p.sd[tid];
@@ -153,7 +165,8 @@ __global__ __launch_bounds__(FWD_THREADS) void ilmlp_forward_kernel(FwdArgs p) {
     const long row = row0 + 16 * s + m;
     float v = 0.f;
     if (row < p.N && k < in_dim) {
-      const float xv = p.x[row * p.stride + (p.mask ? p.mask[k] : k)];
+      const float xv = k < ds ? p.x[row * p.stride + (p.mask ? p.mask[k] : k)]
+                              : p.x2[row * p.stride2 + (p.mask2 ? p.mask2[k - ds] : k - ds)];
       // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
       v = standardise ? (float)(((double)xv - s_mean[k]) / s_sd[k]) : xv;
     }

@@ -107,6 +107,13 @@ struct DiscArgs {
   const float* packed;
   const float* eps;
   float *reward, *logits, *mu, *logvar;
+  // The second part of a paired input (VariationalNet.forward, networks.py:258-278), d2 == 0: none.  Columns [D - d2, D)
+  // are x2[row, mask2[k - ds]]: next states standardised with colstats2 (std2: the statistics after the Standardizer's
+  // SECOND update of the forward) or actions taken raw.
+  int d2, std2, stride2;
+  const float* x2;
+  const int* mask2;
+  const double* colstats2;    // [3, D - d2], as colstats
 };
 
 // NACC 32-row x 32-column tiles of  A W  that share the A operand (k = 0 .. 8 G - 1 in order): A fragments from
@@ -194,14 +201,20 @@ __global__ __launch_bounds__(THREADS, 2) void disc_forward_kernel(DiscArgs p) {
 
   if (tid < ZD + 4) wd[tid] = Pbase[L.wd + tid];
   const bool standardise = p.mean || p.colstats;
+  const int ds = p.D - p.d2;                // the Standardizer's columns (the first part)
   if (tid < p.D && standardise) {
     double mean, sd;
-    if (p.colstats) {
+    if (p.colstats && tid >= ds && !p.std2) {   // actions pass through: f32((f64(a) - 0) / 1) is a
+      mean = 0.0;
+      sd = 1.0;
+    } else if (p.colstats) {
       // Standardizer.update_mean_std (networks.py:76-81) from the running (count, sum, sumsq) rows:
       // _count and _sumsq start at 1e-2, the variance is floored at 1e-2
-      const double cnt = p.colstats[tid] + 1e-2;
-      mean = p.colstats[p.D + tid] / cnt;
-      sd = sqrt(fmax((p.colstats[2 * p.D + tid] + 1e-2) / cnt - mean * mean, 1e-2));
+      const double* cs = tid < ds ? p.colstats : p.colstats2;
+      const int j = tid < ds ? tid : tid - ds;
+      const double cnt = cs[j] + 1e-2;
+      mean = cs[ds + j] / cnt;
+      sd = sqrt(fmax((cs[2 * ds + j] + 1e-2) / cnt - mean * mean, 1e-2));
     } else {
       mean = p.mean[tid];
       sd = p.sd[tid];
@@ -213,14 +226,22 @@ __global__ __launch_bounds__(THREADS, 2) void disc_forward_kernel(DiscArgs p) {
 
   // input element i of this thread: row m = e / KIN, column k = e % KIN of the tile (consecutive threads:
   // consecutive k of one row, so a row is one contiguous read when there is no mask)
+  // THREADS is a multiple of KIN, so every element of this thread is the same column kx of its row: the column's source
+  // (the first part, or the second part of a paired input) and its offset in that source's rows are fixed per thread
   float xr[XPT];
+  const int kx = tid & (KIN - 1);
+  const bool second = kx >= ds;
+  int xcol = 0;
+  if (kx < p.D) xcol = second ? (p.mask2 ? p.mask2[kx - ds] : kx - ds) : (p.mask ? p.mask[kx] : kx);
   auto load_x = [&](long tile) {
     const long row0 = tile * RT;
+    const float* src = second ? p.x2 : p.x;
+    const int stride = second ? p.stride2 : p.Dx;
 #pragma unroll
     for (int i = 0; i < XPT; ++i) {
-      const int e = tid + THREADS * i, m = e / KIN, k = e - m * KIN;
+      const int m = (tid + THREADS * i) / KIN;
       float v = 0.f;
-      if (row0 + m < p.B && k < p.D) v = p.x[(size_t)(row0 + m) * p.Dx + (p.mask ? p.mask[k] : k)];
+      if (row0 + m < p.B && kx < p.D) v = src[(size_t)(row0 + m) * stride + xcol];
       xr[i] = v;
     }
   };
@@ -344,19 +365,27 @@ __global__ __launch_bounds__(THREADS, 2) void disc_forward16_kernel(DiscArgs p) 
   const float* Pbase = p.packed;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 15, h2 = lane >> 4;
+  const int ds = p.D - p.d2;                 // the Standardizer's columns (the first part)
 
   // This kernel serves SMALL batches: one tile per workgroup, one workgroup per CU, nothing else on the CU to hide a
   // memory round trip.  So every load that does not depend on a barrier is requested before the barrier in front of its
   // use: the first tile's rows and layer-1 weights here, ahead of the statistics; each later layer's first two weight
   // groups ahead of the barrier that ends the layer before (they were five exposed L2 / HBM round trips per tile).
+  // (as disc_forward_kernel: the thread's column kx, its source and its offset in that source's rows)
   float xr[XPT];
+  const int kx = tid & (KIN - 1);
+  const bool second = kx >= ds;
+  int xcol = 0;
+  if (kx < p.D) xcol = second ? (p.mask2 ? p.mask2[kx - ds] : kx - ds) : (p.mask ? p.mask[kx] : kx);
   auto load_x = [&](long tile) {
     const long row0 = tile * RT16;
+    const float* src = second ? p.x2 : p.x;
+    const int stride = second ? p.stride2 : p.Dx;
 #pragma unroll
     for (int i = 0; i < XPT; ++i) {
-      const int e = tid + THREADS * i, m = e / KIN, k = e - m * KIN;
+      const int m = (tid + THREADS * i) / KIN;
       float v = 0.f;
-      if (row0 + m < p.B && k < p.D) v = p.x[(size_t)(row0 + m) * p.Dx + (p.mask ? p.mask[k] : k)];
+      if (row0 + m < p.B && kx < p.D) v = src[(size_t)(row0 + m) * stride + xcol];
       xr[i] = v;
     }
   };
@@ -378,10 +407,15 @@ __global__ __launch_bounds__(THREADS, 2) void disc_forward16_kernel(DiscArgs p) 
   const bool standardise = p.mean || p.colstats;
   if (tid < p.D && standardise) {
     double mean, sd;
-    if (p.colstats) {
-      const double cnt = p.colstats[tid] + 1e-2;       // Standardizer.update_mean_std (networks.py:76-81)
-      mean = p.colstats[p.D + tid] / cnt;
-      sd = sqrt(fmax((p.colstats[2 * p.D + tid] + 1e-2) / cnt - mean * mean, 1e-2));
+    if (p.colstats && tid >= ds && !p.std2) {   // actions pass through (see disc_forward_kernel)
+      mean = 0.0;
+      sd = 1.0;
+    } else if (p.colstats) {
+      const double* cs = tid < ds ? p.colstats : p.colstats2;
+      const int j = tid < ds ? tid : tid - ds;
+      const double cnt = cs[j] + 1e-2;                 // Standardizer.update_mean_std (networks.py:76-81)
+      mean = cs[ds + j] / cnt;
+      sd = sqrt(fmax((cs[2 * ds + j] + 1e-2) / cnt - mean * mean, 1e-2));
     } else {
       mean = p.mean[tid];
       sd = p.sd[tid];
@@ -528,18 +562,10 @@ extern "C" int oly_disc_pack(oly_ctx* ctx, int in_dim, int hidden, int enc_out, 
   return OLY_OK;
 }
 
-extern "C" int oly_disc_forward(oly_ctx* ctx, int64_t B, int Dx, int D, const float* x, const int32_t* mask,
-                                const double* mean, const double* sd, const double* colstats, const float* packed,
-                                const float* eps, float* reward, float* logits, float* mu, float* logvar,
-                                oly_stream stream) {
-  if (!ctx) return OLY_EINVAL;
-  if (B < 0 || Dx <= 0 || D <= 0 || D > MAX_IN || (!mask && D != Dx) || (mean == nullptr) != (sd == nullptr) ||
-      (mean && colstats))
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward: bad shape (B %ld, Dx %d, D %d), only one of mean / std, or both mean / std and colstats given",
-             (long)B, Dx, D);
-  if (B == 0) return OLY_OK;
-  if (!x || !packed || (!reward && !logits && !mu && !logvar)) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward: NULL input or no output");
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward: packed must be 16-byte aligned");
+namespace {
+int launch_disc_forward(oly_ctx* ctx, DiscArgs a, oly_stream stream) {
+  const int64_t B = a.B;
+  const int D = a.D;
   long ntiles = (B + RT - 1) / RT;
   if (ntiles > 0x7fffffffL) OLY_FAIL(ctx, OLY_ERANGE, "oly_disc_forward: B too large");
   const long slots = 2L * (ctx->num_cu > 0 ? ctx->num_cu : 256);      // two resident workgroups per CU
@@ -558,7 +584,7 @@ extern "C" int oly_disc_forward(oly_ctx* ctx, int64_t B, int Dx, int D, const fl
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)DISC_LDS));
     ctx->disc_attr_done = true;
   }
-  DiscArgs a{(long)B, Dx, D, (int)ntiles, x, mask, mean, sd, colstats, packed, eps, reward, logits, mu, logvar};
+  a.ntiles = (int)ntiles;
   const dim3 grid((unsigned)(ntiles < slots ? ntiles : slots));
   if (rows16 && D <= 32) hipLaunchKernelGGL(disc_forward16_kernel<2>, grid, dim3(THREADS), DISC16_LDS, oly_s(stream), a);
   else if (rows16) hipLaunchKernelGGL(disc_forward16_kernel<4>, grid, dim3(THREADS), DISC16_LDS, oly_s(stream), a);
@@ -566,6 +592,46 @@ extern "C" int oly_disc_forward(oly_ctx* ctx, int64_t B, int Dx, int D, const fl
   else hipLaunchKernelGGL(disc_forward_kernel<8>, grid, dim3(THREADS), DISC_LDS, oly_s(stream), a);
   OLY_LAUNCH_CHECK(ctx, "disc_forward_kernel");
   return OLY_OK;
+}
+}  // namespace
+
+extern "C" int oly_disc_forward(oly_ctx* ctx, int64_t B, int Dx, int D, const float* x, const int32_t* mask,
+                                const double* mean, const double* sd, const double* colstats, const float* packed,
+                                const float* eps, float* reward, float* logits, float* mu, float* logvar,
+                                oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (B < 0 || Dx <= 0 || D <= 0 || D > MAX_IN || (!mask && D != Dx) || (mean == nullptr) != (sd == nullptr) ||
+      (mean && colstats))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward: bad shape (B %ld, Dx %d, D %d), only one of mean / std, or both mean / std and colstats given",
+             (long)B, Dx, D);
+  if (B == 0) return OLY_OK;
+  if (!x || !packed || (!reward && !logits && !mu && !logvar)) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward: NULL input or no output");
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward: packed must be 16-byte aligned");
+  DiscArgs a{(long)B, Dx, D, 0, x, mask, mean, sd, colstats, packed, eps, reward, logits, mu, logvar};
+  return launch_disc_forward(ctx, a, stream);
+}
+
+extern "C" int oly_disc_forward_pair(oly_ctx* ctx, int64_t B, int Dx, int Ds, const float* x, const int32_t* mask,
+                                     const oly_disc_pair* pair, const double* stats_a, const double* stats_b,
+                                     const float* packed, const float* eps, float* reward, float* logits, float* mu,
+                                     float* logvar, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (!pair)
+    return oly_disc_forward(ctx, B, Dx, Ds, x, mask, nullptr, nullptr, stats_a, packed, eps, reward, logits, mu, logvar, stream);
+  if (B < 0 || Dx <= 0 || Ds <= 0 || Ds > MAX_IN || (!mask && Ds != Dx))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward_pair: bad shape (B %ld, Dx %d, Ds %d)", (long)B, Dx, Ds);
+  const char* why = oly_disc::pair_error(pair, Ds);
+  if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward_pair: %s (Ds %d, d2 %d)", why, Ds, pair->d2);
+  if (pair->standardise && (stats_a == nullptr) != (stats_b == nullptr))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward_pair: a standardised second part takes both stats_a and stats_b, or neither");
+  if (B == 0) return OLY_OK;
+  if (!x || !packed || (!reward && !logits && !mu && !logvar))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward_pair: NULL input or no output");
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_forward_pair: packed must be 16-byte aligned");
+  DiscArgs a{(long)B, Dx, Ds + pair->d2, 0, x, mask, nullptr, nullptr, stats_a, packed, eps, reward, logits, mu, logvar,
+             pair->d2, pair->standardise != 0, pair->stride2, pair->x2, pair->mask2, stats_b};
+  return launch_disc_forward(ctx, a, stream);
 }
 
 // make_discrim_reward's whole device path in ONE call: (optionally) the re-pack of the current weights, then
@@ -586,4 +652,45 @@ extern "C" int oly_disc_reward_step(oly_ctx* ctx, int64_t B, int D, const float*
   rc = oly_col_stats(ctx, (int)B, D, x, colstats, accumulate, stream);
   if (rc != OLY_OK) return rc;
   return oly_disc_forward(ctx, B, D, D, x, nullptr, nullptr, nullptr, colstats, packed, eps, reward, logits, mu, logvar, stream);
+}
+
+// The same on a paired input, with the state mask and the second part's mask applied inside the kernels: the
+// Standardizer's update with the states (S1, kept in stats_a), for next states its second update with them (S2), the
+// forward on (S1, S2).  The statistics launches are K18's (oly_masked_col_stats).
+extern "C" int oly_disc_reward_step_pair(oly_ctx* ctx, int64_t B, int Dx, int Ds, const float* x, const int32_t* mask,
+                                         const oly_disc_pair* pair, double* colstats, double* stats_a, int accumulate,
+                                         const float* const* weights, float* packed, const float* eps, float* reward,
+                                         float* logits, float* mu, float* logvar, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (B < 0 || B > 0x7fffffffL || Dx <= 0 || Ds <= 0 || Ds > MAX_IN || (!mask && Ds != Dx) || !x || !colstats || !packed)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_reward_step_pair: bad shape (B %ld, Dx %d, Ds %d) or NULL x / colstats / packed",
+             (long)B, Dx, Ds);
+  if (pair) {
+    const char* why = oly_disc::pair_error(pair, Ds);
+    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_reward_step_pair: %s (Ds %d, d2 %d)", why, Ds, pair->d2);
+    if (pair->standardise && !stats_a)
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_reward_step_pair: stats_a (the scratch block [3, Ds]) is NULL for a standardised second part");
+    if (pair->standardise && stats_a == colstats)
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_reward_step_pair: stats_a must not be colstats (S1 is kept apart from the running sums)");
+  }
+  // states only on whole rows: oly_disc_reward_step itself (K7's statistics launch), bit for bit
+  if (!pair && !mask)
+    return oly_disc_reward_step(ctx, B, Ds, x, colstats, accumulate, weights, packed, eps, reward, logits, mu, logvar, stream);
+  int rc;
+  if (weights) {
+    for (int i = 0; i < 10; ++i)
+      if (!weights[i]) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_reward_step_pair: NULL weight pointer");
+    rc = oly_disc_pack(ctx, Ds + (pair ? pair->d2 : 0), H1, H2, ZD, weights[0], weights[1], weights[2], weights[3], weights[4],
+                       weights[5], weights[6], weights[7], weights[8], weights[9], packed, stream);
+    if (rc != OLY_OK) return rc;
+  }
+  const bool two = pair && pair->standardise;
+  rc = oly_masked_col_stats(ctx, (long)B, Dx, Ds, x, mask, colstats, accumulate, two ? stats_a : nullptr, stream);
+  if (rc != OLY_OK) return rc;
+  if (two) {
+    rc = oly_masked_col_stats(ctx, (long)B, pair->stride2, Ds, pair->x2, pair->mask2, colstats, 1, nullptr, stream);
+    if (rc != OLY_OK) return rc;
+  }
+  return oly_disc_forward_pair(ctx, B, Dx, Ds, x, mask, pair, two ? stats_a : colstats, colstats, packed, eps, reward, logits,
+                               mu, logvar, stream);
 }

@@ -18,6 +18,12 @@
 //                           outputs and colstats += minibatch b; workgroups 1 .. 16 sum minibatch b+1's rows into the
 //                           statistics partials launch A of b+1 reads.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits.
+//
+// oly_disc_fit_epoch_pair is the same epoch on a paired input (oly_disc_pair: (s, s') with use_next_states, (s, a) with
+// actions; VariationalNet.forward, networks.py:258-278): launch A gathers perm rows from both sources, standardises the
+// states with colstats + the minibatch's states and the next states with that + the minibatch's next states (actions
+// raw); the statistics partials carry both sets of column sums and workgroup 0's colstats += adds both.  The states-only
+// entry point is the paired one with no second part.
 #include <cstdlib>
 
 #include "disc_common.h"
@@ -111,6 +117,8 @@ struct AdamK {
 
 struct FitArgs {
   int in_dim, n_rows, n_plcy;
+  int ds, d2, std2, stride2; // x [n_rows, ds] | x2 [n_rows, stride2]'s first d2 columns (d2 = in_dim - ds, 0: none);
+  const float* x2;           // std2: x2 goes through the Standardizer (next states), else raw (actions)
   int R, Rn;                 // rows of minibatch b / b+1 (0: none)
   long off, off_next;        // first position of minibatch b / b+1 in perm and eps
   const int32_t* perm;
@@ -137,9 +145,10 @@ __device__ void stats_slice(const FitArgs& a, long off, int R, int s, double* pa
   const int tid = threadIdx.x, k = tid & (MAX_IN - 1), grp = tid >> 6;
   const int per = (R + NSP - 1) / NSP, r0 = s * per, r1 = min(R, r0 + per);
   double sum = 0.0, ss = 0.0;
-  if (k < a.in_dim)
+  if (k < a.ds || (k < a.in_dim && a.std2))
     for (int r = r0 + grp; r < r1; r += 4) {
-      const double v = a.x[(size_t)row_at(a, off + r) * a.in_dim + k];
+      const size_t row = row_at(a, off + r);
+      const double v = k < a.ds ? a.x[row * a.ds + k] : a.x2[row * a.stride2 + (k - a.ds)];
       sum += v;
       ss += v * v;
     }
@@ -204,15 +213,32 @@ __global__ __launch_bounds__(THREADS) void fitd_rows_kernel(FitArgs a) {
 
   if (tid < in_dim) {   // Standardizer.update_mean_std with the minibatch's rows (networks.py:76-81), as K16
     const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
+    const int ds = a.ds;
     double s = 0.0, ss = 0.0;
     for (int p = 0; p < NSP; ++p) {
       s += sp[p * 2 * MAX_IN + tid];
       ss += sp[p * 2 * MAX_IN + MAX_IN + tid];
     }
-    const double cnt = a.colstats[tid] + (double)R + 1e-2;
-    const double mean = (a.colstats[in_dim + tid] + s) / cnt;
+    double mean = 0.0, sd = 1.0;        // an action column passes through: f32((f64(a) - 0) / 1) is a
+    if (tid < ds) {
+      const double cnt = a.colstats[tid] + (double)R + 1e-2;
+      mean = (a.colstats[ds + tid] + s) / cnt;
+      sd = sqrt(fmax((a.colstats[2 * ds + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    } else if (a.std2) {
+      // a next-state column: the Standardizer has taken the minibatch's states in, then its next states
+      // (VariationalNet.forward, networks.py:266-270), so column j's statistics hold both sets of sums
+      const int j = tid - ds;
+      double s1 = 0.0, ss1 = 0.0;
+      for (int p = 0; p < NSP; ++p) {
+        s1 += sp[p * 2 * MAX_IN + j];
+        ss1 += sp[p * 2 * MAX_IN + MAX_IN + j];
+      }
+      const double cnt = a.colstats[j] + (double)R + (double)R + 1e-2;
+      mean = ((a.colstats[ds + j] + s1) + s) / cnt;
+      sd = sqrt(fmax(((a.colstats[2 * ds + j] + ss1) + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    }
     st[tid] = mean;
-    st[MAX_IN + tid] = sqrt(fmax((a.colstats[2 * in_dim + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    st[MAX_IN + tid] = sd;
     if (blockIdx.x == 0) {
       double* d = reinterpret_cast<double*>(ws + a.W.delta);
       d[tid] = s;
@@ -226,7 +252,10 @@ __global__ __launch_bounds__(THREADS) void fitd_rows_kernel(FitArgs a) {
     const int m = e / MAX_IN, k = e & (MAX_IN - 1), row = rows_x[m];
     float v = 0.f;
     // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
-    if (row >= 0 && k < in_dim) v = (float)(((double)a.x[(size_t)row * in_dim + k] - st[k]) / st[MAX_IN + k]);
+    if (row >= 0 && k < in_dim) {
+      const float* src = k < a.ds ? a.x + ((size_t)row * a.ds + k) : a.x2 + ((size_t)row * a.stride2 + (k - a.ds));
+      v = (float)(((double)*src - st[k]) / st[MAX_IN + k]);
+    }
     xT[act16_index(k, m)] = v;
     if (row >= 0) ws[a.W.xs + (size_t)(row0 + m) * MAX_IN + k] = v;
   }
@@ -543,11 +572,20 @@ __global__ __launch_bounds__(THREADS) void fitd_weights_kernel(FitArgs a) {
       if (a.kl_out) a.kl_out[0] = kl;
       if (a.beta_out) a.beta_out[0] = nb;
     }
-    if (tid < a.in_dim) {
+    if (tid < a.ds) {
       const double* d = reinterpret_cast<const double*>(a.ws + W.delta);
-      a.colstats[tid] = a.colstats[tid] + (double)R;
-      a.colstats[a.in_dim + tid] = a.colstats[a.in_dim + tid] + d[tid];
-      a.colstats[2 * a.in_dim + tid] = a.colstats[2 * a.in_dim + tid] + d[MAX_IN + tid];
+      const int ds = a.ds;
+      double cnt = a.colstats[tid] + (double)R;
+      double sum = a.colstats[ds + tid] + d[tid];
+      double sq = a.colstats[2 * ds + tid] + d[MAX_IN + tid];
+      if (a.std2) {       // the minibatch's next states, taken in after its states
+        cnt += (double)R;
+        sum += d[ds + tid];
+        sq += d[MAX_IN + ds + tid];
+      }
+      a.colstats[tid] = cnt;
+      a.colstats[ds + tid] = sum;
+      a.colstats[2 * ds + tid] = sq;
     }
   } else if (blockIdx.x <= NSP && a.Rn > 0) {
     stats_slice(a, a.off_next, a.Rn, blockIdx.x - 1, dred);
@@ -574,10 +612,26 @@ extern "C" int64_t oly_disc_fit_ws_floats(int batch, int in_dim) {
   return (int64_t)ws_layout(batch).total;
 }
 
+extern "C" int64_t oly_disc_fit_pair_ws_floats(int batch, int ds, int d2, int standardise) {
+  if (ds <= 0 || d2 <= 0 || ds > MAX_IN || d2 > MAX_IN || (standardise && d2 != ds)) return -1;
+  return oly_disc_fit_ws_floats(batch, ds + d2);
+}
+
 extern "C" int oly_disc_fit_epoch(oly_ctx* ctx, const oly_disc_fit* f, const int32_t* perm, int n_rows, int batch,
                                   oly_stream stream) {
+  return oly_disc_fit_epoch_pair(ctx, f, nullptr, perm, n_rows, batch, stream);
+}
+
+extern "C" int oly_disc_fit_epoch_pair(oly_ctx* ctx, const oly_disc_fit* f, const oly_disc_pair* pair, const int32_t* perm,
+                                       int n_rows, int batch, oly_stream stream) {
   if (!ctx) return OLY_EINVAL;
   if (!f || !perm) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch: NULL argument");
+  if (pair) {
+    const char* why = f->in_dim - pair->d2 <= 0 ? "d2 leaves the first part no column"
+                                                : oly_disc::pair_error(pair, f->in_dim - pair->d2);
+    if (!why && pair->mask2) why = "the fit takes the second part already gathered (mask2 NULL)";
+    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch_pair: %s (in_dim %d, d2 %d)", why, f->in_dim, pair->d2);
+  }
   if (n_rows < 0 || oly_disc_fit_ws_floats(batch, f->in_dim) < 0)
     OLY_FAIL(ctx, OLY_ERANGE, "oly_disc_fit_epoch: supported: 0 < batch <= %d, 0 < in_dim <= %d (got n %d, batch %d, in %d)",
              MAX_BATCH, MAX_IN, n_rows, batch, f->in_dim);
@@ -595,6 +649,13 @@ extern "C" int oly_disc_fit_epoch(oly_ctx* ctx, const oly_disc_fit* f, const int
   const int in_dim = f->in_dim;
   FitArgs a{};
   a.in_dim = in_dim;
+  a.ds = in_dim - (pair ? pair->d2 : 0);
+  if (pair) {
+    a.d2 = pair->d2;
+    a.std2 = pair->standardise != 0;
+    a.stride2 = pair->stride2;
+    a.x2 = pair->x2;
+  }
   a.n_rows = n_rows;
   a.n_plcy = f->n_plcy;
   a.perm = perm;

@@ -8,6 +8,12 @@
 //                            reward formula (reward_of, disc_common.h) on the logit.
 //   oly_gail_reward_step     the Standardizer's update with the masked rows (networks.py:68-81), then that forward.
 //   oly_gail_disc_fit_epoch  one epoch of _fit_discriminator's minibatch loop (gail_TRPO.py:167-220, states only).
+//   oly_gail_*_pair          the same three on a paired input (oly_disc_pair: (s, s') with use_next_states, (s, a) with
+//                            actions; DiscriminatorNetwork.preprocess_inputs, networks.py:216-234).  A row is staged from
+//                            two sources; the states' half is standardised with the statistics after the states went in,
+//                            the next states' half with those after the next states went in as well (two updates per
+//                            forward, networks.py:224-227), actions raw.  The states-only entry points are the paired
+//                            ones with no second part.
 //
 // The fit, per call: oly_ilmlp_pack (the stream from param), gfit_prologue_kernel (the transposed W2 stream of the
 // backward, the statistics partials of minibatch 0), then per minibatch b
@@ -76,6 +82,8 @@ struct AdamK {
 
 struct FitArgs {
   int in_dim, n_rows, n_plcy;
+  int ds, d2, std2, stride2; // x [n_rows, ds] | x2 [n_rows, stride2]'s first d2 columns (d2 = in_dim - ds, 0: none);
+  const float* x2;           // std2: x2 goes through the Standardizer (next states), else raw (actions)
   int R, Rn;                 // rows of minibatch b / b+1 (0: none)
   long off, off_next;        // first position of minibatch b / b+1 in perm
   const int32_t* perm;
@@ -100,9 +108,10 @@ __device__ void stats_slice(const FitArgs& a, long off, int R, int s, double* pa
   const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
   const int per = (R + NSP - 1) / NSP, r0 = s * per, r1 = min(R, r0 + per);
   double sum = 0.0, ss = 0.0;
-  if (k < a.in_dim)
+  if (k < a.ds || (k < a.in_dim && a.std2))
     for (int r = r0 + grp; r < r1; r += 4) {
-      const double v = a.x[(size_t)row_at(a, off + r) * a.in_dim + k];
+      const size_t row = row_at(a, off + r);
+      const double v = k < a.ds ? a.x[row * a.ds + k] : a.x2[row * a.stride2 + (k - a.ds)];
       sum += v;
       ss += v * v;
     }
@@ -136,8 +145,12 @@ constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16 + H2 + 16
 constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (2 * IN_MAX + 2 * 16);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
 
+// waves_per_eu(7, 8) holds the allocator to the register budget of seven waves per SIMD (72 VGPRs), which both
+// instantiations fit without a spill.  Left to itself it gives both 74 with the two-source staging (six waves in the
+// compiler's report; the 32-column instantiation had 72 before).  A 512-thread workgroup with this kernel's LDS never has
+// seven waves resident on a SIMD, so the attribute bounds registers and nothing else.
 template <int G1>
-__global__ __launch_bounds__(RTHREADS) void gfit_rows_kernel(FitArgs a) {
+__global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(7, 8))) void gfit_rows_kernel(FitArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xT = lds;                       // [64 x 16]   standardised input (act16 images, mlp_tiles.h)
   float* hA = xT + IN_MAX * 16;          // [512 x 16]  h1
@@ -160,15 +173,32 @@ __global__ __launch_bounds__(RTHREADS) void gfit_rows_kernel(FitArgs a) {
 
   if (tid < in_dim) {   // Standardizer.update_mean_std with the minibatch's rows (networks.py:76-81), as K15
     const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
+    const int ds = a.ds;
     double s = 0.0, ss = 0.0;
     for (int p = 0; p < NSP; ++p) {
       s += sp[p * 2 * IN_MAX + tid];
       ss += sp[p * 2 * IN_MAX + IN_MAX + tid];
     }
-    const double cnt = a.colstats[tid] + (double)R + 1e-2;
-    const double mean = (a.colstats[in_dim + tid] + s) / cnt;
+    double mean = 0.0, sd = 1.0;        // an action column passes through: f32((f64(a) - 0) / 1) is a
+    if (tid < ds) {
+      const double cnt = a.colstats[tid] + (double)R + 1e-2;
+      mean = (a.colstats[ds + tid] + s) / cnt;
+      sd = sqrt(fmax((a.colstats[2 * ds + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    } else if (a.std2) {
+      // a next-state column: the Standardizer has taken the minibatch's states in, then its next states
+      // (preprocess_inputs, networks.py:224-227), so column j's statistics hold both sets of sums
+      const int j = tid - ds;
+      double s1 = 0.0, ss1 = 0.0;
+      for (int p = 0; p < NSP; ++p) {
+        s1 += sp[p * 2 * IN_MAX + j];
+        ss1 += sp[p * 2 * IN_MAX + IN_MAX + j];
+      }
+      const double cnt = a.colstats[j] + (double)R + (double)R + 1e-2;
+      mean = ((a.colstats[ds + j] + s1) + s) / cnt;
+      sd = sqrt(fmax(((a.colstats[2 * ds + j] + ss1) + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    }
     st[tid] = mean;
-    st[IN_MAX + tid] = sqrt(fmax((a.colstats[2 * in_dim + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    st[IN_MAX + tid] = sd;
     if (blockIdx.x == 0) {
       double* d = reinterpret_cast<double*>(ws + a.W.delta);
       d[tid] = s;
@@ -182,7 +212,10 @@ __global__ __launch_bounds__(RTHREADS) void gfit_rows_kernel(FitArgs a) {
     const int m = e / IN_MAX, k = e & (IN_MAX - 1), row = rows_x[m];
     float v = 0.f;
     // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
-    if (row >= 0 && k < in_dim) v = (float)(((double)a.x[(size_t)row * in_dim + k] - st[k]) / st[IN_MAX + k]);
+    if (row >= 0 && k < in_dim) {
+      const float* src = k < a.ds ? a.x + ((size_t)row * a.ds + k) : a.x2 + ((size_t)row * a.stride2 + (k - a.ds));
+      v = (float)(((double)*src - st[k]) / st[IN_MAX + k]);
+    }
     xT[act16_index(k, m)] = v;
     ws[a.W.xs + ((size_t)((row0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
   }
@@ -432,11 +465,20 @@ __global__ __launch_bounds__(THREADS) void gfit_weights_kernel(FitArgs a) {
       if (a.bce_out) a.bce_out[0] = bce;
       if (a.ent_out) a.ent_out[0] = ent;
     }
-    if (tid < a.in_dim) {
+    if (tid < a.ds) {
       const double* d = reinterpret_cast<const double*>(a.ws + W.delta);
-      a.colstats[tid] = a.colstats[tid] + (double)R;
-      a.colstats[a.in_dim + tid] = a.colstats[a.in_dim + tid] + d[tid];
-      a.colstats[2 * a.in_dim + tid] = a.colstats[2 * a.in_dim + tid] + d[IN_MAX + tid];
+      const int ds = a.ds;
+      double cnt = a.colstats[tid] + (double)R;
+      double sum = a.colstats[ds + tid] + d[tid];
+      double sq = a.colstats[2 * ds + tid] + d[IN_MAX + tid];
+      if (a.std2) {       // the minibatch's next states, taken in after its states
+        cnt += (double)R;
+        sum += d[ds + tid];
+        sq += d[IN_MAX + ds + tid];
+      }
+      a.colstats[tid] = cnt;
+      a.colstats[ds + tid] = sum;
+      a.colstats[2 * ds + tid] = sq;
     }
   } else if (blockIdx.x <= NSP && a.Rn > 0) {
     stats_slice(a, a.off_next, a.Rn, blockIdx.x - 1, dred);
@@ -486,7 +528,8 @@ __global__ __launch_bounds__(THREADS) void gail_stats_partial_kernel(long B, int
 }
 
 __global__ __launch_bounds__(64) void gail_stats_finish_kernel(long B, int D, const double* __restrict__ part,
-                                                               double* __restrict__ colstats, int accumulate) {
+                                                               double* __restrict__ colstats, int accumulate,
+                                                               double* __restrict__ copy_out) {
   const int k = threadIdx.x;
   if (k >= D) return;
   double s = 0.0, ss = 0.0;
@@ -498,6 +541,9 @@ __global__ __launch_bounds__(64) void gail_stats_finish_kernel(long B, int D, co
     colstats[k] += (double)B; colstats[D + k] += s; colstats[2 * D + k] += ss;
   } else {
     colstats[k] = (double)B; colstats[D + k] = s; colstats[2 * D + k] = ss;
+  }
+  if (copy_out) {      // the statistics as they stand now, for a forward that runs after a later update
+    copy_out[k] = colstats[k]; copy_out[D + k] = colstats[D + k]; copy_out[2 * D + k] = colstats[2 * D + k];
   }
 }
 static_assert(sizeof(double) * STAT_BLOCKS * 2 * IN_MAX <= sizeof(double) * OLY_STATS_MAX_BLOCKS * 2 * OLY_MAX_OBS,
@@ -527,7 +573,50 @@ int launch_forward(oly_ctx* ctx, const FwdArgs& a, oly_stream stream) {
   OLY_LAUNCH_CHECK(ctx, "gail discriminator forward");
   return OLY_OK;
 }
+
 }  // namespace
+
+int oly_masked_col_stats(oly_ctx* ctx, long B, int Dx, int D, const float* x, const int32_t* mask, double* colstats,
+                         int accumulate, double* copy_out, oly_stream stream) {
+  hipLaunchKernelGGL(gail_stats_partial_kernel, dim3(STAT_BLOCKS), dim3(THREADS), 0, oly_s(stream), B, Dx, D, x, mask,
+                     ctx->stats_ws);
+  hipLaunchKernelGGL(gail_stats_finish_kernel, dim3(1), dim3(64), 0, oly_s(stream), B, D, ctx->stats_ws, colstats,
+                     accumulate, copy_out);
+  OLY_LAUNCH_CHECK(ctx, "gail statistics kernels");
+  return OLY_OK;
+}
+
+extern "C" int oly_gail_disc_forward_pair(oly_ctx* ctx, int64_t B, int Dx, int Ds, const float* x, const int32_t* mask,
+                                          const oly_disc_pair* pair, const double* stats_a, const double* stats_b,
+                                          const float* packed, float* reward, float* logits, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (B < 0 || B > 0x7fffffffL || Dx <= 0 || Ds <= 0 || Ds > IN_MAX || (!mask && Ds != Dx))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward_pair: bad shape (B %ld, Dx %d, Ds %d; Ds <= %d)", (long)B, Dx, Ds, IN_MAX);
+  if (pair) {
+    const char* why = oly_disc::pair_error(pair, Ds);
+    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward_pair: %s (Ds %d, d2 %d)", why, Ds, pair->d2);
+    if (pair->standardise && (stats_a == nullptr) != (stats_b == nullptr))
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward_pair: a standardised second part takes both stats_a and stats_b, or neither");
+  }
+  if (!x || !packed || (!reward && !logits)) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward_pair: NULL input or no output");
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward_pair: packed must be 16-byte aligned");
+  if (B == 0) return OLY_OK;
+  FwdArgs a{(long)B, Ds, 1, OLY_ACT_IDENTITY, Dx, x, mask, nullptr, nullptr, stats_a, packed, logits, reward};
+  if (pair) {
+    a.in_dim = Ds + pair->d2;
+    a.d2 = pair->d2;
+    a.std2 = pair->standardise != 0;
+    a.stride2 = pair->stride2;
+    a.x2 = pair->x2;
+    a.mask2 = pair->mask2;
+    a.colstats2 = stats_b;
+  }
+  // 16-row tiles while the 32-row tiles would leave CUs without a second workgroup (as K16)
+  const long slots = 2L * (ctx->num_cu > 0 ? ctx->num_cu : 256);
+  if ((B + 31) / 32 < slots) return launch_forward<1>(ctx, a, stream);
+  return launch_forward<2>(ctx, a, stream);
+}
 
 extern "C" int oly_gail_disc_forward(oly_ctx* ctx, int64_t B, int Dx, int D, const float* x, const int32_t* mask,
                                      const double* mean, const double* sd, const double* colstats, const float* packed,
@@ -540,11 +629,51 @@ extern "C" int oly_gail_disc_forward(oly_ctx* ctx, int64_t B, int Dx, int D, con
   if (!x || !packed || (!reward && !logits)) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward: NULL input or no output");
   if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_forward: packed must be 16-byte aligned");
   if (B == 0) return OLY_OK;
+  if (!mean) return oly_gail_disc_forward_pair(ctx, B, Dx, D, x, mask, nullptr, colstats, nullptr, packed, reward, logits, stream);
   const FwdArgs a{(long)B, D, 1, OLY_ACT_IDENTITY, Dx, x, mask, mean, sd, colstats, packed, logits, reward};
   // 16-row tiles while the 32-row tiles would leave CUs without a second workgroup (as K16)
   const long slots = 2L * (ctx->num_cu > 0 ? ctx->num_cu : 256);
   if ((B + 31) / 32 < slots) return launch_forward<1>(ctx, a, stream);
   return launch_forward<2>(ctx, a, stream);
+}
+
+extern "C" int oly_gail_reward_step_pair(oly_ctx* ctx, int64_t B, int Dx, int Ds, const float* x, const int32_t* mask,
+                                         const oly_disc_pair* pair, double* colstats, double* stats_a, int accumulate,
+                                         const float* const* weights, float* packed, float* reward, float* logits,
+                                         oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (B < 0 || B > 0x7fffffffL || Dx <= 0 || Ds <= 0 || Ds > IN_MAX || (!mask && Ds != Dx))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: bad shape (B %ld, Dx %d, Ds %d; Ds <= %d)", (long)B, Dx, Ds, IN_MAX);
+  if (pair) {
+    const char* why = oly_disc::pair_error(pair, Ds);
+    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: %s (Ds %d, d2 %d)", why, Ds, pair->d2);
+    if (pair->standardise && !stats_a)
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: stats_a (the scratch block [3, Ds]) is NULL for a standardised second part");
+    if (pair->standardise && stats_a == colstats)
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: stats_a must not be colstats (S1 is kept apart from the running sums)");
+  }
+  if (!x || !colstats || !packed || (!reward && !logits))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: NULL x / colstats / packed, or no output");
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: packed must be 16-byte aligned");
+  const int D = Ds + (pair ? pair->d2 : 0);
+  if (weights) {
+    for (int i = 0; i < 6; ++i)
+      if (!weights[i]) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step_pair: NULL weight pointer");
+    const int rc = oly_ilmlp_pack(ctx, D, H1, H2, 1, weights[0], weights[1], weights[2], weights[3], weights[4], weights[5],
+                                  packed, stream);
+    if (rc != OLY_OK) return rc;
+  }
+  const bool two = pair && pair->standardise;
+  // _stand(states): the running sums take the states in; S1 is what the states' half is standardised with
+  int rc = oly_masked_col_stats(ctx, (long)B, Dx, Ds, x, mask, colstats, accumulate, two ? stats_a : nullptr, stream);
+  if (rc != OLY_OK) return rc;
+  if (two) {  // _stand(next_states): a second update, S2 = S1 + the next states (networks.py:226-227)
+    rc = oly_masked_col_stats(ctx, (long)B, pair->stride2, Ds, pair->x2, pair->mask2, colstats, 1, nullptr, stream);
+    if (rc != OLY_OK) return rc;
+  }
+  return oly_gail_disc_forward_pair(ctx, B, Dx, Ds, x, mask, pair, two ? stats_a : colstats, colstats, packed, reward, logits,
+                                    stream);
 }
 
 extern "C" int oly_gail_reward_step(oly_ctx* ctx, int64_t B, int Dx, int D, const float* x, const int32_t* mask,
@@ -556,19 +685,11 @@ extern "C" int oly_gail_reward_step(oly_ctx* ctx, int64_t B, int Dx, int D, cons
   if (!x || !colstats || !packed || (!reward && !logits))
     OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step: NULL x / colstats / packed, or no output");
   if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step: packed must be 16-byte aligned");
-  if (weights) {
+  if (weights)
     for (int i = 0; i < 6; ++i)
       if (!weights[i]) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_reward_step: NULL weight pointer");
-    const int rc = oly_ilmlp_pack(ctx, D, H1, H2, 1, weights[0], weights[1], weights[2], weights[3], weights[4], weights[5],
-                                  packed, stream);
-    if (rc != OLY_OK) return rc;
-  }
-  hipLaunchKernelGGL(gail_stats_partial_kernel, dim3(STAT_BLOCKS), dim3(THREADS), 0, oly_s(stream), (long)B, Dx, D, x, mask,
-                     ctx->stats_ws);
-  hipLaunchKernelGGL(gail_stats_finish_kernel, dim3(1), dim3(64), 0, oly_s(stream), (long)B, D, ctx->stats_ws, colstats,
-                     accumulate);
-  OLY_LAUNCH_CHECK(ctx, "gail statistics kernels");
-  return oly_gail_disc_forward(ctx, B, Dx, D, x, mask, nullptr, nullptr, colstats, packed, reward, logits, stream);
+  return oly_gail_reward_step_pair(ctx, B, Dx, D, x, mask, nullptr, colstats, nullptr, accumulate, weights, packed, reward,
+                                   logits, stream);
 }
 
 extern "C" int64_t oly_gail_disc_fit_ws_floats(int batch, int in_dim) {
@@ -576,10 +697,25 @@ extern "C" int64_t oly_gail_disc_fit_ws_floats(int batch, int in_dim) {
   return (int64_t)ws_layout(batch).total;
 }
 
+extern "C" int64_t oly_gail_disc_fit_pair_ws_floats(int batch, int ds, int d2, int standardise) {
+  if (ds <= 0 || d2 <= 0 || ds > IN_MAX || d2 > IN_MAX || (standardise && d2 != ds)) return -1;
+  return oly_gail_disc_fit_ws_floats(batch, ds + d2);
+}
+
 extern "C" int oly_gail_disc_fit_epoch(oly_ctx* ctx, const oly_gail_disc_fit* f, const int32_t* perm, int n_rows,
                                        int batch, oly_stream stream) {
+  return oly_gail_disc_fit_epoch_pair(ctx, f, nullptr, perm, n_rows, batch, stream);
+}
+
+extern "C" int oly_gail_disc_fit_epoch_pair(oly_ctx* ctx, const oly_gail_disc_fit* f, const oly_disc_pair* pair,
+                                            const int32_t* perm, int n_rows, int batch, oly_stream stream) {
   if (!ctx) return OLY_EINVAL;
   if (!f || !perm) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: NULL argument");
+  if (pair) {
+    const char* why = f->in_dim - pair->d2 <= 0 ? "d2 leaves the first part no column" : oly_disc::pair_error(pair, f->in_dim - pair->d2);
+    if (!why && pair->mask2) why = "the fit takes the second part already gathered (mask2 NULL)";
+    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch_pair: %s (in_dim %d, d2 %d)", why, f->in_dim, pair->d2);
+  }
   if (n_rows < 0 || oly_gail_disc_fit_ws_floats(batch, f->in_dim) < 0)
     OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: supported: 0 < batch <= %d, 0 < in_dim <= %d (got n %d, batch %d, in %d)",
              MAX_BATCH, IN_MAX, n_rows, batch, f->in_dim);
@@ -597,6 +733,13 @@ extern "C" int oly_gail_disc_fit_epoch(oly_ctx* ctx, const oly_gail_disc_fit* f,
   const int in_dim = f->in_dim;
   FitArgs a{};
   a.in_dim = in_dim;
+  a.ds = in_dim - (pair ? pair->d2 : 0);
+  if (pair) {
+    a.d2 = pair->d2;
+    a.std2 = pair->standardise != 0;
+    a.stride2 = pair->stride2;
+    a.x2 = pair->x2;
+  }
   a.n_rows = n_rows;
   a.n_plcy = f->n_plcy;
   a.perm = perm;

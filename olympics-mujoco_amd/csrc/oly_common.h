@@ -103,6 +103,11 @@ struct oly_ctx {
 
 // K7's finishing step over ctx->stats_ws[0 .. 2*nblocks) -> (n, sum, sumsq); used by K6's fused statistics
 int oly_stats_finish(oly_ctx* ctx, int nblocks, int64_t n, double* stats3_out, oly_stream stream);
+// K18's statistics launches: the Standardizer's running (count, sum, sumsq) [3,D] over the masked columns of x [B,Dx]
+// (accumulate != 0: added), then copied to copy_out [3,D] when given; uses ctx->stats_ws.  Shared with K12's paired reward
+// step.  Fixed summation order, no atomics.
+int oly_masked_col_stats(oly_ctx* ctx, long B, int Dx, int D, const float* x, const int32_t* mask, double* colstats,
+                         int accumulate, double* copy_out, oly_stream stream);
 // oly_a3_step over the host batcher's compact staging (compact_base: qpos = [N,4] base quaternion, qvel = [N,3])
 int oly_a3_step_strided(oly_ctx* ctx, int N, const oly_a3_inputs* in, const oly_a3_state* st, void* obs, float* rew6,
                         float* reward, uint8_t* done, int out_flags, int compact_base, oly_stream stream);

@@ -173,6 +173,12 @@ class GailDiscFit(C.Structure):
                 ("bce_out", vp), ("ent_out", vp)]
 
 
+class DiscPair(C.Structure):
+    """oly_disc_pair: the second part (next states or actions) of a paired discriminator input."""
+    _fields_ = [("x2", vp), ("mask2", vp), ("stride2", C.c_int32), ("d2", C.c_int32), ("standardise", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 OLY_TRPO_ACCEPT_OR, OLY_TRPO_ACCEPT_AND, OLY_TRPO_SCALARS = 0, 1, 8
 
 
@@ -279,6 +285,16 @@ SIGNATURES = {
     "oly_gail_reward_step": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [vp] * 5),
     "oly_gail_disc_fit_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "oly_gail_disc_fit_epoch": (C.c_int, [vp, C.POINTER(GailDiscFit), vp, C.c_int, C.c_int, vp]),
+    "oly_disc_forward_pair": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.POINTER(DiscPair)] + [vp] * 9),
+    "oly_disc_reward_step_pair": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.POINTER(DiscPair), vp, vp, C.c_int]
+                                  + [vp] * 8),
+    "oly_disc_fit_pair_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "oly_disc_fit_epoch_pair": (C.c_int, [vp, C.POINTER(DiscFit), C.POINTER(DiscPair), vp, C.c_int, C.c_int, vp]),
+    "oly_gail_disc_forward_pair": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.POINTER(DiscPair)] + [vp] * 6),
+    "oly_gail_reward_step_pair": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.POINTER(DiscPair), vp, vp, C.c_int]
+                                  + [vp] * 5),
+    "oly_gail_disc_fit_pair_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "oly_gail_disc_fit_epoch_pair": (C.c_int, [vp, C.POINTER(GailDiscFit), C.POINTER(DiscPair), vp, C.c_int, C.c_int, vp]),
     "oly_trpo_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),

@@ -747,6 +747,147 @@ class Engine:
         self.ctx.call("oly_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
         return loss_out
 
+    # ---- K12 / K15 on a paired input: (s, s') with use_next_states, (s, a) with actions (networks.py:258-278)
+    def _disc_packed_floats(self, D):
+        from ._ffi import lib
+        cache = self.__dict__.setdefault("_disc_sizes", {})
+        if D not in cache:
+            cache[D] = int(lib().oly_disc_packed_floats(D, 256, 128, 128))
+        return cache[D]
+
+    def _disc_outputs(self, name, B, want, out):
+        f32, dv = torch.float32, self.device
+        shapes = dict(reward=(B,), logits=(B,), mu=(B, 128), logvar=(B, 128))
+        out = dict(out or {})
+        if not want:
+            raise OlyError(f"{name}: no output requested")
+        for k in want:
+            if k not in shapes:
+                raise OlyError(f"{name}: unknown output {k!r}")
+            out[k] = _req(out.get(k) if out.get(k) is not None else self._new(shapes[k], f32), k, shapes[k], f32, dv)
+        return out, (lambda k: ptr(out[k]) if k in want else None)
+
+    def disc_forward_pair(self, x, x2, packed, standardise, mask=None, mask2=None, stats_a=None, stats_b=None, eps=None,
+                          want=("reward",), out=None):
+        """oly_disc_forward_pair: disc_forward on [ standardise(x[:, mask]) | second ], second = standardise(x2[:, mask2])
+        with stats_b (standardise: next states) or x2[:, mask2] raw (actions).  stats_a / stats_b [3,Ds] f64 running sums,
+        or both None (nothing is standardised)."""
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), f32, dv)
+        Ds = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
+        pair, d2 = self._disc_pair("disc_forward_pair", x2, mask2, standardise, B, Ds)
+        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=True)
+        _req(stats_b, "stats_b", (3, Ds), f64, dv, optional=True)
+        if standardise and (stats_a is None) != (stats_b is None):
+            raise OlyError("disc_forward_pair: give stats_a and stats_b together")
+        _req(packed, "packed", (self._disc_packed_floats(Ds + d2),), f32, dv)
+        _req(eps, "eps", (B, 128), f32, dv, optional=True)
+        out, g = self._disc_outputs("disc_forward_pair", B, want, out)
+        self.ctx.call("oly_disc_forward_pair", C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(stats_a),
+                      ptr(stats_b), ptr(packed), ptr(eps), g("reward"), g("logits"), g("mu"), g("logvar"), self._s())
+        return out
+
+    def disc_reward_step_pair(self, x, x2, packed, colstats, stats_a, accumulate, standardise, mask=None, mask2=None,
+                              eps=None, want=("reward",), out=None, weights=None):
+        """oly_disc_reward_step_pair: the Standardizer's update with x's masked rows (colstats [3,Ds]; that result kept in
+        stats_a [3,Ds]), for next states its second update with x2's masked rows, then the paired forward on both, one C
+        call without a host synchronisation.  accumulate=None: validate now and return `launch(accumulate)`."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), f32, dv)
+        Ds = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
+        pair, d2 = self._disc_pair("disc_reward_step_pair", x2, mask2, standardise, B, Ds)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=not standardise)
+        D = Ds + d2
+        _req(packed, "packed", (self._disc_packed_floats(D),), f32, dv)
+        _req(eps, "eps", (B, 128), f32, dv, optional=True)
+        wp = None
+        if weights is not None:
+            shapes_w = ((256, D), (256,), (128, 256), (128,), (128, 128), (128,), (128, 128), (128,), (1, 128), (1,))
+            if len(weights) != 10:
+                raise OlyError("disc_reward_step_pair: weights = the ten tensors of disc_pack")
+            for i, (t, sh) in enumerate(zip(weights, shapes_w)):
+                _req(t, f"weights[{i}]", sh, f32, dv)
+            wp = (C.c_void_p * 10)(*[t.data_ptr() for t in weights])
+        out, g = self._disc_outputs("disc_reward_step_pair", B, want, out)
+        head = (C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(colstats), ptr(stats_a))
+        tail = (wp, ptr(packed), ptr(eps), g("reward"), g("logits"), g("mu"), g("logvar"))
+        if accumulate is None:
+            from ._ffi import check
+            fn, h = lib().oly_disc_reward_step_pair, self.ctx.handle
+            keep = (x, x2, mask, mask2, colstats, stats_a, packed, eps, weights, pair, out)
+
+            def launch(acc):
+                rc = fn(h, *head, 1 if acc else 0, *tail, self._s())
+                if rc:
+                    check(h, rc, "oly_disc_reward_step_pair")
+                return keep[-1]
+            return launch
+        self.ctx.call("oly_disc_reward_step_pair", *head, int(bool(accumulate)), *tail, self._s())
+        return out
+
+    def disc_fit_pair_ws(self, batch, ds, d2, standardise):
+        """A workspace for disc_fit_epoch_pair with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_disc_fit_pair_ws_floats(int(batch), int(ds), int(d2), int(bool(standardise))))
+        if n < 0:
+            raise OlyError(f"disc_fit_pair: unsupported batch={batch}, {ds} + {d2} columns (0 < batch <= 4096, 0 < D2, "
+                           "Ds + D2 <= 64, next states as wide as the states)")
+        return self._new((n,), torch.float32)
+
+    def disc_fit_epoch_pair(self, x, x2, standardise, n_plcy, eps, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed,
+                            beta, ws, step, lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
+                            info_constraint=0.1, lr_beta=1e-5, targets=None, loss_out=None, bce_out=None, kl_out=None,
+                            beta_out=None):
+        """oly_disc_fit_epoch_pair: disc_fit_epoch on the paired rows x [n,Ds] | x2 [n,D2] (both masked and concatenated,
+        policy rows first); colstats [3,Ds]; param / moments for in = Ds + D2."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [n,Ds] tensor")
+        n, Ds = (int(v) for v in x.shape)
+        _req(x, "x", (n, Ds), f32, dv)
+        pair, d2 = self._disc_pair("disc_fit_epoch_pair", x2, None, standardise, n, Ds)
+        batch, in_dim = int(batch), Ds + d2
+        nws = int(lib().oly_disc_fit_pair_ws_floats(batch, Ds, d2, int(bool(standardise))))
+        if nws < 0:
+            raise OlyError(f"disc_fit_epoch_pair: unsupported batch={batch} (0 < batch <= 4096)")
+        if not 0 <= int(n_plcy) <= n:
+            raise OlyError(f"disc_fit_epoch_pair: n_plcy={n_plcy} outside [0, {n}]")
+        nb = (n + batch - 1) // batch
+        n_par = 256 * in_dim + 256 + 128 * 256 + 128 + 2 * (128 * 128 + 128) + 128 + 1
+        _req(eps, "eps", (n, 128), f32, dv)
+        _req(perm, "perm", (n,), torch.int32, dv)
+        _req(targets, "targets", (n,), f32, dv, optional=True)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (self._disc_packed_floats(in_dim),), f32, dv)
+        _req(beta, "beta", (1,), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
+        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
+        _req(kl_out, "kl_out", (nb,), f64, dv, optional=True)
+        _req(beta_out, "beta_out", (nb,), f32, dv, optional=True)
+        f = _abi.DiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
+                         beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
+                         info_constraint=float(info_constraint), lr_beta=float(lr_beta), x=x.data_ptr(),
+                         targets=ptr(targets), eps=eps.data_ptr(), colstats=colstats.data_ptr(), param=param.data_ptr(),
+                         exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), packed=packed.data_ptr(),
+                         beta=beta.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
+                         bce_out=ptr(bce_out), kl_out=ptr(kl_out), beta_out=ptr(beta_out))
+        self.ctx.call("oly_disc_fit_epoch_pair", C.byref(f), C.byref(pair), ptr(perm), n, batch, self._s())
+        return loss_out
+
     # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
     def _gail_packed_floats(self, D):
         from ._ffi import lib
@@ -864,6 +1005,126 @@ class Engine:
                              packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
                              bce_out=ptr(bce_out), ent_out=ptr(ent_out))
         self.ctx.call("oly_gail_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
+        return loss_out
+
+    # ---- K18 on a paired input: (s, s') with use_next_states, (s, a) with actions (networks.py:216-234)
+    def _disc_pair(self, name, x2, mask2, standardise, rows, Ds):
+        """The oly_disc_pair block of x2 [rows, W2] f32 (mask2 [d2] int32 or None) -> (block, d2).  Refused: an empty
+        second part, Ds + d2 > 64, next states of another width than the states."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(x2, torch.Tensor) or x2.dim() != 2:
+            raise OlyError(f"{name}: x2: expected a [rows,W2] tensor")
+        W2 = int(x2.shape[1])
+        _req(x2, "x2", (rows, W2), f32, dv)
+        d2 = W2 if mask2 is None else int(mask2.shape[0])
+        _req(mask2, "mask2", (d2,), torch.int32, dv, optional=True)
+        if d2 <= 0:
+            raise OlyError(f"{name}: the second part has no column (D2 == 0)")
+        if Ds + d2 > 64:
+            raise OlyError(f"{name}: the paired input is {Ds} + {d2} columns wide, the kernels take at most 64")
+        if standardise and d2 != Ds:
+            raise OlyError(f"{name}: next states have {d2} masked columns, the states {Ds}")
+        return _abi.DiscPair(x2=x2.data_ptr(), mask2=ptr(mask2), stride2=W2, d2=d2, standardise=int(bool(standardise))), d2
+
+    def gail_disc_forward_pair(self, x, x2, packed, standardise, mask=None, mask2=None, stats_a=None, stats_b=None,
+                               want=("reward",), out=None):
+        """oly_gail_disc_forward_pair: gail_disc_forward on [ standardise(x[:, mask]) | second ], second =
+        standardise(x2[:, mask2]) with stats_b (standardise: next states) or x2[:, mask2] raw (actions).  stats_a /
+        stats_b [3,Ds] f64 running sums, or both None (nothing is standardised)."""
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), f32, dv)
+        Ds = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
+        pair, d2 = self._disc_pair("gail_disc_forward_pair", x2, mask2, standardise, B, Ds)
+        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=True)
+        _req(stats_b, "stats_b", (3, Ds), f64, dv, optional=True)
+        if standardise and (stats_a is None) != (stats_b is None):
+            raise OlyError("gail_disc_forward_pair: give stats_a and stats_b together")
+        _req(packed, "packed", (self._gail_packed_floats(Ds + d2),), f32, dv)
+        out, g = self._gail_outputs("gail_disc_forward_pair", B, want, out)
+        self.ctx.call("oly_gail_disc_forward_pair", C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(stats_a),
+                      ptr(stats_b), ptr(packed), g("reward"), g("logits"), self._s())
+        return out
+
+    def gail_reward_step_pair(self, x, x2, packed, colstats, stats_a, accumulate, standardise, mask=None, mask2=None,
+                              want=("reward",), out=None, weights=None):
+        """oly_gail_reward_step_pair: the Standardizer's update with x's masked rows (colstats [3,Ds]; that result kept in
+        stats_a [3,Ds]), for next states its second update with x2's masked rows, then the paired forward on both, one C
+        call without a host synchronisation."""
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), f32, dv)
+        Ds = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
+        pair, d2 = self._disc_pair("gail_reward_step_pair", x2, mask2, standardise, B, Ds)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=not standardise)
+        D = Ds + d2
+        _req(packed, "packed", (self._gail_packed_floats(D),), f32, dv)
+        wp = None
+        if weights is not None:
+            shapes_w = ((512, D), (512,), (256, 512), (256,), (1, 256), (1,))
+            if len(weights) != 6:
+                raise OlyError("gail_reward_step_pair: weights = the six tensors of ilmlp_pack")
+            for i, (t, sh) in enumerate(zip(weights, shapes_w)):
+                _req(t, f"weights[{i}]", sh, f32, dv)
+            wp = (C.c_void_p * 6)(*[t.data_ptr() for t in weights])
+        out, g = self._gail_outputs("gail_reward_step_pair", B, want, out)
+        self.ctx.call("oly_gail_reward_step_pair", C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(colstats),
+                      ptr(stats_a), int(bool(accumulate)), wp, ptr(packed), g("reward"), g("logits"), self._s())
+        return out
+
+    def gail_disc_fit_pair_ws(self, batch, ds, d2, standardise):
+        """A workspace for gail_disc_fit_epoch_pair with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_gail_disc_fit_pair_ws_floats(int(batch), int(ds), int(d2), int(bool(standardise))))
+        if n < 0:
+            raise OlyError(f"gail_disc_fit_pair: unsupported batch={batch}, {ds} + {d2} columns (0 < batch <= 4096, "
+                           "0 < D2, Ds + D2 <= 64, next states as wide as the states)")
+        return self._new((n,), torch.float32)
+
+    def gail_disc_fit_epoch_pair(self, x, x2, standardise, n_plcy, perm, batch, colstats, param, exp_avg, exp_avg_sq,
+                                 packed, ws, step, lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
+                                 entcoeff=1e-3, targets=None, loss_out=None, bce_out=None, ent_out=None):
+        """oly_gail_disc_fit_epoch_pair: gail_disc_fit_epoch on the paired rows x [n,Ds] | x2 [n,D2] (both masked and
+        concatenated, policy rows first); colstats [3,Ds]; param / moments for in = Ds + D2."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [n,Ds] tensor")
+        n, Ds = (int(v) for v in x.shape)
+        _req(x, "x", (n, Ds), f32, dv)
+        pair, d2 = self._disc_pair("gail_disc_fit_epoch_pair", x2, None, standardise, n, Ds)
+        batch, in_dim = int(batch), Ds + d2
+        nws = int(lib().oly_gail_disc_fit_pair_ws_floats(batch, Ds, d2, int(bool(standardise))))
+        if nws < 0:
+            raise OlyError(f"gail_disc_fit_epoch_pair: unsupported batch={batch} (0 < batch <= 4096)")
+        if not 0 <= int(n_plcy) <= n:
+            raise OlyError(f"gail_disc_fit_epoch_pair: n_plcy={n_plcy} outside [0, {n}]")
+        nb = (n + batch - 1) // batch
+        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 256 + 1
+        _req(perm, "perm", (n,), torch.int32, dv)
+        _req(targets, "targets", (n,), f32, dv, optional=True)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (self._gail_packed_floats(in_dim),), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
+        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
+        _req(ent_out, "ent_out", (nb,), f64, dv, optional=True)
+        f = _abi.GailDiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
+                             beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
+                             entcoeff=float(entcoeff), x=x.data_ptr(), targets=ptr(targets), colstats=colstats.data_ptr(),
+                             param=param.data_ptr(), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(),
+                             packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
+                             bce_out=ptr(bce_out), ent_out=ptr(ent_out))
+        self.ctx.call("oly_gail_disc_fit_epoch_pair", C.byref(f), C.byref(pair), ptr(perm), n, batch, self._s())
         return loss_out
 
     # -------------------------------------------------------------- K6

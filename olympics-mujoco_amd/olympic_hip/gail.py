@@ -78,11 +78,73 @@ class VariationalDiscriminator(nn.Module):
         return self.mu_out(h), self.logvar_out(h)
 
 
-class DiscriminatorReward:
-    """make_discrim_reward for a batch of observations on the device."""
+class PairedInput:
+    """What DiscriminatorReward and GAILDiscriminatorReward share when built with a `pair`: the widths and masks of
+    [ s[:, state_mask] | second ] and the checks of the two tensors."""
 
-    def __init__(self, engine, net, state_mask=None, standardizer=None):
+    def _init_pair(self, dim, state_mask, act_mask, standardizer):
+        """The widths and masks of a paired input: Ds state columns, D2 of the second part, Ds + D2 = the network's."""
+        from ._ffi import OlyError
+        self.mask, self.mask2, self._mask_max, self._mask2_max = pair_masks(
+            type(self).__name__, self.pair, dim, state_mask, act_mask, self.eng.device)
+        self.ds = int(self.mask.numel()) if self.mask is not None else (dim // 2 if self.pair == "next_state" else
+                                                                        dim - int(self.mask2.numel()))
+        self.d2 = dim - self.ds
+        self.stand = standardizer or DeviceStandardizer(self.eng, self.ds)
+        if not isinstance(self.stand, DeviceStandardizer):
+            raise OlyError(f"{type(self).__name__}: pair={self.pair!r} takes a DeviceStandardizer (its running sums are "
+                           f"updated inside the reward's call), not {type(self.stand).__name__}")
+        if tuple(self.stand.colstats.shape) != (3, self.ds):
+            raise OlyError(f"{type(self).__name__}: the standardizer has {self.stand.colstats.shape[1]} columns, the "
+                           f"states {self.ds}")
+        self._stats_a = torch.zeros((3, self.ds), dtype=torch.float64, device=self.eng.device)   # S1 of a forward
+        self._packed = None
+
+    def _check_pair(self, x, x2):
+        from ._ffi import OlyError
+        self._check_first(x)
+        if x2 is None:
+            raise OlyError(f"{type(self).__name__}: pair={self.pair!r} needs the second tensor (x2)")
+        if x2.dim() != 2 or int(x2.shape[0]) != int(x.shape[0]):
+            raise OlyError(f"{type(self).__name__}: x2 is [B, columns] with x's {x.shape[0]} rows")
+        if self.mask2 is None and int(x2.shape[1]) != self.d2:
+            raise OlyError(f"{type(self).__name__}: x2 has {x2.shape[1]} columns, the second part {self.d2}")
+        if self.mask2 is not None and int(x2.shape[1]) <= self._mask2_max:
+            raise OlyError(f"{type(self).__name__}: x2 has {x2.shape[1]} columns, its mask reads column {self._mask2_max}")
+
+    def _check_first(self, x):
+        from ._ffi import OlyError
+        if x.dim() != 2:
+            raise OlyError(f"{type(self).__name__}: x is [B, obs]")
+        if self.mask is None and int(x.shape[1]) != self.ds:
+            raise OlyError(f"{type(self).__name__}: {x.shape[1]} columns, the states' part takes {self.ds}")
+        if self.mask is not None and int(x.shape[1]) <= self._mask_max:
+            raise OlyError(f"{type(self).__name__}: {x.shape[1]} columns, the state mask reads column {self._mask_max}")
+
+
+class DiscriminatorReward(PairedInput):
+    """make_discrim_reward for a batch of observations on the device.
+
+    pair: what the discriminator looks at besides the states (VariationalNet.forward, networks.py:258-278;
+    prepare_discrim_inputs, gail_TRPO.py:297-313), as GAILDiscriminatorReward documents it: None (states only),
+    "next_state" ([standardise(s) | standardise(s')], two Standardizer updates per forward) or "action"
+    ([standardise(s) | a[:, act_mask]]).  forward / prepared / logits / __call__ then take the second tensor as x2; the
+    paired path is the fused network's (K12) only."""
+
+    def __init__(self, engine, net, state_mask=None, standardizer=None, pair=None, act_mask=None):
         self.eng, self.net = engine, net
+        self.pair = pair
+        if pair is not None:
+            from ._ffi import OlyError
+            self._packed, self._packed_ver = None, None
+            if not self.fused:
+                raise OlyError("DiscriminatorReward: a paired input needs the fused network "
+                               "in <= 64 -> 256 -> 128 -> (mu, logvar) 128 -> 1")
+            self._init_pair(int(net.encoder[0].in_features), state_mask, act_mask, standardizer)
+            return
+        if act_mask is not None and np.asarray(act_mask).size:
+            from ._ffi import OlyError
+            raise OlyError("DiscriminatorReward: an act_mask needs pair='action'")
         self.mask = None if state_mask is None else torch.as_tensor(np.asarray(state_mask, dtype=np.int32),
                                                                    device=engine.device)
         dim = net.encoder[0].in_features
@@ -127,9 +189,28 @@ class DiscriminatorReward:
         self.stand.update_mean_std(x if whole else x[:, self.mask.long()].contiguous())
         return None if whole else self.mask
 
+    def _pair_args(self, x, x2):
+        self._check_pair(x, x2)
+        ps = [p.detach() for p in self._params()]
+        direct = all(p.dtype == torch.float32 and p.is_contiguous() for p in ps)
+        if self._packed is None or not direct or getattr(self, "cache_packed", False):
+            packed, ps = self.packed(), None
+        else:
+            packed = self._packed
+        return x.to(torch.float32).contiguous(), x2.to(torch.float32).contiguous(), packed, ps
+
     @torch.no_grad()
-    def forward(self, x, eps, want=("reward",), out=None):
-        """Statistics update + oly_disc_forward: any of reward / logits / mu / logvar for x [B,Dx]."""
+    def forward(self, x, eps, want=("reward",), out=None, x2=None):
+        """Statistics update + oly_disc_forward: any of reward / logits / mu / logvar for x [B,Dx] (and the second tensor
+        x2 [B, obs or act] of a paired reward: oly_disc_reward_step_pair, the masks applied inside the kernels)."""
+        if self.pair is not None:
+            x, x2, packed, ps = self._pair_args(x, x2)
+            st = self.stand
+            o = self.eng.disc_reward_step_pair(x, x2, packed, st.colstats, self._stats_a, not st._fresh,
+                                               self.pair == "next_state", mask=self.mask, mask2=self.mask2, eps=eps,
+                                               want=want, out=out, weights=ps)
+            st._fresh = False
+            return o
         whole = self.mask is None or (self._identity_mask and x.shape[1] == self.mask.numel())
         if whole and isinstance(self.stand, DeviceStandardizer):
             # statistics update + forward issued by ONE C call (three launches): from Python the separate calls are
@@ -148,10 +229,22 @@ class DiscriminatorReward:
         return self.eng.disc_forward(x, self.packed(), mask=mask, colstats=self.stand.colstats, eps=eps, want=want,
                                      out=out)
 
-    def prepared(self, x, eps, want=("reward",), out=None):
+    def prepared(self, x, eps, want=("reward",), out=None, x2=None):
         """`step()` = forward(x, eps, want, out) on these same tensors with every argument validated once: the loop a
         reward evaluation over a fixed rollout block runs (whole rows, fused network).  The weights are re-packed from
         the live parameters inside every call."""
+        if self.pair is not None:
+            x, x2, packed, ps = self._pair_args(x, x2)
+            st = self.stand
+            launch = self.eng.disc_reward_step_pair(x, x2, packed, st.colstats, self._stats_a, None,
+                                                    self.pair == "next_state", mask=self.mask, mask2=self.mask2, eps=eps,
+                                                    want=want, out=out, weights=ps)
+
+            def pair_step():
+                o = launch(not st._fresh)
+                st._fresh = False
+                return o
+            return pair_step
         whole = self.mask is None or (self._identity_mask and x.shape[1] == self.mask.numel())
         ps = [p.detach() for p in self._params()]
         if not (whole and self.fused and isinstance(self.stand, DeviceStandardizer)
@@ -178,17 +271,31 @@ class DiscriminatorReward:
         return self.net.decoder(z).reshape(-1).contiguous(), mu, logvar
 
     @torch.no_grad()
-    def logits(self, x, eps):
+    def logits(self, x, eps, x2=None):
         if not self.fused:
             return self.logits_unfused(x, eps)
-        o = self.forward(x, eps, want=("logits", "mu", "logvar"))
+        o = self.forward(x, eps, want=("logits", "mu", "logvar"), x2=x2)
         return o["logits"], o["mu"], o["logvar"]
 
     @torch.no_grad()
-    def __call__(self, x, eps=None, generator=None):
+    def predict(self, x, eps=None, want=("logits",), out=None, x2=None):
+        """The paired forward on the current statistics, without updating them."""
+        from ._ffi import OlyError
+        if self.pair is None:
+            raise OlyError("DiscriminatorReward.predict serves a paired reward; states only: eng.disc_forward")
+        self._check_pair(x, x2)
+        cs = self.stand.colstats
+        return self.eng.disc_forward_pair(x.to(torch.float32).contiguous(), x2.to(torch.float32).contiguous(),
+                                          self.packed(), self.pair == "next_state", mask=self.mask, mask2=self.mask2,
+                                          stats_a=cs, stats_b=cs, eps=eps, want=want, out=out)
+
+    @torch.no_grad()
+    def __call__(self, x, eps=None, generator=None, x2=None):
         if eps is None:
             eps = torch.randn((x.shape[0], self.net.mu_out.out_features), dtype=torch.float32,
                               device=x.device, generator=generator)
+        if self.pair is not None:
+            return self.forward(x, eps, x2=x2)["reward"]
         if self.fused:
             return self.forward(x, eps)["reward"]
         d, _, _ = self.logits_unfused(x, eps)
@@ -217,16 +324,25 @@ class GAILDiscriminator(nn.Module):
         return self._linears[-1](h)
 
 
-class GAILDiscriminatorReward:
+class GAILDiscriminatorReward(PairedInput):
     """make_discrim_reward (gail_TRPO.py:320-327) for GAIL's discriminator on the device (K18): the Standardizer's
     update with the masked rows, then in -> 512 -> 256 -> 1 (tanh, tanh, identity) and the reward formula in one launch,
     the state mask (prepare_discrim_inputs, :297-313) applied inside the kernel.
 
     net: any module exposing three `_linears` of widths in <= 64 -> 512 -> 256 -> 1 (GAILDiscriminator, the reference's
     DiscriminatorNetwork); others are refused with OlyError.  standardizer: the discriminator's own DeviceStandardizer
-    (the D_standardizer), created when not given."""
+    (the D_standardizer), created when not given.
 
-    def __init__(self, engine, net, state_mask=None, standardizer=None):
+    pair: what the discriminator looks at besides the states (DiscriminatorNetwork.preprocess_inputs, networks.py:216-234;
+    prepare_discrim_inputs, gail_TRPO.py:297-313).  None: states only.  "next_state" (use_next_states=True): the input
+    is [standardise(s[:, state_mask]) | standardise(s'[:, state_mask])], the network takes 2 Ds columns and the
+    Standardizer is updated twice per forward, with the states and then with the next states, so the two halves of a row
+    are standardised with different statistics and the count rises by 2 B.  "action" (disc_only_states=False): the input
+    is [standardise(s[:, state_mask]) | a[:, act_mask]], the actions raw.  The Standardizer has Ds columns in every mode.
+    forward / predict / __call__ then take the second tensor as x2.  Next states together with an act_mask (the
+    reference's ValueError, gail_TRPO.py:195-196,308-309), an empty second part and Ds + D2 > 64 are refused."""
+
+    def __init__(self, engine, net, state_mask=None, standardizer=None, pair=None, act_mask=None):
         from ._ffi import OlyError
         lins = list(getattr(net, "_linears", ()))
         if len(lins) != 3 or not all(isinstance(l, nn.Linear) for l in lins):
@@ -236,6 +352,12 @@ class GAILDiscriminatorReward:
                                  int(lins[2].in_features), int(lins[2].out_features)) != (512, 512, 256, 256, 1):
             raise OlyError("GAILDiscriminatorReward: supported network is in <= 64 -> 512 -> 256 -> 1")
         self.eng, self.net, self.lins, self.in_dim = engine, net, lins, dim
+        self.pair = pair
+        if pair is not None:
+            self._init_pair(dim, state_mask, act_mask, standardizer)
+            return
+        if act_mask is not None and np.asarray(act_mask).size:
+            raise OlyError("GAILDiscriminatorReward: an act_mask needs pair='action'")
         self.mask = None
         if state_mask is not None:
             m = np.asarray(state_mask, dtype=np.int64).reshape(-1)
@@ -269,32 +391,91 @@ class GAILDiscriminatorReward:
             raise OlyError(f"GAILDiscriminatorReward: {x.shape[1]} columns, the state mask reads column {self._mask_max}")
 
     @torch.no_grad()
-    def forward(self, x, want=("reward",), out=None):
-        """Statistics update with the masked rows + forward, one C call: any of reward / logits for x [B,obs]."""
-        self._check(x)
+    def forward(self, x, want=("reward",), out=None, x2=None):
+        """Statistics update with the masked rows + forward, one C call: any of reward / logits for x [B,obs] (and the
+        second tensor x2 [B, obs or act] of a paired reward)."""
+        if self.pair is not None:
+            self._check_pair(x, x2)
+        else:
+            self._check(x)
         st = self.stand
         ps = [p.detach() for p in self._params()]
         if self._packed is None or not all(p.dtype == torch.float32 and p.is_contiguous() for p in ps):
             packed, ps = self.packed(), None                        # separate pack call
         else:
             packed = self._packed                                  # re-packed from the live parameters inside the call
+        if self.pair is not None:
+            o = self.eng.gail_reward_step_pair(x.to(torch.float32).contiguous(), x2.to(torch.float32).contiguous(), packed,
+                                               st.colstats, self._stats_a, not st._fresh, self.pair == "next_state",
+                                               mask=self.mask, mask2=self.mask2, want=want, out=out, weights=ps)
+            st._fresh = False
+            return o
         o = self.eng.gail_reward_step(x.to(torch.float32).contiguous(), packed, st.colstats, not st._fresh,
                                       mask=self.mask, want=want, out=out, weights=ps)
         st._fresh = False
         return o
 
     @torch.no_grad()
-    def predict(self, x, want=("logits",), out=None):
+    def predict(self, x, want=("logits",), out=None, x2=None):
         """The forward on the current statistics, without updating them."""
+        if self.pair is not None:
+            self._check_pair(x, x2)
+            cs = self.stand.colstats
+            return self.eng.gail_disc_forward_pair(x.to(torch.float32).contiguous(), x2.to(torch.float32).contiguous(),
+                                                   self.packed(), self.pair == "next_state", mask=self.mask,
+                                                   mask2=self.mask2, stats_a=cs, stats_b=cs, want=want, out=out)
         self._check(x)
         return self.eng.gail_disc_forward(x.to(torch.float32).contiguous(), self.packed(), mask=self.mask,
                                           colstats=self.stand.colstats, want=want, out=out)
 
     @torch.no_grad()
-    def __call__(self, x, eps=None, generator=None):
+    def __call__(self, x, eps=None, generator=None, x2=None):
         """The reward [B].  eps / generator are accepted and ignored (GAIL's discriminator draws no noise), so the
         agent's sequence can call either discriminator."""
-        return self.forward(x)["reward"]
+        return self.forward(x, x2=x2)["reward"]
+
+
+PAIR_MODES = (None, "next_state", "action")
+
+
+def pair_masks(who, pair, dim, state_mask, act_mask, device):
+    """(mask, mask2, max(mask), max(mask2)) of a paired discriminator input of `dim` columns, each mask an int32 device
+    tensor or None (identity).  pair "next_state": both parts read state_mask, dim = 2 Ds; an act_mask with columns is
+    the reference's refused three-part combination.  pair "action": the second part reads act_mask; one of the two
+    masks may be left out (its part then takes the source's columns as they are, dim - the other's width of them)."""
+    from ._ffi import OlyError
+    if pair not in PAIR_MODES or pair is None:
+        raise OlyError(f"{who}: pair is None, 'next_state' or 'action' (got {pair!r})")
+
+    def arr(m, name):
+        m = np.asarray(m, dtype=np.int64).reshape(-1)
+        if m.size and m.min() < 0:
+            raise OlyError(f"{who}: negative column in the {name}")
+        return m
+    sm = None if state_mask is None else arr(state_mask, "state mask")
+    am = None if act_mask is None else arr(act_mask, "act_mask")
+    if pair == "next_state":
+        if am is not None and am.size:
+            raise OlyError(f"{who}: states, actions and next states together are not supported (the reference raises "
+                           "ValueError, gail_TRPO.py:195-196,308-309)")
+        if dim % 2 or (sm is not None and 2 * sm.size != dim) or dim < 2:
+            raise OlyError(f"{who}: with next states the network takes twice the masked state columns, not {dim}")
+        am = sm
+    else:
+        ds = dim - am.size if am is not None else (sm.size if sm is not None else -1)
+        if am is None and sm is None:
+            raise OlyError(f"{who}: pair='action' needs a state mask or an act_mask to split the {dim} columns")
+        if (am is not None and am.size == 0) or ds >= dim:
+            raise OlyError(f"{who}: the second part has no column (D2 == 0)")
+        if ds <= 0 or (sm is not None and sm.size != ds):
+            raise OlyError(f"{who}: the masks select {-1 if sm is None else sm.size} + {-1 if am is None else am.size} "
+                           f"columns, the network takes {dim}")
+    if dim > 64:
+        raise OlyError(f"{who}: the paired input is {dim} columns wide, the kernels take at most 64")
+
+    def dev(m):
+        return None if m is None else torch.as_tensor(m.astype(np.int32), device=device)
+    return dev(sm), dev(am), (None if sm is None else int(sm.max())), (None if am is None else int(am.max()))
 
 
 class GAILAdvantage:

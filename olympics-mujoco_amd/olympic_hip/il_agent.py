@@ -140,6 +140,10 @@ class VAILAgent:
         self.critic_fit_params = dict(n_epochs=3, batch_size=256) if critic_fit_params is None else dict(critic_fit_params)
         self.post = GAERollout(engine, gamma=gamma, lam=lam)
         self.iter = int(start_iter)
+        if getattr(disc_reward, "pair", None) is not None and not isinstance(disc_trainer, PairedDemonstrations):
+            raise OlyError(f"{type(self).__name__}: the reward was built with pair={disc_reward.pair!r}, which only the "
+                           "device trainers fit (DeviceDiscriminatorTrainer, DeviceGAILDiscriminatorTrainer), not "
+                           f"{type(disc_trainer).__name__}")
 
     @property
     def standardizer(self):
@@ -156,13 +160,16 @@ class VAILAgent:
         return vals
 
     @torch.no_grad()
-    def _advantage(self, x, xn, r_env, absorbing, last, eps=None, generator=None):
+    def _advantage(self, x, xn, r_env, absorbing, last, eps=None, generator=None, second=None):
         from . import _abi
         from .rollout import RolloutBuffer
         T, N, D = x.shape
         flat = x.reshape(T * N, D)
         if self.frac < 1.0:
-            r_disc = self.disc(flat, eps, generator=generator).reshape(T, N)
+            if second is not None:      # a paired reward: (s, s') or (s, a), make_discrim_reward (gail_TRPO.py:320-325)
+                r_disc = self.disc(flat, eps, generator=generator, x2=second).reshape(T, N)
+            else:
+                r_disc = self.disc(flat, eps, generator=generator).reshape(T, N)
             r = r_env * self.frac + r_disc * (1 - self.frac)
         else:
             r = r_env.clone()
@@ -185,9 +192,11 @@ class VAILAgent:
         flat = x.reshape(T * N, D)
         st = self.standardizer
         st.update_mean_std(flat)
-        r, v_target, adv = self._advantage(x, xn, reward.to(torch.float32).reshape(T, N), absorbing.reshape(T, N),
-                                           last.reshape(T, N), eps=eps, generator=generator)
         obs, act = flat, action.to(torch.float32).reshape(T * N, -1)
+        pair = getattr(self.disc, "pair", None)      # what the discriminator looks at besides the states
+        second = None if pair is None else (xn.reshape(T * N, D) if pair == "next_state" else act.contiguous())
+        r, v_target, adv = self._advantage(x, xn, reward.to(torch.float32).reshape(T, N), absorbing.reshape(T, N),
+                                           last.reshape(T, N), eps=eps, generator=generator, second=second)
         self.policy_step(obs, act, adv.reshape(T * N), self)
         fit = dict(self.critic_fit_params)
         for _ in range(int(fit.get("n_epochs", 3))):
@@ -196,15 +205,73 @@ class VAILAgent:
                                       batch_size=int(fit.get("batch_size", 256)), generator=generator)
         disc_loss, trained = None, False
         if self.iter % self.train_D_n_th_epoch == 0:
-            disc_loss = self.disc_trainer.fit(flat, generator=generator)
+            if second is not None:
+                disc_loss = self.disc_trainer.fit(flat, generator=generator, x2=second)
+            else:
+                disc_loss = self.disc_trainer.fit(flat, generator=generator)
             trained = True
         self.iter += 1
         return dict(reward=r, v_target=v_target, adv=adv, critic_loss=critic_loss, disc_loss=disc_loss,
                     disc_trained=trained)
 
 
-class DeviceDiscriminatorTrainer:
-    """_fit_discriminator (gail_TRPO.py:167-220) for VAIL, states only, on K15.  Per epoch:
+class PairedDemonstrations:
+    """What the two device trainers share when their reward was built with a `pair`: the demonstrations' second array
+    and the draw that selects both parts together."""
+
+    def _init_pair_demo(self, demo):
+        """The demonstrations of a paired fit: an ExpertDataset (next states: its minibatch(idx, want_next=True)) or a
+        dict with the reference's keys, `states` and `next_states` or `actions` (gail_TRPO.py:177-194)."""
+        from .gail import ExpertDataset
+        r, dev = self.r, self.eng.device
+        key = "next_states" if self.pair == "next_state" else "actions"
+        if isinstance(demo, ExpertDataset):
+            if self.pair != "next_state":
+                raise OlyError(f"{type(self).__name__}: an ExpertDataset holds no actions; give a dict with "
+                               "`states` and `actions`")
+            if int(demo.cols.numel()) != r.ds:
+                raise OlyError(f"{type(self).__name__}: the ExpertDataset has {int(demo.cols.numel())} masked "
+                               f"columns, the states' part takes {r.ds}")
+            self.expert = demo
+            return
+        if not isinstance(demo, dict) or "states" not in demo:
+            raise OlyError(f"{type(self).__name__}: pair={self.pair!r} takes an ExpertDataset or a dict with "
+                           f"`states` and `{key}`")
+        if demo.get(key) is None:
+            raise OlyError(f"{type(self).__name__}: the demonstrations lack `{key}` (pair={self.pair!r})")
+
+        def up(a):
+            return a.to(device=dev, dtype=torch.float32) if torch.is_tensor(a) else torch.as_tensor(
+                np.asarray(a), dtype=torch.float32, device=dev)
+        self.demo, self.demo2 = up(demo["states"]), up(demo[key])
+        if self.demo.dim() != 2 or self.demo2.dim() != 2 or self.demo.shape[0] != self.demo2.shape[0]:
+            raise OlyError(f"{type(self).__name__}: `states` and `{key}` are [rows, columns] with the same rows")
+        r._check_pair(self.demo[:1], self.demo2[:1])
+
+    def _pair_demo_rows(self, idx):
+        """(states, second) of the drawn rows, masked: one draw selects both (gail_TRPO.py:178-180, 187-189)."""
+        if self.expert is not None:
+            return self.expert.minibatch(idx, want_next=True)
+        d, d2 = self.demo[idx], self.demo2[idx]
+        return (d if self.r.mask is None else d[:, self.r.mask.long()],
+                d2 if self.r.mask2 is None else d2[:, self.r.mask2.long()])
+
+    def _pair_policy_rows(self, plcy, x2):
+        """The policy's second tensor, checked and masked."""
+        r = self.r
+        if x2 is None:
+            raise OlyError(f"{type(self).__name__}.fit: pair={self.pair!r} needs the policy's second tensor (x2)")
+        plcy2 = x2.reshape(-1, x2.shape[-1]).to(torch.float32)
+        r._check_pair(plcy, plcy2)
+        if r.mask2 is not None:
+            plcy2 = plcy2[:, r.mask2.long()]
+        return plcy2.contiguous()
+
+
+class DeviceDiscriminatorTrainer(PairedDemonstrations):
+    """_fit_discriminator (gail_TRPO.py:167-220) for VAIL on K15: states only, or the paired input of a reward built
+    with pair="next_state" / "action" (then fit takes the policy's second tensor, the demonstrations carry the second
+    array, one draw selects both, and the explicit update of :206 still takes the states only).  Per epoch:
 
         plcy = plcy_obs[:, state_mask] (n rows); demo = the first m = min(n, rows) rows of a shuffle of the
         demonstration states (minibatch_generator, :198-200); concat = [plcy; demo]; targets 0 / 1, or
@@ -219,7 +286,9 @@ class DeviceDiscriminatorTrainer:
     SummaryWriter is attached, are not replayed.
 
     reward: the DiscriminatorReward whose network (VariationalDiscriminator, the K12 shape) and standardizer are
-    fitted; demo: an ExpertDataset (mask folded in) or an array of full observations; loss: a VDBLoss, whose
+    fitted; demo: an ExpertDataset (mask folded in) or an array of full observations (a paired reward: an ExpertDataset,
+    whose minibatch(idx, want_next=True) serves the next states, or a dict with the reference's keys `states` and
+    `next_states` / `actions`); loss: a VDBLoss, whose
     _beta is read at the start of every fit and written back once at its end.  Every fit starts from the module's
     current parameters and writes the stepped ones back in place (the pointers DiscriminatorReward.prepared()
     captured stay valid); the reward's packed stream is left current.  The optimiser's moments and step count
@@ -238,15 +307,22 @@ class DeviceDiscriminatorTrainer:
                            "in <= 64 -> 256 -> 128 -> (mu, logvar) 128 -> 1")
         self.r, self.loss, self.eng = reward, loss, reward.eng
         self.in_dim = int(reward.net.encoder[0].in_features)
-        self._mask_max = None if reward.mask is None else int(reward.mask.max())
         self.batch = int(batch_size)
-        self._ws = self.eng.disc_fit_ws(self.batch, self.in_dim)
+        self.pair = getattr(reward, "pair", None)
         self.lr, self.betas, self.eps, self.wd = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
         dev = self.eng.device
-        self.expert = demo if isinstance(demo, ExpertDataset) else None
-        self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
-                                                                         device=dev)
+        if self.pair is not None:
+            self._mask_max = reward._mask_max
+            self._ws = self.eng.disc_fit_pair_ws(self.batch, reward.ds, reward.d2, self.pair == "next_state")
+            self.demo, self.demo2, self.expert = None, None, None
+            self._init_pair_demo(demo)
+        else:
+            self._mask_max = None if reward.mask is None else int(reward.mask.max())
+            self._ws = self.eng.disc_fit_ws(self.batch, self.in_dim)
+            self.expert = demo if isinstance(demo, ExpertDataset) else None
+            self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
+                                                                             device=dev)
         n_par = sum(int(p.numel()) for p in reward._params())
         self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros_like(self.param)
@@ -257,14 +333,17 @@ class DeviceDiscriminatorTrainer:
     def _demo_rows(self, n, generator):
         rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
         idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
+        if self.pair is not None:
+            return self._pair_demo_rows(idx)
         if self.expert is not None:
             return self.expert.minibatch(idx)
         d = self.demo[idx]
         return d if self.r.mask is None else d[:, self.r.mask.long()]
 
     @torch.no_grad()
-    def fit(self, plcy_obs, generator=None, eps=None):
-        """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations).  eps: the reparameterisation
+    def fit(self, plcy_obs, generator=None, eps=None, x2=None):
+        """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations) and, for a paired reward, the
+        policy's second tensor x2 [n, obs or act] (next states or actions, full width).  eps: the reparameterisation
         noise, [n_epochs, n + m, 128] (or [n + m, 128] for one epoch) in minibatch order, or None (drawn from
         `generator`).  Returns the per-minibatch losses, [n_epochs, n_batches] f64 on the device."""
         r, eng, dev = self.r, self.eng, self.eng.device
@@ -272,13 +351,14 @@ class DeviceDiscriminatorTrainer:
         if self._mask_max is not None and int(plcy.shape[1]) <= self._mask_max:
             raise OlyError(f"DeviceDiscriminatorTrainer.fit: {plcy.shape[1]} columns, the state mask reads column "
                            f"{self._mask_max}")
+        plcy2 = self._pair_policy_rows(plcy, x2) if self.pair is not None else None
         if r.mask is not None:
             plcy = plcy[:, r.mask.long()]
         plcy = plcy.contiguous()
         n = int(plcy.shape[0])
         if n == 0:
             raise OlyError("DeviceDiscriminatorTrainer.fit: no policy rows")
-        if int(plcy.shape[1]) != self.in_dim:
+        if int(plcy.shape[1]) != (self.in_dim if self.pair is None else r.ds):
             raise OlyError(f"DeviceDiscriminatorTrainer.fit: {plcy.shape[1]} masked columns, the network takes {self.in_dim}")
         ps = r._params()
         torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=self.param)
@@ -292,9 +372,13 @@ class DeviceDiscriminatorTrainer:
         losses = None
         for e in range(self.n_epochs):
             demo = self._demo_rows(n, generator)
+            xb = None
+            if self.pair is not None:
+                demo, demo2 = demo
+                xb = torch.cat([plcy2, demo2]).contiguous()
             x = torch.cat([plcy, demo]).contiguous()
             rows = int(x.shape[0])
-            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206
+            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206: states only
             targets = None
             if self.noisy:                                          # :209-211: demo targets drawn first
                 demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
@@ -308,6 +392,14 @@ class DeviceDiscriminatorTrainer:
             nb = (rows + self.batch - 1) // self.batch
             if losses is None:
                 losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
+            if self.pair is not None:
+                eng.disc_fit_epoch_pair(x, xb, self.pair == "next_state", n, noise.to(torch.float32).contiguous(), perm,
+                                        self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq, r._packed,
+                                        self.beta, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
+                                        adam_eps=self.eps, weight_decay=self.wd, info_constraint=self.loss._info_constr,
+                                        lr_beta=self.loss._lr_beta, targets=targets, loss_out=losses[e])
+                self.step += nb
+                continue
             eng.disc_fit_epoch(x, n, noise.to(torch.float32).contiguous(), perm, self.batch, st.colstats, self.param,
                                self.exp_avg, self.exp_avg_sq, r._packed, self.beta, self._ws, self.step, self.lr,
                                beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps, weight_decay=self.wd,
@@ -324,9 +416,9 @@ class DeviceDiscriminatorTrainer:
         return losses
 
 
-class DeviceGAILDiscriminatorTrainer:
-    """_fit_discriminator (gail_TRPO.py:167-220) for GAIL, states only, on K18: DeviceDiscriminatorTrainer's semantics
-    with GAIL's network and loss.  Per epoch:
+class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
+    """_fit_discriminator (gail_TRPO.py:167-220) for GAIL on K18: DeviceDiscriminatorTrainer's semantics with GAIL's
+    network and loss, states only or the paired input of a reward built with pair="next_state" / "action".  Per epoch:
 
         plcy = plcy_obs[:, state_mask] (n rows); demo = the first m = min(n, rows) rows of a shuffle of the
         demonstration states (minibatch_generator, :198-200); concat = [plcy; demo]; targets 0 / 1, or
@@ -340,7 +432,7 @@ class DeviceGAILDiscriminatorTrainer:
     HumanoidMuscle's of confs.yaml (lr_disc 5e-6, d_entr_coef 1e-3) and create_gail_agent's (weight_decay 0, batch 2048).
 
     reward: the GAILDiscriminatorReward whose network and standardizer are fitted; demo: an ExpertDataset (mask folded
-    in) or an array of full observations.  Every fit starts from the module's current parameters and writes the stepped
+    in) or an array of full observations (a paired reward: an ExpertDataset or a dict, as DeviceDiscriminatorTrainer).  Every fit starts from the module's current parameters and writes the stepped
     ones back in place; the reward's packed stream is left current.  The optimiser's moments and step count persist
     across fits."""
 
@@ -353,17 +445,24 @@ class DeviceGAILDiscriminatorTrainer:
         self.r, self.eng = reward, reward.eng
         self.in_dim = reward.in_dim
         self.batch = int(batch_size)
-        self._ws = self.eng.gail_disc_fit_ws(self.batch, self.in_dim)
+        self.pair = getattr(reward, "pair", None)
+        if self.pair is not None:
+            self._ws = self.eng.gail_disc_fit_pair_ws(self.batch, reward.ds, reward.d2, self.pair == "next_state")
+            self.demo, self.demo2, self.expert = None, None, None
+            self._init_pair_demo(demo)
+        else:
+            self._ws = self.eng.gail_disc_fit_ws(self.batch, self.in_dim)
         self.entcoeff, self.lr, self.betas = float(entcoeff), float(lr), (float(betas[0]), float(betas[1]))
         self.eps, self.wd = float(eps), float(weight_decay)
         self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
         dev = self.eng.device
-        self.expert = demo if isinstance(demo, ExpertDataset) else None
-        self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
-                                                                         device=dev)
-        if self.demo is not None and (self.demo.dim() != 2 or int(self.demo.shape[1]) <=
-                                      (reward._mask_max if reward.mask is not None else self.in_dim - 1)):
-            raise OlyError("DeviceGAILDiscriminatorTrainer: the demonstrations are [rows, obs] full observations")
+        if self.pair is None:
+            self.expert = demo if isinstance(demo, ExpertDataset) else None
+            self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
+                                                                             device=dev)
+            if self.demo is not None and (self.demo.dim() != 2 or int(self.demo.shape[1]) <=
+                                          (reward._mask_max if reward.mask is not None else self.in_dim - 1)):
+                raise OlyError("DeviceGAILDiscriminatorTrainer: the demonstrations are [rows, obs] full observations")
         n_par = sum(int(p.numel()) for p in reward._params())
         self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros_like(self.param)
@@ -373,21 +472,28 @@ class DeviceGAILDiscriminatorTrainer:
     def _demo_rows(self, n, generator):
         rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
         idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
+        if self.pair is not None:
+            return self._pair_demo_rows(idx)
         if self.expert is not None:
             return self.expert.minibatch(idx)
         d = self.demo[idx]
         return d if self.r.mask is None else d[:, self.r.mask.long()]
 
     @torch.no_grad()
-    def fit(self, plcy_obs, generator=None):
-        """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations).  Returns the per-minibatch losses,
-        [n_epochs, n_batches] f64 on the device."""
+    def fit(self, plcy_obs, generator=None, x2=None):
+        """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations) and, for a paired reward, the
+        policy's second tensor x2 [n, obs or act] (next states or actions, full width).  Returns the per-minibatch
+        losses, [n_epochs, n_batches] f64 on the device."""
         r, eng, dev = self.r, self.eng, self.eng.device
         plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
         n = int(plcy.shape[0])
         if n == 0:
             raise OlyError("DeviceGAILDiscriminatorTrainer.fit: no policy rows")
-        r._check(plcy)
+        plcy2 = None
+        if self.pair is not None:
+            plcy2 = self._pair_policy_rows(plcy, x2)
+        else:
+            r._check(plcy)
         if r.mask is not None:
             plcy = plcy[:, r.mask.long()]
         plcy = plcy.contiguous()
@@ -402,9 +508,13 @@ class DeviceGAILDiscriminatorTrainer:
         losses = None
         for e in range(self.n_epochs):
             demo = self._demo_rows(n, generator)
+            xb = None
+            if self.pair is not None:
+                demo, demo2 = demo
+                xb = torch.cat([plcy2, demo2]).contiguous()
             x = torch.cat([plcy, demo]).contiguous()
             rows = int(x.shape[0])
-            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206
+            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206: states only
             targets = None
             if self.noisy:                                          # :209-211: demo targets drawn first
                 demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
@@ -414,6 +524,14 @@ class DeviceGAILDiscriminatorTrainer:
             nb = (rows + self.batch - 1) // self.batch
             if losses is None:
                 losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
+            if self.pair is not None:
+                eng.gail_disc_fit_epoch_pair(x, xb, self.pair == "next_state", n, perm, self.batch, st.colstats, self.param,
+                                             self.exp_avg, self.exp_avg_sq, r._packed, self._ws, self.step, self.lr,
+                                             beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps,
+                                             weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
+                                             loss_out=losses[e])
+                self.step += nb
+                continue
             eng.gail_disc_fit_epoch(x, n, perm, self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq,
                                     r._packed, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
                                     adam_eps=self.eps, weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,

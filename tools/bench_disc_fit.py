@@ -6,6 +6,12 @@ reference launcher's size (n = 1000: one minibatch of 2000 rows) and at [100, 40
 on [100, 4096] with and without a discriminator call.  HIP events on the stream; every shape is warmed up first.
 
     python tools/bench_disc_fit.py [--out FILE]
+
+--in-dim D (states only at another width) and --pair next_state | action (the paired input, (s, s') at 32 + 32 or (s, a)
+at 32 + 11, through oly_disc_fit_epoch_pair) measure the epoch call alone, two runs:
+
+    python tools/bench_disc_fit.py --in-dim 64
+    python tools/bench_disc_fit.py --pair next_state
 """
 import argparse
 import json
@@ -50,7 +56,13 @@ def wall(fn, reps, warmup=1):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--epoch-only", action="store_true", help="only the epoch call, two runs")
+    ap.add_argument("--in-dim", type=int, default=IN, help="states-only input width; != 32: only the epoch call")
+    ap.add_argument("--pair", choices=("next_state", "action"), default=None, help="the paired input: (s, s') at 32 + 32 or (s, a) at 32 + 11; only the epoch call is measured")
     args = ap.parse_args()
+    ds, d2 = (32, 32 if args.pair == "next_state" else 11) if args.pair else (args.in_dim, 0)
+    width = ds + d2
+    epoch_only = args.epoch_only or width != IN or args.pair is not None
     from olympic_hip.engine import Engine
     from olympic_hip.gail import DeviceStandardizer, DiscriminatorReward, VariationalDiscriminator, VDBLoss
     from olympic_hip.il_agent import DeviceDiscriminatorTrainer, DeviceILCritic, VAILAgent
@@ -61,8 +73,9 @@ def main():
     # ---- the epoch call: 131 072 rows, 64 minibatches of 2048
     n = 131072
     nb = n // BATCH
-    net = VariationalDiscriminator(in_dim=IN).cuda()
-    x = (torch.randn((n, IN), device="cuda") * 1.3 + 0.2).contiguous()
+    net = VariationalDiscriminator(in_dim=width).cuda()
+    x = (torch.randn((n, ds), device="cuda") * 1.3 + 0.2).contiguous()
+    x2 = (torch.randn((n, d2), device="cuda") * 0.8 + 0.5).contiguous() if args.pair else None
     eps = torch.randn((n, 128), device="cuda")
     perm = torch.randperm(n, device="cuda").to(torch.int32)
     flat = torch.cat([p.detach().reshape(-1) for p in (net.encoder[0].weight, net.encoder[0].bias, net.encoder[1].weight,
@@ -73,13 +86,23 @@ def main():
     packed = eng.disc_pack(*[p.detach().contiguous() for p in DiscriminatorReward(eng, net)._params()])
     beta = torch.full((1,), 0.1, device="cuda")
     cs = eng.col_stats(x)
-    ws = eng.disc_fit_ws(BATCH, IN)
+    ns = args.pair == "next_state"
+    ws = eng.disc_fit_pair_ws(BATCH, ds, d2, ns) if args.pair else eng.disc_fit_ws(BATCH, width)
     step = [0]
 
     def epoch():
-        eng.disc_fit_epoch(x, n // 2, eps, perm, BATCH, cs, flat, m, v, packed, beta, ws, step[0], 5e-5,
-                           info_constraint=0.1, lr_beta=1e-5)
+        if args.pair:
+            eng.disc_fit_epoch_pair(x, x2, ns, n // 2, eps, perm, BATCH, cs, flat, m, v, packed, beta, ws, step[0], 5e-5,
+                                    info_constraint=0.1, lr_beta=1e-5)
+        else:
+            eng.disc_fit_epoch(x, n // 2, eps, perm, BATCH, cs, flat, m, v, packed, beta, ws, step[0], 5e-5,
+                               info_constraint=0.1, lr_beta=1e-5)
         step[0] += nb
+    if epoch_only:
+        runs = [timed(epoch, 5) for _ in range(2)]
+        res.update(in_dim=width, pair=args.pair, fit_us_per_minibatch_2048_runs=[ms * 1e3 / nb for ms in runs])
+        print(json.dumps(res))
+        return
     ms = timed(epoch, 5)
     res["fit_us_per_minibatch_2048"] = ms * 1e3 / nb
     res["fit_tflops"] = FLOP_PER_ROW * n / (ms * 1e-3) / 1e12

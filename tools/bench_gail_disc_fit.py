@@ -7,6 +7,12 @@ on [100, 4096] with and without a discriminator call; the reward forward at 4096
 forward on the same shapes.  HIP events on the stream; every shape is warmed up first.
 
     python tools/bench_gail_disc_fit.py [--out FILE]
+
+--in-dim D (states only at another width) and --pair next_state | action (the paired input, (s, s') at 32 + 32 or (s, a)
+at 32 + 11, through oly_gail_disc_fit_epoch_pair) measure the epoch call alone, two runs:
+
+    python tools/bench_gail_disc_fit.py --in-dim 64
+    python tools/bench_gail_disc_fit.py --pair next_state
 """
 import argparse
 import json
@@ -52,36 +58,48 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--epoch-only", action="store_true", help="only the epoch call (for a kernel trace)")
+    ap.add_argument("--in-dim", type=int, default=IN, help="states-only input width; != 32: only the epoch call")
+    ap.add_argument("--pair", choices=("next_state", "action"), default=None, help="the paired input: (s, s') at 32 + 32 or (s, a) at 32 + 11; only the epoch call is measured")
     args = ap.parse_args()
+    ds, d2 = (32, 32 if args.pair == "next_state" else 11) if args.pair else (args.in_dim, 0)
+    width = ds + d2
+    args.epoch_only = args.epoch_only or width != IN or args.pair is not None
     from olympic_hip.engine import Engine
     from olympic_hip.gail import (DeviceStandardizer, GAILDiscriminator, GAILDiscriminatorReward,
                                   gail_discriminator_loss)
     from olympic_hip.il_agent import DeviceGAILDiscriminatorTrainer, DeviceILCritic, GAILAgent
     eng = Engine(0)
     torch.manual_seed(0)
-    res = {"device": torch.cuda.get_device_name(0), "flop_per_row": FLOP_PER_ROW}
+    flop_per_row = 3 * 2 * (width * 512 + 512 * 256 + 256) - 2 * width * 512
+    res = {"device": torch.cuda.get_device_name(0), "flop_per_row": flop_per_row, "in_dim": width, "pair": args.pair}
 
     # ---- the epoch call: 131 072 rows, 64 minibatches of 2048
     n = 131072
     nb = n // BATCH
-    net = GAILDiscriminator(IN).cuda()
-    x = (torch.randn((n, IN), device="cuda") * 1.3 + 0.2).contiguous()
+    net = GAILDiscriminator(width).cuda()
+    x = (torch.randn((n, ds), device="cuda") * 1.3 + 0.2).contiguous()
+    x2 = (torch.randn((n, d2), device="cuda") * 0.8 + 0.5).contiguous() if args.pair else None
     perm = torch.randperm(n, device="cuda").to(torch.int32)
     ps = [t.detach() for lin in net._linears for t in (lin.weight, lin.bias)]
     flat = torch.cat([p.reshape(-1) for p in ps]).contiguous()
     m, v = torch.zeros_like(flat), torch.zeros_like(flat)
     packed = eng.ilmlp_pack(*[p.contiguous() for p in ps])
     cs = eng.col_stats(x)
-    ws = eng.gail_disc_fit_ws(BATCH, IN)
+    ns = args.pair == "next_state"
+    ws = eng.gail_disc_fit_pair_ws(BATCH, ds, d2, ns) if args.pair else eng.gail_disc_fit_ws(BATCH, width)
     step = [0]
 
     def epoch():
-        eng.gail_disc_fit_epoch(x, n // 2, perm, BATCH, cs, flat, m, v, packed, ws, step[0], 5e-6, entcoeff=1e-3)
+        if args.pair:
+            eng.gail_disc_fit_epoch_pair(x, x2, ns, n // 2, perm, BATCH, cs, flat, m, v, packed, ws, step[0], 5e-6,
+                                         entcoeff=1e-3)
+        else:
+            eng.gail_disc_fit_epoch(x, n // 2, perm, BATCH, cs, flat, m, v, packed, ws, step[0], 5e-6, entcoeff=1e-3)
         step[0] += nb
     runs = [timed(epoch, 5) for _ in range(2)]
     res["fit_us_per_minibatch_2048_runs"] = [ms * 1e3 / nb for ms in runs]
     res["fit_us_per_minibatch_2048"] = max(runs) * 1e3 / nb
-    res["fit_tflops"] = FLOP_PER_ROW * n / (max(runs) * 1e-3) / 1e12
+    res["fit_tflops"] = flop_per_row * n / (max(runs) * 1e-3) / 1e12
     if args.epoch_only:
         print(json.dumps(res))
         return
