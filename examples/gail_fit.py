@@ -7,7 +7,7 @@ max_kl 1e-2, std_0 0.8.  The policy step is the caller's.  By default it is a st
 it was handed, and the policy is a random one on the kinematic stand-in physics.  With --policy device the actions come
 from a DeviceGaussianPolicy (obs -> [512, 256] -> act) and DeviceTRPO (K17) trains it.
 
-    python examples/gail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device]
+    python examples/gail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device] [--log]
                                 [--disc_use_next_states] [--disc_only_states False]
 
 --disc_use_next_states gives the discriminator (state, next state) (64 columns for H1's 32-column kinematic mask),
@@ -25,7 +25,7 @@ from olympic_hip.envs import LocoEnvBase  # noqa: E402
 from olympic_hip.gail import DeviceStandardizer, GAILDiscriminator, GAILDiscriminatorReward  # noqa: E402
 from olympic_hip.il_agent import (DeviceGAILDiscriminatorTrainer, DeviceGaussianPolicy, DeviceILCritic,  # noqa: E402
                                   DeviceTRPO, GAILAgent)
-from vail_fit import paired_inputs  # noqa: E402  (the example beside this one: the two switches mean the same there)
+from vail_fit import PrintingWriter, paired_inputs  # noqa: E402  (the example beside this one: the two switches mean the same there)
 
 
 def policy_step(obs, act, adv, agent):
@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--disc_only_states", type=lambda s: s.lower() in ("1", "true", "yes"), default=True,
                     help="False: the discriminator sees (state, action) (disc_only_states of the reference's launcher); needs a "
                          "dataset with `actions`, which the bundled task's trajectory does not hold")
+    ap.add_argument("--log", action="store_true",
+                    help="give the agent a writer, as the reference's launcher does: the discriminator's diagnostics "
+                         "(_discriminator_logging, K19) run after every discriminator epoch and are printed")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
@@ -70,7 +73,7 @@ def main():
         step = DeviceTRPO(policy, max_kl=1e-2, ent_coeff=1e-3, n_epochs_cg=25)
     agent = GAILAgent(eng, disc, trainer, critic, step, gamma=0.99, lam=0.97, env_reward_frac=0.0,
                       train_D_n_th_epoch=3 if args.disc_fit == "device" else 10 ** 9,
-                      critic_fit_params=dict(n_epochs=3, batch_size=256))
+                      critic_fit_params=dict(n_epochs=3, batch_size=256), sw=PrintingWriter() if args.log else None)
     T, N = args.steps, args.num_envs
     x = torch.empty((T + 1, N, n_obs), dtype=torch.float32, device="cuda")
     act = torch.empty((T, N, n_act), dtype=torch.float32, device="cuda")

@@ -6,7 +6,7 @@ the policy is a random one on the kinematic stand-in physics.  With --policy dev
 DeviceGaussianPolicy (obs -> [512, 256] -> act, std_0 0.5) and DeviceTRPO (K17) trains it with UnitreeH1's confs.yaml
 values (max_kl 5e-3, ent_coeff 1e-3, n_epochs_cg 25).
 
-    python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device]
+    python examples/vail_fit.py --num_envs 4096 --steps 100 --iters 3 [--disc-fit device] [--policy device] [--log]
                                 [--disc_use_next_states] [--disc_only_states False]
 
 --disc_use_next_states gives the discriminator (state, next state) (64 columns for H1's 32-column kinematic mask),
@@ -32,6 +32,13 @@ def policy_step(obs, act, adv, agent):
     """The caller's TRPO step would go here; this one only looks at its inputs."""
     print(f"  policy_step: {obs.shape[0]} rows, advantage mean {float(adv.mean()):+.2e} "
           f"std {float(adv.std(unbiased=False)):.4f}")
+
+
+class PrintingWriter:
+    """The part of a SummaryWriter the agent uses: add_scalar, printed."""
+
+    def add_scalar(self, tag, value, step):
+        print(f"    [{step}] {tag}: {value:.6g}")
 
 
 def paired_inputs(args, env, mask, n_act):
@@ -63,7 +70,13 @@ def main():
     ap.add_argument("--disc_only_states", type=lambda s: s.lower() in ("1", "true", "yes"), default=True,
                     help="False: the discriminator sees (state, action) (disc_only_states of the reference's launcher); needs a "
                          "dataset with `actions`, which the bundled task's trajectory does not hold")
+    ap.add_argument("--log", action="store_true",
+                    help="give the agent a writer, as the reference's launcher does: the discriminator's diagnostics "
+                         "(_discriminator_logging, K19) run after every discriminator epoch and are printed; needs "
+                         "--disc-fit device")
     args = ap.parse_args()
+    if args.log and args.disc_fit != "device":
+        raise SystemExit("--log needs --disc-fit device (the torch trainer has no diagnostics)")
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
     vec, eng = env.vec, env.vec.eng
@@ -93,7 +106,8 @@ def main():
         policy = DeviceGaussianPolicy(eng, pol_lins, trpo_standardizer, std_0=0.5)
         step = DeviceTRPO(policy, max_kl=5e-3, ent_coeff=1e-3, n_epochs_cg=25)
     agent = VAILAgent(eng, disc, trainer, critic, step, gamma=0.99, lam=0.97, env_reward_frac=0.0,
-                      train_D_n_th_epoch=3, critic_fit_params=dict(n_epochs=3, batch_size=256))
+                      train_D_n_th_epoch=3, critic_fit_params=dict(n_epochs=3, batch_size=256),
+                      sw=PrintingWriter() if args.log else None)
     T, N = args.steps, args.num_envs
     x = torch.empty((T + 1, N, n_obs), dtype=torch.float32, device="cuda")
     act = torch.empty((T, N, n_act), dtype=torch.float32, device="cuda")

@@ -179,6 +179,26 @@ class DiscPair(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class GailDiscLog(C.Structure):
+    """oly_gail_disc_log_args (K19): GAIL's discriminator diagnostics for oly_gail_disc_log."""
+    _fields_ = [("in_dim", C.c_int32), ("n_rows", C.c_int32), ("n_plcy", C.c_int32), ("entcoeff", C.c_float), ("x", vp),
+                ("targets", vp), ("colstats", vp), ("packed", vp), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp)]
+
+
+class DiscLog(C.Structure):
+    """oly_disc_log_args (K19): the VAIL discriminator's diagnostics for oly_disc_log."""
+    _fields_ = [("in_dim", C.c_int32), ("n_rows", C.c_int32), ("n_plcy", C.c_int32), ("entcoeff", C.c_float),
+                ("info_constraint", C.c_float), ("lr_beta", C.c_float), ("x", vp), ("targets", vp), ("eps", vp),
+                ("beta", vp), ("colstats", vp), ("packed", vp), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp)]
+
+
+# out [OLY_DISC_LOG_SCALARS] of oly_gail_disc_log / oly_disc_log: the reference's tags in the order of its add_scalar
+# calls (gail_TRPO.py:227-249, vail_TRPO.py:30-32); GAIL fills the first nine
+OLY_DISC_LOG_SCALARS = 12
+DISC_LOG_TAGS = ("DiscrimLoss", "D_Generator_Accuracy", "D_Out_Generator", "D_Expert_Accuracy", "D_Out_Expert",
+                 "Bernoulli Ent.", "Neg. Bernoulli Ent. Loss (incl. in DiscrimLoss)", "Generator_loss", "Expert_Loss",
+                 "Bottleneck_Loss", "Beta", "Bottleneck_Loss_times_Beta")
+
 OLY_TRPO_ACCEPT_OR, OLY_TRPO_ACCEPT_AND, OLY_TRPO_SCALARS = 0, 1, 8
 
 
@@ -295,6 +315,10 @@ SIGNATURES = {
                                   + [vp] * 5),
     "oly_gail_disc_fit_pair_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_gail_disc_fit_epoch_pair": (C.c_int, [vp, C.POINTER(GailDiscFit), C.POINTER(DiscPair), vp, C.c_int, C.c_int, vp]),
+    "oly_gail_disc_log_ws_floats": (C.c_int64, [C.c_int]),
+    "oly_disc_log_ws_floats": (C.c_int64, [C.c_int]),
+    "oly_gail_disc_log": (C.c_int, [vp, C.POINTER(GailDiscLog), C.POINTER(DiscPair), vp]),
+    "oly_disc_log": (C.c_int, [vp, C.POINTER(DiscLog), C.POINTER(DiscPair), vp]),
     "oly_trpo_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),

@@ -1127,6 +1127,79 @@ class Engine:
         self.ctx.call("oly_gail_disc_fit_epoch_pair", C.byref(f), C.byref(pair), ptr(perm), n, batch, self._s())
         return loss_out
 
+    # -------------------------------------------------------------- K19 (the discriminator's diagnostics)
+    def gail_disc_log_ws(self, n_rows):
+        """A workspace for gail_disc_log on up to n_rows rows."""
+        from ._ffi import lib
+        n = int(lib().oly_gail_disc_log_ws_floats(int(n_rows)))
+        if n < 0:
+            raise OlyError(f"gail_disc_log: unsupported n_rows={n_rows} (at least one policy and one demonstration row)")
+        return self._new((n,), torch.float32)
+
+    def disc_log_ws(self, n_rows):
+        """A workspace for disc_log on up to n_rows rows."""
+        from ._ffi import lib
+        n = int(lib().oly_disc_log_ws_floats(int(n_rows)))
+        if n < 0:
+            raise OlyError(f"disc_log: unsupported n_rows={n_rows} (at least one policy and one demonstration row)")
+        return self._new((n,), torch.float32)
+
+    def _disc_log_common(self, name, x, n_plcy, colstats, ws, need, x2, standardise, targets, out):
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [n,Ds] tensor")
+        n, Ds = (int(v) for v in x.shape)
+        _req(x, "x", (n, Ds), f32, dv)
+        pair, d2 = None, 0
+        if x2 is not None:
+            pair, d2 = self._disc_pair(name, x2, None, standardise, n, Ds)
+        if not 0 < int(n_plcy) < n:
+            raise OlyError(f"{name}: n_plcy={n_plcy} outside (0, {n}): both halves need a row")
+        _req(targets, "targets", (n,), f32, dv, optional=True)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        nws = int(need(n))
+        if not isinstance(ws, torch.Tensor) or ws.dim() != 1 or int(ws.shape[0]) < nws:
+            raise OlyError(f"{name}: the workspace holds {0 if not isinstance(ws, torch.Tensor) else int(ws.numel())} "
+                           f"floats, {n} rows need {nws}")
+        _req(ws, "ws", (int(ws.shape[0]),), f32, dv)
+        out = _req(out if out is not None else self._new((_abi.OLY_DISC_LOG_SCALARS,), f64), "out",
+                   (_abi.OLY_DISC_LOG_SCALARS,), f64, dv)
+        return n, Ds, d2, pair, out
+
+    def gail_disc_log(self, x, n_plcy, colstats, packed, ws, entcoeff=1e-3, x2=None, standardise=False, targets=None,
+                      out=None):
+        """oly_gail_disc_log: _discriminator_logging's six forwards for GAIL on x [n,Ds] f32 (the masked concatenated
+        rows, n_plcy policy rows first) and, for a paired discriminator, x2 [n,D2] (standardise: next states).  colstats
+        [3,Ds] f64 is read and left where the reference's Standardizer ends; packed is the ilmlp_pack stream of the
+        current parameters.  Returns out [12] f64 on the device in _abi.DISC_LOG_TAGS' order (GAIL fills nine)."""
+        from ._ffi import lib
+        n, Ds, d2, pair, out = self._disc_log_common("gail_disc_log", x, n_plcy, colstats, ws,
+                                                     lib().oly_gail_disc_log_ws_floats, x2, standardise, targets, out)
+        _req(packed, "packed", (self._gail_packed_floats(Ds + d2),), torch.float32, self.device)
+        f = _abi.GailDiscLog(in_dim=Ds + d2, n_rows=n, n_plcy=int(n_plcy), entcoeff=float(entcoeff), x=x.data_ptr(),
+                             targets=ptr(targets), colstats=colstats.data_ptr(), packed=packed.data_ptr(),
+                             ws=ws.data_ptr(), ws_floats=int(ws.shape[0]), out=out.data_ptr())
+        self.ctx.call("oly_gail_disc_log", C.byref(f), C.byref(pair) if pair is not None else None, self._s())
+        return out
+
+    def disc_log(self, x, n_plcy, colstats, packed, beta, ws, info_constraint=0.1, lr_beta=1e-5, entcoeff=1e-3, eps=None,
+                 x2=None, standardise=False, targets=None, out=None):
+        """oly_disc_log: _discriminator_logging's seven forwards for VAIL.  As gail_disc_log, with beta [1] f32 the
+        VDBLoss's beta (read only) and eps [2 n + 2 n_plcy + 2 n_demo = 4 n, 128] f32 the noise of forwards 1 .. 6 in
+        forward order (all rows, demonstration half, policy half, twice), or None (z = mu)."""
+        from ._ffi import lib
+        n, Ds, d2, pair, out = self._disc_log_common("disc_log", x, n_plcy, colstats, ws, lib().oly_disc_log_ws_floats,
+                                                     x2, standardise, targets, out)
+        _req(packed, "packed", (self._disc_packed_floats(Ds + d2),), torch.float32, self.device)
+        _req(beta, "beta", (1,), torch.float32, self.device)
+        _req(eps, "eps", (4 * n, 128), torch.float32, self.device, optional=True)
+        f = _abi.DiscLog(in_dim=Ds + d2, n_rows=n, n_plcy=int(n_plcy), entcoeff=float(entcoeff),
+                         info_constraint=float(info_constraint), lr_beta=float(lr_beta), x=x.data_ptr(),
+                         targets=ptr(targets), eps=ptr(eps), beta=beta.data_ptr(), colstats=colstats.data_ptr(),
+                         packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=int(ws.shape[0]), out=out.data_ptr())
+        self.ctx.call("oly_disc_log", C.byref(f), C.byref(pair) if pair is not None else None, self._s())
+        return out
+
     # -------------------------------------------------------------- K6
     # -------------------------------------------------------------- K17 (TRPO's policy step)
     def trpo_args(self, obs, act, adv, colstats, theta, max_kl=0.01, ent_coeff=0.0, n_epochs_cg=10, cg_damping=1e-1,

@@ -18,9 +18,14 @@ fit minibatch adds its rows to it, as Standardizer.forward does (networks.py:68-
 import numpy as np
 import torch
 
+from . import _abi
 from ._ffi import OlyError
 
 _H1, _H2 = 512, 256
+
+# The scalars of _discriminator_logging in the order of the reference's add_scalar calls (gail_TRPO.py:227-249; VAIL adds
+# vail_TRPO.py:30-32): the columns of the `logs` a device trainer's fit(log=True) returns.
+DISC_LOG_NAMES = dict(gail=_abi.DISC_LOG_TAGS[:9], vail=_abi.DISC_LOG_TAGS)
 
 
 class DeviceILCritic:
@@ -125,12 +130,27 @@ class VAILAgent:
     disc_reward: DiscriminatorReward; disc_trainer: DiscriminatorTrainer (or anything with fit(x, generator=));
     critic: DeviceILCritic whose standardizer is the policy's trpo_standardizer.
 
+    sw: None, or a writer (anything with add_scalar(tag, value, step)) as the reference's launcher always passes one
+    (examples/imitation_learning/experiment.py:37,48).  With it every trained iteration runs _discriminator_logging
+    (gail_TRPO.py:222-249) on the device after each discriminator epoch, which also moves the discriminator's
+    Standardizer as the reference's extra forwards do, reads the scalars back once and calls
+    sw.add_scalar(tag, value, iter // 3) with the reference's tags in its order (DISC_LOG_NAMES), per epoch; the result
+    gains disc_log, a dict tag -> the last epoch's value.  _logging_sw's scalars (:251-272) are not produced.
+
     `start_iter` (1) and critic_fit_params' default n_epochs (3) are readings of mushroom-rl's TRPO, whose source is
     not part of this project's reference: they are not verified facts, which is why both are arguments."""
 
     def __init__(self, engine, disc_reward, disc_trainer, critic, policy_step, gamma=0.99, lam=0.97,
-                 env_reward_frac=0.0, train_D_n_th_epoch=3, critic_fit_params=None, start_iter=1):
+                 env_reward_frac=0.0, train_D_n_th_epoch=3, critic_fit_params=None, start_iter=1, sw=None):
+        import inspect
         from .rollout import GAERollout
+        if sw is not None:
+            if not callable(getattr(sw, "add_scalar", None)):
+                raise OlyError(f"{type(self).__name__}: sw must have add_scalar(tag, value, step) (a SummaryWriter)")
+            if "log" not in inspect.signature(disc_trainer.fit).parameters:
+                raise OlyError(f"{type(self).__name__}: sw needs a discriminator trainer whose fit takes log= (the "
+                               f"device trainers), not {type(disc_trainer).__name__}")
+        self.sw = sw
         if not 0.0 <= env_reward_frac <= 1.0:
             raise ValueError("Environment reward must be between [0,1]")
         self.eng, self.disc, self.disc_trainer, self.critic = engine, disc_reward, disc_trainer, critic
@@ -184,7 +204,8 @@ class VAILAgent:
 
     def fit(self, dataset, eps=None, generator=None):
         """One GAIL_TRPO.fit on [T,N,...] device blocks.  eps: the discriminator's reparameterisation noise [T*N, z]
-        or None (drawn from `generator`).  Returns dict(reward, v_target, adv, critic_loss, disc_loss, disc_trained)."""
+        or None (drawn from `generator`).  Returns dict(reward, v_target, adv, critic_loss, disc_loss, disc_trained),
+        and disc_log on a trained iteration of an agent with a writer."""
         state, action, reward, next_state, absorbing, last = self._blocks(dataset)
         x = state.to(torch.float32).contiguous()
         xn = next_state.to(torch.float32).contiguous()
@@ -203,16 +224,29 @@ class VAILAgent:
             st.update_mean_std(flat)
         critic_loss = self.critic.fit(flat, v_target.reshape(T * N), n_epochs=int(fit.get("n_epochs", 3)),
                                       batch_size=int(fit.get("batch_size", 256)), generator=generator)
-        disc_loss, trained = None, False
+        disc_loss, trained, disc_log = None, False, None
         if self.iter % self.train_D_n_th_epoch == 0:
+            kw = dict(generator=generator)
             if second is not None:
-                disc_loss = self.disc_trainer.fit(flat, generator=generator, x2=second)
-            else:
-                disc_loss = self.disc_trainer.fit(flat, generator=generator)
+                kw["x2"] = second
+            if self.sw is not None:
+                kw["log"] = True
+            disc_loss = self.disc_trainer.fit(flat, **kw)
+            if self.sw is not None:
+                disc_loss, logs = disc_loss
+                vals = logs.cpu().numpy()                           # the one read-back of the diagnostics
+                names = getattr(self.disc_trainer, "log_names", DISC_LOG_NAMES["vail"])
+                for row in vals:                                    # one _discriminator_logging per epoch, :220
+                    for i, name in enumerate(names):
+                        self.sw.add_scalar(name, float(row[i]), self.iter // 3)
+                disc_log = {name: float(vals[-1][i]) for i, name in enumerate(names)}
             trained = True
         self.iter += 1
-        return dict(reward=r, v_target=v_target, adv=adv, critic_loss=critic_loss, disc_loss=disc_loss,
-                    disc_trained=trained)
+        out = dict(reward=r, v_target=v_target, adv=adv, critic_loss=critic_loss, disc_loss=disc_loss,
+                   disc_trained=trained)
+        if disc_log is not None:
+            out["disc_log"] = disc_log
+        return out
 
 
 class PairedDemonstrations:
@@ -283,7 +317,8 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
     Differences from the reference, all stated: the demo draw, the permutation, the noise and the noisy targets come
     from the caller's torch.Generator (the reference uses np.random and torch's global generator), drawn in that
     order per epoch; _discriminator_logging's extra forwards (:222-250), which update the statistics only when a
-    SummaryWriter is attached, are not replayed.
+    SummaryWriter is attached, run with fit(log=True) (K19, oly_disc_log) and not otherwise: log=False is the
+    reference's sw=None agent.
 
     reward: the DiscriminatorReward whose network (VariationalDiscriminator, the K12 shape) and standardizer are
     fitted; demo: an ExpertDataset (mask folded in) or an array of full observations (a paired reward: an ExpertDataset,
@@ -329,6 +364,8 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
         self.exp_avg_sq = torch.zeros_like(self.param)
         self.beta = torch.empty(1, dtype=torch.float32, device=dev)
         self.step = 0
+        self._log_ws = None
+        self.log_names = DISC_LOG_NAMES["vail"]
 
     def _demo_rows(self, n, generator):
         rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
@@ -341,11 +378,22 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
         return d if self.r.mask is None else d[:, self.r.mask.long()]
 
     @torch.no_grad()
-    def fit(self, plcy_obs, generator=None, eps=None, x2=None):
+    def fit(self, plcy_obs, generator=None, eps=None, x2=None, log=False, log_eps=None):
         """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations) and, for a paired reward, the
         policy's second tensor x2 [n, obs or act] (next states or actions, full width).  eps: the reparameterisation
         noise, [n_epochs, n + m, 128] (or [n + m, 128] for one epoch) in minibatch order, or None (drawn from
-        `generator`).  Returns the per-minibatch losses, [n_epochs, n_batches] f64 on the device."""
+        `generator`).  Returns the per-minibatch losses, [n_epochs, n_batches] f64 on the device.
+
+        log=True: _discriminator_logging (gail_TRPO.py:222-249, vail_TRPO.py:23-32) runs on the device right after
+        each epoch's minibatch loop, where :220 puts it, so with n_epochs > 1 its seven forwards shift the next epoch's
+        statistics; the return value is then (losses, logs), logs [n_epochs, 12] f64 on the device in
+        DISC_LOG_NAMES["vail"]'s order.  The noise of forwards 1 .. 6 is log_eps [n_epochs, 4 (n + m), 128] (or
+        [4 (n + m), 128]: all rows, demonstration half, policy half, twice), or drawn from `generator` after the epoch's
+        other draws.  The halves split at the true boundary n; the reference splits at len // 2, which is the same
+        whenever the reference runs at all (with fewer demonstrations than policy rows its target array no longer
+        matches its inputs).  The copy of the loss the reference logs through takes beta's dual update between its
+        three loss evaluations and is then dropped; that is reproduced, and the trainer's beta is not changed.  With
+        log=False nothing differs from a trainer without diagnostics: same return value, statistics and bits."""
         r, eng, dev = self.r, self.eng, self.eng.device
         plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
         if self._mask_max is not None and int(plcy.shape[1]) <= self._mask_max:
@@ -370,6 +418,7 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
             st.colstats.zero_()
             st._fresh = False
         losses = None
+        logs = torch.zeros((self.n_epochs, _abi.OLY_DISC_LOG_SCALARS), dtype=torch.float64, device=dev) if log else None
         for e in range(self.n_epochs):
             demo = self._demo_rows(n, generator)
             xb = None
@@ -398,14 +447,24 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
                                         self.beta, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
                                         adam_eps=self.eps, weight_decay=self.wd, info_constraint=self.loss._info_constr,
                                         lr_beta=self.loss._lr_beta, targets=targets, loss_out=losses[e])
-                self.step += nb
-                continue
-            eng.disc_fit_epoch(x, n, noise.to(torch.float32).contiguous(), perm, self.batch, st.colstats, self.param,
-                               self.exp_avg, self.exp_avg_sq, r._packed, self.beta, self._ws, self.step, self.lr,
-                               beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps, weight_decay=self.wd,
-                               info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta, targets=targets,
-                               loss_out=losses[e])
+            else:
+                eng.disc_fit_epoch(x, n, noise.to(torch.float32).contiguous(), perm, self.batch, st.colstats, self.param,
+                                   self.exp_avg, self.exp_avg_sq, r._packed, self.beta, self._ws, self.step, self.lr,
+                                   beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps, weight_decay=self.wd,
+                                   info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta, targets=targets,
+                                   loss_out=losses[e])
             self.step += nb
+            if log:                                                 # _discriminator_logging, :220
+                if log_eps is None:
+                    leps = torch.randn((4 * rows, 128), device=dev, generator=generator)
+                else:
+                    leps = (log_eps[e] if log_eps.dim() == 3 else log_eps).to(torch.float32).contiguous()
+                if self._log_ws is None or self._log_ws[0] < rows:
+                    self._log_ws = (rows, eng.disc_log_ws(rows))
+                eng.disc_log(x, n, st.colstats, r._packed, self.beta, self._log_ws[1],
+                             info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta,
+                             entcoeff=float(getattr(self.loss, "entcoeff", 1e-3)), eps=leps, x2=xb,
+                             standardise=self.pair == "next_state", targets=targets, out=logs[e])
         o = 0
         for p in ps:                                                # in place: captured pointers stay valid
             k = int(p.numel())
@@ -413,7 +472,7 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
             o += k
         r.invalidate()
         self.loss._beta = float(self.beta)                           # the one host read-back of the call
-        return losses
+        return (losses, logs) if log else losses
 
 
 class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
@@ -428,7 +487,8 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
         Standardizer.forward, DiscriminatorNetwork.forward, GailDiscriminatorLoss(entcoeff), backward, Adam   (K18)
 
     The draws come from the caller's torch.Generator in the order demo, noisy targets (demo first), perm, per epoch;
-    _discriminator_logging's extra forwards are not replayed (as DeviceDiscriminatorTrainer).  Defaults are
+    _discriminator_logging's extra forwards run with fit(log=True) (K19, oly_gail_disc_log; as
+    DeviceDiscriminatorTrainer).  Defaults are
     HumanoidMuscle's of confs.yaml (lr_disc 5e-6, d_entr_coef 1e-3) and create_gail_agent's (weight_decay 0, batch 2048).
 
     reward: the GAILDiscriminatorReward whose network and standardizer are fitted; demo: an ExpertDataset (mask folded
@@ -468,6 +528,8 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
         self.exp_avg = torch.zeros_like(self.param)
         self.exp_avg_sq = torch.zeros_like(self.param)
         self.step = 0
+        self._log_ws = None
+        self.log_names = DISC_LOG_NAMES["gail"]
 
     def _demo_rows(self, n, generator):
         rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
@@ -480,10 +542,18 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
         return d if self.r.mask is None else d[:, self.r.mask.long()]
 
     @torch.no_grad()
-    def fit(self, plcy_obs, generator=None, x2=None):
+    def fit(self, plcy_obs, generator=None, x2=None, log=False):
         """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations) and, for a paired reward, the
         policy's second tensor x2 [n, obs or act] (next states or actions, full width).  Returns the per-minibatch
-        losses, [n_epochs, n_batches] f64 on the device."""
+        losses, [n_epochs, n_batches] f64 on the device.
+
+        log=True: _discriminator_logging (gail_TRPO.py:222-249) runs on the device right after each epoch's minibatch
+        loop, where :220 puts it, so with n_epochs > 1 its six forwards shift the next epoch's statistics; the return
+        value is then (losses, logs), logs [n_epochs, 12] f64 on the device, the first nine columns in
+        DISC_LOG_NAMES["gail"]'s order and the rest 0.  The halves split at the true boundary n; the reference splits at
+        len // 2, which is the same whenever the reference runs at all (with fewer demonstrations than policy rows its
+        target array no longer matches its inputs).  With log=False nothing differs from a trainer without
+        diagnostics: same return value, statistics and bits."""
         r, eng, dev = self.r, self.eng, self.eng.device
         plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
         n = int(plcy.shape[0])
@@ -506,6 +576,7 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
             st.colstats.zero_()
             st._fresh = False
         losses = None
+        logs = torch.zeros((self.n_epochs, _abi.OLY_DISC_LOG_SCALARS), dtype=torch.float64, device=dev) if log else None
         for e in range(self.n_epochs):
             demo = self._demo_rows(n, generator)
             xb = None
@@ -530,19 +601,23 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
                                              beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps,
                                              weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
                                              loss_out=losses[e])
-                self.step += nb
-                continue
-            eng.gail_disc_fit_epoch(x, n, perm, self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq,
-                                    r._packed, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
-                                    adam_eps=self.eps, weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
-                                    loss_out=losses[e])
+            else:
+                eng.gail_disc_fit_epoch(x, n, perm, self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq,
+                                        r._packed, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
+                                        adam_eps=self.eps, weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
+                                        loss_out=losses[e])
             self.step += nb
+            if log:                                                 # _discriminator_logging, :220
+                if self._log_ws is None or self._log_ws[0] < rows:
+                    self._log_ws = (rows, eng.gail_disc_log_ws(rows))
+                eng.gail_disc_log(x, n, st.colstats, r._packed, self._log_ws[1], entcoeff=self.entcoeff, x2=xb,
+                                  standardise=self.pair == "next_state", targets=targets, out=logs[e])
         o = 0
         for p in ps:                                                # in place: captured pointers stay valid
             k = int(p.numel())
             p.data.copy_(self.param[o:o + k].view_as(p))
             o += k
-        return losses
+        return (losses, logs) if log else losses
 
 
 class GAILAgent(VAILAgent):
@@ -552,7 +627,7 @@ class GAILAgent(VAILAgent):
 
     def fit(self, dataset, generator=None):
         """One GAIL_TRPO.fit on [T,N,...] device blocks.  Returns dict(reward, v_target, adv, critic_loss, disc_loss,
-        disc_trained)."""
+        disc_trained), and disc_log on a trained iteration of an agent with a writer."""
         return super().fit(dataset, eps=None, generator=generator)
 
 
