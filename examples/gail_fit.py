@@ -24,7 +24,7 @@ import torch  # noqa: E402
 from olympic_hip.envs import LocoEnvBase  # noqa: E402
 from olympic_hip.gail import DeviceStandardizer, GAILDiscriminator, GAILDiscriminatorReward  # noqa: E402
 from olympic_hip.il_agent import (DeviceGAILDiscriminatorTrainer, DeviceGaussianPolicy, DeviceILCritic,  # noqa: E402
-                                  DeviceTRPO, GAILAgent)
+                                  DeviceTRPO, GAILAgent, episode_stats)
 from vail_fit import PrintingWriter, paired_inputs  # noqa: E402  (the example beside this one: the two switches mean the same there)
 
 
@@ -50,7 +50,9 @@ def main():
                          "dataset with `actions`, which the bundled task's trajectory does not hold")
     ap.add_argument("--log", action="store_true",
                     help="give the agent a writer, as the reference's launcher does: the discriminator's diagnostics "
-                         "(_discriminator_logging, K19) run after every discriminator epoch and are printed")
+                         "(_discriminator_logging, K19) run after every discriminator epoch and are printed.  With "
+                         "--policy device the iteration's diagnostics (_logging_sw, K20: the episode means, vf_loss, "
+                         "entropy, kl) run and are printed as well")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
@@ -73,7 +75,8 @@ def main():
         step = DeviceTRPO(policy, max_kl=1e-2, ent_coeff=1e-3, n_epochs_cg=25)
     agent = GAILAgent(eng, disc, trainer, critic, step, gamma=0.99, lam=0.97, env_reward_frac=0.0,
                       train_D_n_th_epoch=3 if args.disc_fit == "device" else 10 ** 9,
-                      critic_fit_params=dict(n_epochs=3, batch_size=256), sw=PrintingWriter() if args.log else None)
+                      critic_fit_params=dict(n_epochs=3, batch_size=256), sw=PrintingWriter() if args.log else None,
+                      iteration_log=args.log and policy is not None)
     T, N = args.steps, args.num_envs
     x = torch.empty((T + 1, N, n_obs), dtype=torch.float32, device="cuda")
     act = torch.empty((T, N, n_act), dtype=torch.float32, device="cuda")
@@ -90,6 +93,8 @@ def main():
             o, r, a, info = vec.step(act[t])
             x[t + 1], r_env[t], absorbing[t], last[t] = o.to(torch.float32), r, a, info["last"]
         last[-1] = True
+        ep = episode_stats(eng, r_env, last).tolist()      # compute_J / compute_episodes_length of the rollout (K20)
+        print(f"rollout {it}: {ep[3]:.0f} episodes, mean return {ep[0]:.4f}, mean length {ep[2]:.2f} over {ep[4]:.0f} completed")
         out = agent.fit(dict(state=x[:-1], action=act, reward=r_env, next_state=x[1:], absorbing=absorbing, last=last),
                         generator=gen)
         loss = out["critic_loss"]

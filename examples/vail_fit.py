@@ -25,7 +25,7 @@ from olympic_hip.envs import LocoEnvBase  # noqa: E402
 from olympic_hip.gail import (DeviceStandardizer, DiscriminatorReward, DiscriminatorTrainer,  # noqa: E402
                               VariationalDiscriminator, VDBLoss)
 from olympic_hip.il_agent import (DeviceDiscriminatorTrainer, DeviceGaussianPolicy, DeviceILCritic,  # noqa: E402
-                                  DeviceTRPO, VAILAgent)
+                                  DeviceTRPO, VAILAgent, episode_stats)
 
 
 def policy_step(obs, act, adv, agent):
@@ -73,7 +73,8 @@ def main():
     ap.add_argument("--log", action="store_true",
                     help="give the agent a writer, as the reference's launcher does: the discriminator's diagnostics "
                          "(_discriminator_logging, K19) run after every discriminator epoch and are printed; needs "
-                         "--disc-fit device")
+                         "--disc-fit device.  With --policy device the iteration's diagnostics (_logging_sw, K20: the "
+                         "episode means, vf_loss, entropy, kl) run and are printed as well")
     args = ap.parse_args()
     if args.log and args.disc_fit != "device":
         raise SystemExit("--log needs --disc-fit device (the torch trainer has no diagnostics)")
@@ -107,7 +108,7 @@ def main():
         step = DeviceTRPO(policy, max_kl=5e-3, ent_coeff=1e-3, n_epochs_cg=25)
     agent = VAILAgent(eng, disc, trainer, critic, step, gamma=0.99, lam=0.97, env_reward_frac=0.0,
                       train_D_n_th_epoch=3, critic_fit_params=dict(n_epochs=3, batch_size=256),
-                      sw=PrintingWriter() if args.log else None)
+                      sw=PrintingWriter() if args.log else None, iteration_log=args.log and policy is not None)
     T, N = args.steps, args.num_envs
     x = torch.empty((T + 1, N, n_obs), dtype=torch.float32, device="cuda")
     act = torch.empty((T, N, n_act), dtype=torch.float32, device="cuda")
@@ -124,6 +125,8 @@ def main():
             o, r, a, info = vec.step(act[t])
             x[t + 1], r_env[t], absorbing[t], last[t] = o.to(torch.float32), r, a, info["last"]
         last[-1] = True
+        ep = episode_stats(eng, r_env, last).tolist()      # compute_J / compute_episodes_length of the rollout (K20)
+        print(f"rollout {it}: {ep[3]:.0f} episodes, mean return {ep[0]:.4f}, mean length {ep[2]:.2f} over {ep[4]:.0f} completed")
         out = agent.fit(dict(state=x[:-1], action=act, reward=r_env, next_state=x[1:], absorbing=absorbing, last=last),
                         generator=gen)
         loss = out["critic_loss"]

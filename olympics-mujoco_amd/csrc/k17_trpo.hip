@@ -875,6 +875,15 @@ extern "C" int64_t oly_trpo_ws_floats(int n, int in_dim, int h1, int h2, int out
   return (int64_t)ws_layout(n, in_dim, out_dim).total;
 }
 
+extern "C" int oly_trpo_old_offsets(int n, int in_dim, int h1, int h2, int out_dim, int64_t* mu_old_off,
+                                    int64_t* log_sigma_old_off) {
+  if (n <= 0 || !shape_ok(in_dim, h1, h2, out_dim, OLY_ACT_IDENTITY) || !mu_old_off || !log_sigma_old_off) return OLY_EINVAL;
+  const Ws w = ws_layout(n, in_dim, out_dim);
+  *mu_old_off = (int64_t)w.mu_old;
+  *log_sigma_old_off = (int64_t)(w.th0 + layout(in_dim, out_dim).ls);
+  return OLY_OK;
+}
+
 extern "C" int oly_trpo_grad(oly_ctx* ctx, const oly_trpo_step_args* a, int k_stats, const float* logp_old,
                              float* grad_out, double* j_out, oly_stream stream) {
   if (!ctx) return OLY_EINVAL;

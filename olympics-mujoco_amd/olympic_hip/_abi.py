@@ -202,6 +202,20 @@ DISC_LOG_TAGS = ("DiscrimLoss", "D_Generator_Accuracy", "D_Out_Generator", "D_Ex
 OLY_TRPO_ACCEPT_OR, OLY_TRPO_ACCEPT_AND, OLY_TRPO_SCALARS = 0, 1, 8
 
 
+class IterLog(C.Structure):
+    """oly_iter_log_args (K20): the agent's iteration diagnostics (_logging_sw) for oly_iter_log."""
+    _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("act_dim", C.c_int32), ("T", C.c_int32), ("N", C.c_int32),
+                ("rew_f64", C.c_int32), ("x", vp), ("v_target", vp), ("mu_old", vp), ("log_sigma_old", vp),
+                ("log_sigma", vp), ("critic_packed", vp), ("policy_packed", vp), ("rew_env", vp), ("rew", vp), ("last", vp),
+                ("colstats", vp), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp)]
+
+
+# out [OLY_ITER_LOG_SCALARS] of oly_iter_log: the reference's tags in the order of its add_scalar calls
+# (gail_TRPO.py:267-272), then the mean episode length before rounding and the number of completed episodes
+OLY_EPISODE_STATS, OLY_ITER_LOG_SCALARS = 8, 8
+ITER_LOG_TAGS = ("EpTrueRewMean", "EpRewMean", "EpLenMean", "vf_loss", "entropy", "kl")
+
+
 class TRPOStep(C.Structure):
     """oly_trpo_step_args (K17): one TRPO policy step, or the gradient / FVP pieces."""
     _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32),
@@ -321,6 +335,10 @@ SIGNATURES = {
     "oly_disc_log": (C.c_int, [vp, C.POINTER(DiscLog), C.POINTER(DiscPair), vp]),
     "oly_trpo_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "oly_trpo_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "oly_trpo_old_offsets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "oly_episode_stats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]),
+    "oly_iter_log_ws_floats": (C.c_int64, [C.c_int]),
+    "oly_iter_log": (C.c_int, [vp, C.POINTER(IterLog), vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

@@ -1200,6 +1200,102 @@ class Engine:
         self.ctx.call("oly_disc_log", C.byref(f), C.byref(pair) if pair is not None else None, self._s())
         return out
 
+    # -------------------------------------------------------------- K20 (the agent's iteration diagnostics)
+    def _episode_blocks(self, name, reward, last, reward2):
+        f32, dv = torch.float32, self.device
+        if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
+            raise OlyError(f"{name}: reward is a [T,N] tensor")
+        T, N = (int(v) for v in reward.shape)
+        if T < 1 or N < 1 or T * N >= 2 ** 31:
+            raise OlyError(f"{name}: supported: T >= 1, N >= 1, T N < 2^31 (got [{T}, {N}])")
+        r64 = reward.dtype == torch.float64
+        _req(reward, "reward", (T, N), torch.float64 if r64 else f32, dv)
+        _req(reward2, "reward2", (T, N), f32, dv, optional=True)
+        if not isinstance(last, torch.Tensor) or last.dtype not in (torch.bool, torch.uint8):
+            raise OlyError(f"{name}: last is a bool or uint8 tensor")
+        _req(last, "last", (T, N), last.dtype, dv)
+        return T, N, r64
+
+    def episode_stats(self, reward, last, gamma=1.0, reward2=None, out=None):
+        """oly_episode_stats: compute_J / compute_episodes_length per environment over reward [T,N] (f32 or f64), an
+        optional second block reward2 [T,N] f32 and last [T,N] (bool or uint8).  Returns out [8] f64 on the device: mean
+        return, mean return of reward2, mean length (NaN without a completed episode), number of returns, number of
+        lengths, and the three sums.  No synchronisation."""
+        T, N, r64 = self._episode_blocks("episode_stats", reward, last, reward2)
+        if not 0.0 <= float(gamma) <= 1.0:
+            raise OlyError(f"episode_stats: gamma {gamma} outside [0, 1]")
+        out = _req(out if out is not None else self._new((_abi.OLY_EPISODE_STATS,), torch.float64), "out",
+                   (_abi.OLY_EPISODE_STATS,), torch.float64, self.device)
+        self.ctx.call("oly_episode_stats", T, N, int(r64), C.c_double(float(gamma)), ptr(reward), ptr(reward2), ptr(last),
+                      ptr(out), self._s())
+        return out
+
+    def iter_log_ws(self, n):
+        """A workspace for iter_log on up to n rows."""
+        from ._ffi import lib
+        k = int(lib().oly_iter_log_ws_floats(int(n)))
+        if k < 0:
+            raise OlyError(f"iter_log: unsupported n={n}")
+        return self._new((k,), torch.float32)
+
+    def iter_log(self, x, v_target, mu_old, log_sigma_old, log_sigma, critic_packed, policy_packed, reward_env, reward, last,
+                 colstats, ws, out=None):
+        """oly_iter_log: _logging_sw (gail_TRPO.py:251-272) on x [n,in] f32 (row t N + e), v_target [n] f32, the old
+        distribution mu_old [n,act] / log_sigma_old [act], the stepped policy's log_sigma [act], the packed critic and
+        policy mean networks, reward_env [T,N] (f32 or f64), reward [T,N] f32 (the reward trained on) and last [T,N].
+        colstats [3,in] f64 is read as S and left at S + 2c.  Returns out [8] f64 on the device: _abi.ITER_LOG_TAGS'
+        six scalars, the mean episode length before rounding, the completed episodes."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(mu_old, torch.Tensor) or mu_old.dim() != 2:
+            raise OlyError("iter_log: x [n,in] and mu_old [n,act] must be 2-D tensors")
+        n, D = (int(v) for v in x.shape)
+        A = int(mu_old.shape[1])
+        T, N, r64 = self._episode_blocks("iter_log", reward_env, last, reward)
+        if reward is None:
+            raise OlyError("iter_log: reward (the reward the agent trained on) is required")
+        if T * N != n:
+            raise OlyError(f"iter_log: x has {n} rows, the blocks are [{T}, {N}]")
+        np_c = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 1))
+        np_p = int(lib().oly_ilmlp_packed_floats(D, 512, 256, A))
+        if np_c < 0 or np_p < 0:
+            raise OlyError(f"iter_log: unsupported shape in={D} act={A} (in <= 64, act <= 32)")
+        _req(x, "x", (n, D), f32, dv)
+        _req(v_target, "v_target", (n,), f32, dv)
+        _req(mu_old, "mu_old", (n, A), f32, dv)
+        _req(log_sigma_old, "log_sigma_old", (A,), f32, dv)
+        _req(log_sigma, "log_sigma", (A,), f32, dv)
+        _req(critic_packed, "critic_packed", (np_c,), f32, dv)
+        _req(policy_packed, "policy_packed", (np_p,), f32, dv)
+        _req(colstats, "colstats", (3, D), f64, dv)
+        need = int(lib().oly_iter_log_ws_floats(n))
+        if not isinstance(ws, torch.Tensor) or ws.dim() != 1 or int(ws.shape[0]) < need:
+            raise OlyError(f"iter_log: the workspace holds {0 if not isinstance(ws, torch.Tensor) else int(ws.numel())} "
+                           f"floats, {n} rows need {need}")
+        _req(ws, "ws", (int(ws.shape[0]),), f32, dv)
+        out = _req(out if out is not None else self._new((_abi.OLY_ITER_LOG_SCALARS,), f64), "out",
+                   (_abi.OLY_ITER_LOG_SCALARS,), f64, dv)
+        f = _abi.IterLog(n=n, in_dim=D, act_dim=A, T=T, N=N, rew_f64=int(r64), x=x.data_ptr(), v_target=v_target.data_ptr(),
+                         mu_old=mu_old.data_ptr(), log_sigma_old=log_sigma_old.data_ptr(), log_sigma=log_sigma.data_ptr(),
+                         critic_packed=critic_packed.data_ptr(), policy_packed=policy_packed.data_ptr(),
+                         rew_env=reward_env.data_ptr(), rew=reward.data_ptr(), last=last.data_ptr(),
+                         colstats=colstats.data_ptr(), ws=ws.data_ptr(), ws_floats=int(ws.shape[0]), out=out.data_ptr())
+        self.ctx.call("oly_iter_log", C.byref(f), self._s())
+        return out
+
+    def trpo_old_distribution(self, ws, n, in_dim, out_dim, hidden=(512, 256)):
+        """Views (no copy) of the old distribution the last trpo_step on `ws` left in it: (mu_old [n,out] f32,
+        log_sigma_old [out] f32), gail_TRPO.py:132-133."""
+        from ._ffi import lib
+        a, b = C.c_int64(), C.c_int64()
+        rc = lib().oly_trpo_old_offsets(int(n), int(in_dim), int(hidden[0]), int(hidden[1]), int(out_dim), C.byref(a),
+                                        C.byref(b))
+        if rc != _abi.OLY_OK:
+            raise OlyError(f"trpo_old_distribution: unsupported n={n} / policy {in_dim} -> {hidden} -> {out_dim}")
+        need = int(lib().oly_trpo_ws_floats(int(n), int(in_dim), int(hidden[0]), int(hidden[1]), int(out_dim)))
+        _req(ws, "ws", (need,), torch.float32, self.device)
+        return ws[a.value:a.value + n * out_dim].view(n, out_dim), ws[b.value:b.value + out_dim]
+
     # -------------------------------------------------------------- K6
     # -------------------------------------------------------------- K17 (TRPO's policy step)
     def trpo_args(self, obs, act, adv, colstats, theta, max_kl=0.01, ent_coeff=0.0, n_epochs_cg=10, cg_damping=1e-1,

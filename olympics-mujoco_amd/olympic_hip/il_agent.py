@@ -11,6 +11,8 @@
                                                              reading: one Adam step per epoch on the whole batch)
   TRPO's policy step (:131-149)                           -> the caller's policy_step, e.g. DeviceTRPO (K17,
                                                              oly_trpo_step) on a DeviceGaussianPolicy
+  the iteration's diagnostics (_logging_sw, :163, 251-272) -> VAILAgent(iteration_log=True) (K20, oly_iter_log);
+                                                             compute_J / compute_episodes_length: episode_stats
 
 The critic shares the policy's running Standardizer (trpo_standardizer, utils.py:123); every evaluation and every
 fit minibatch adds its rows to it, as Standardizer.forward does (networks.py:68-81).
@@ -26,6 +28,22 @@ _H1, _H2 = 512, 256
 # The scalars of _discriminator_logging in the order of the reference's add_scalar calls (gail_TRPO.py:227-249; VAIL adds
 # vail_TRPO.py:30-32): the columns of the `logs` a device trainer's fit(log=True) returns.
 DISC_LOG_NAMES = dict(gail=_abi.DISC_LOG_TAGS[:9], vail=_abi.DISC_LOG_TAGS)
+# The scalars of _logging_sw in the order of the reference's add_scalar calls (gail_TRPO.py:267-272): the keys of the
+# `iter_log` an agent built with iteration_log=True returns.
+ITER_LOG_NAMES = _abi.ITER_LOG_TAGS
+
+
+def episode_stats(eng, reward, last, gamma=1.0, reward2=None):
+    """mushroom-rl's compute_J(dataset, gamma) and compute_episodes_length(dataset) (a reading of mushroom-rl >= 1.10;
+    the launcher's Eval_R / Eval_J / Eval_L, examples/imitation_learning/experiment.py:57-64, and _logging_sw's episode
+    scalars) over [T,N] device blocks, every environment's column one dataset: reward f32 or f64, reward2 an optional
+    second f32 block, last bool or uint8.  Returns a device tensor [8] f64 without synchronising: mean return, mean return
+    of reward2 (0 without), mean length, number of returns, number of lengths, sum of the returns, of reward2's, of the
+    lengths.  An episode still open at the end of a column counts among the returns and not among the lengths; without
+    a completed episode the mean length is NaN (the reference raises in int(np.round(nan)))."""
+    T, N = int(reward.shape[0]), int(reward.shape[1])
+    return eng.episode_stats(reward.reshape(T, N).contiguous(), last.reshape(T, N).contiguous(), gamma=gamma,
+                             reward2=None if reward2 is None else reward2.reshape(T, N).to(torch.float32).contiguous())
 
 
 class DeviceILCritic:
@@ -135,13 +153,23 @@ class VAILAgent:
     (gail_TRPO.py:222-249) on the device after each discriminator epoch, which also moves the discriminator's
     Standardizer as the reference's extra forwards do, reads the scalars back once and calls
     sw.add_scalar(tag, value, iter // 3) with the reference's tags in its order (DISC_LOG_NAMES), per epoch; the result
-    gains disc_log, a dict tag -> the last epoch's value.  _logging_sw's scalars (:251-272) are not produced.
+    gains disc_log, a dict tag -> the last epoch's value.
+
+    iteration_log: False, or True to run _logging_sw (:163, 251-272) as well, which the reference does on the same
+    iterations: after the discriminator's fit and its diagnostics one oly_iter_log call (K20) forms EpTrueRewMean,
+    EpRewMean, EpLenMean, vf_loss, entropy and kl (ITER_LOG_NAMES) and moves the policy / critic Standardizer two
+    batches further, as self._V(x) and self.policy.distribution(x) do there; the six doubles are read back once,
+    handed to sw.add_scalar(tag, value, iter // 3) after the discriminator's tags, and returned as iter_log (a dict
+    tag -> value).  It needs sw, a policy_step with `policy` (a DeviceGaussianPolicy) and old_distribution() (DeviceTRPO),
+    and a policy and critic sharing one Standardizer.  EpLenMean is NaN when the rollout completed no episode (the
+    reference raises in int(np.round(nan))).  On other iterations nothing runs and the statistics do not move.
 
     `start_iter` (1) and critic_fit_params' default n_epochs (3) are readings of mushroom-rl's TRPO, whose source is
     not part of this project's reference: they are not verified facts, which is why both are arguments."""
 
     def __init__(self, engine, disc_reward, disc_trainer, critic, policy_step, gamma=0.99, lam=0.97,
-                 env_reward_frac=0.0, train_D_n_th_epoch=3, critic_fit_params=None, start_iter=1, sw=None):
+                 env_reward_frac=0.0, train_D_n_th_epoch=3, critic_fit_params=None, start_iter=1, sw=None,
+                 iteration_log=False):
         import inspect
         from .rollout import GAERollout
         if sw is not None:
@@ -151,6 +179,19 @@ class VAILAgent:
                 raise OlyError(f"{type(self).__name__}: sw needs a discriminator trainer whose fit takes log= (the "
                                f"device trainers), not {type(disc_trainer).__name__}")
         self.sw = sw
+        self.iteration_log = bool(iteration_log)
+        self._iter_ws = None
+        if self.iteration_log:
+            name = type(self).__name__
+            if sw is None:
+                raise OlyError(f"{name}: iteration_log=True needs sw (the writer _logging_sw's scalars go to)")
+            pol = getattr(policy_step, "policy", None)
+            if not isinstance(pol, DeviceGaussianPolicy) or not callable(getattr(policy_step, "old_distribution", None)):
+                raise OlyError(f"{name}: iteration_log=True needs a policy_step with `policy` (a DeviceGaussianPolicy) "
+                               f"and old_distribution() (DeviceTRPO), not {type(policy_step).__name__}")
+            if pol.stand is not critic.stand:
+                raise OlyError(f"{name}: iteration_log=True needs the policy and the critic to share one Standardizer "
+                               "(trpo_standardizer, examples/imitation_learning/utils.py:123)")
         if not 0.0 <= env_reward_frac <= 1.0:
             raise ValueError("Environment reward must be between [0,1]")
         self.eng, self.disc, self.disc_trainer, self.critic = engine, disc_reward, disc_trainer, critic
@@ -205,7 +246,7 @@ class VAILAgent:
     def fit(self, dataset, eps=None, generator=None):
         """One GAIL_TRPO.fit on [T,N,...] device blocks.  eps: the discriminator's reparameterisation noise [T*N, z]
         or None (drawn from `generator`).  Returns dict(reward, v_target, adv, critic_loss, disc_loss, disc_trained),
-        and disc_log on a trained iteration of an agent with a writer."""
+        and disc_log (with iteration_log=True also iter_log) on a trained iteration of an agent with a writer."""
         state, action, reward, next_state, absorbing, last = self._blocks(dataset)
         x = state.to(torch.float32).contiguous()
         xn = next_state.to(torch.float32).contiguous()
@@ -224,7 +265,7 @@ class VAILAgent:
             st.update_mean_std(flat)
         critic_loss = self.critic.fit(flat, v_target.reshape(T * N), n_epochs=int(fit.get("n_epochs", 3)),
                                       batch_size=int(fit.get("batch_size", 256)), generator=generator)
-        disc_loss, trained, disc_log = None, False, None
+        disc_loss, trained, disc_log, iter_log = None, False, None, None
         if self.iter % self.train_D_n_th_epoch == 0:
             kw = dict(generator=generator)
             if second is not None:
@@ -241,12 +282,36 @@ class VAILAgent:
                         self.sw.add_scalar(name, float(row[i]), self.iter // 3)
                 disc_log = {name: float(vals[-1][i]) for i, name in enumerate(names)}
             trained = True
+            if self.iteration_log:                                  # _logging_sw, :163
+                iter_log = self._logging_sw(flat, v_target.reshape(T * N), reward.reshape(T, N), r, last.reshape(T, N))
         self.iter += 1
         out = dict(reward=r, v_target=v_target, adv=adv, critic_loss=critic_loss, disc_loss=disc_loss,
                    disc_trained=trained)
         if disc_log is not None:
             out["disc_log"] = disc_log
+        if iter_log is not None:
+            out["iter_log"] = iter_log
         return out
+
+    @torch.no_grad()
+    def _logging_sw(self, flat, v_target, r_env, r, last):
+        """_logging_sw (gail_TRPO.py:251-272) on K20: one call, one read-back, six add_scalar calls."""
+        eng, pol = self.eng, self.policy_step.policy
+        mu_old, ls_old = self.policy_step.old_distribution()
+        n = int(flat.shape[0])
+        if int(mu_old.shape[0]) != n:
+            raise OlyError(f"{type(self).__name__}: old_distribution() holds {int(mu_old.shape[0])} rows, the batch {n}")
+        if self._iter_ws is None or self._iter_ws[0] < n:
+            self._iter_ws = (n, eng.iter_log_ws(n))
+        r_env = r_env if r_env.dtype == torch.float64 else r_env.to(torch.float32)
+        last = last if last.dtype in (torch.bool, torch.uint8) else last != 0
+        vals = eng.iter_log(flat, v_target.to(torch.float32).contiguous(), mu_old, ls_old, pol.log_sigma,
+                            self.critic.packed, pol.packed, r_env.contiguous(), r.to(torch.float32).contiguous(),
+                            last.contiguous(), self.standardizer.colstats, self._iter_ws[1]).cpu().numpy()
+        log = {name: float(vals[i]) for i, name in enumerate(ITER_LOG_NAMES)}
+        for name in ITER_LOG_NAMES:
+            self.sw.add_scalar(name, log[name], self.iter // 3)
+        return log
 
 
 class PairedDemonstrations:
@@ -764,6 +829,14 @@ class DeviceTRPO:
                        n_epochs_line_search=int(n_epochs_line_search), accept_rule=accept_rule)
         self._ws = None
         self.last = None
+
+    def old_distribution(self):
+        """old_pol_dist of the last call (gail_TRPO.py:132-133) as (mu_old [n,act], log_sigma_old [act]): views into
+        the step's workspace, valid until the next call; mu_old at the statistics it was computed with."""
+        if self._ws is None or self.last is None:
+            raise OlyError("DeviceTRPO.old_distribution: no step has run yet")
+        pol = self.policy
+        return self.eng.trpo_old_distribution(self._ws[1], self._ws[0], pol.in_dim, pol.out_dim)
 
     def scalars(self):
         """`last` read back to the host as a dict (one synchronisation)."""
