@@ -78,6 +78,7 @@ struct oly_ctx {
   unsigned discfit_attr_done = 0;  // same for the discriminator fit's row kernels (K15)
   unsigned gail_attr_done = 0;  // same for GAIL's discriminator: the forward's instantiations and the fit's row kernels (K18)
   int num_cu;
+  unsigned ilact_attr_done = 0; // same for the acting step's instantiations (K21)
 };
 
 #define OLY_FAIL(ctx, code, ...)                                \

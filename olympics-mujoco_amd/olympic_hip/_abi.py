@@ -216,6 +216,13 @@ OLY_EPISODE_STATS, OLY_ITER_LOG_SCALARS = 8, 8
 ITER_LOG_TAGS = ("EpTrueRewMean", "EpRewMean", "EpLenMean", "vf_loss", "entropy", "kl")
 
 
+class ILAct(C.Structure):
+    """oly_il_act_args (K21): one acting step (statistics update, mean network, Gaussian sample, controls)."""
+    _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("act_dim", C.c_int32), ("update_stats", C.c_int32), ("x", vp),
+                ("colstats", vp), ("packed", vp), ("log_sigma", vp), ("eps", vp), ("action", vp), ("mu", vp), ("ctrl", vp),
+                ("out_flags", C.c_int32), ("pad", C.c_int32)]
+
+
 class TRPOStep(C.Structure):
     """oly_trpo_step_args (K17): one TRPO policy step, or the gradient / FVP pieces."""
     _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32),
@@ -339,6 +346,7 @@ SIGNATURES = {
     "oly_episode_stats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]),
     "oly_iter_log_ws_floats": (C.c_int64, [C.c_int]),
     "oly_iter_log": (C.c_int, [vp, C.POINTER(IterLog), vp]),
+    "oly_il_act": (C.c_int, [vp, C.POINTER(ILAct), vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

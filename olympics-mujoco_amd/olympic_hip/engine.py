@@ -1283,6 +1283,63 @@ class Engine:
         self.ctx.call("oly_iter_log", C.byref(f), self._s())
         return out
 
+    # -------------------------------------------------------------- K21 (one acting step) / K5
+    def il_ctrl(self, action, ctrl_f64=False, out=None):
+        """oly_il_ctrl: action [N,n_act] f32 -> ctrl [N,nu] (f32, or f64), un-normalised, clamped, actuator order."""
+        sp = self.il_spec
+        if sp is None:
+            raise OlyError("il_ctrl before il_configure")
+        if not isinstance(action, torch.Tensor) or action.dim() != 2:
+            raise OlyError("il_ctrl: action is a [N,n_act] tensor")
+        N = int(action.shape[0])
+        _req(action, "action", (N, sp.n_act), torch.float32, self.device)
+        cd = torch.float64 if ctrl_f64 else torch.float32
+        out = _req(out if out is not None else self._new((N, sp.nu), cd), "ctrl", (N, sp.nu), cd, self.device)
+        self.ctx.call("oly_il_ctrl", N, ptr(action), ptr(out), _abi.OUT_CTRL_F64 if ctrl_f64 else 0, self._s())
+        return out
+
+    def il_act(self, x, packed, log_sigma, colstats, eps=None, update_stats=True, want_mu=False, want_ctrl=False,
+               ctrl_f64=False, out=None):
+        """oly_il_act: one acting step on x [n,in] f32.  colstats [3,in] f64 takes the rows first (update_stats), the mean
+        network (packed, ilmlp_pack's stream) runs on the statistics after that, action = mu + exp(log_sigma) eps (eps
+        [n,act] f32, None: action = mu) and, with want_ctrl, ctrl [n,nu] = il_ctrl(action) from the configured model.
+        Returns dict(action, mu or None, ctrl or None); `out` may supply the buffers.  No synchronisation."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(log_sigma, torch.Tensor) or log_sigma.dim() != 1:
+            raise OlyError("il_act: x [n,in] and log_sigma [act] must be tensors")
+        n, D = (int(v) for v in x.shape)
+        A = int(log_sigma.shape[0])
+        if n < 1:
+            raise OlyError(f"il_act: n={n} rows (n >= 1)")
+        npk = int(lib().oly_ilmlp_packed_floats(D, 512, 256, A))
+        if npk < 0:
+            raise OlyError(f"il_act: unsupported shape in={D} act={A} (in <= 64, act <= 32)")
+        _req(x, "x", (n, D), f32, dv)
+        _req(packed, "packed", (npk,), f32, dv)
+        _req(log_sigma, "log_sigma", (A,), f32, dv)
+        _req(colstats, "colstats", (3, D), f64, dv)
+        _req(eps, "eps", (n, A), f32, dv, optional=True)
+        nu = 0
+        if want_ctrl:
+            sp = self.il_spec
+            if sp is None:
+                raise OlyError("il_act: want_ctrl before il_configure")
+            if int(sp.n_act) != A:
+                raise OlyError(f"il_act: want_ctrl for {A} actions, the configured model has n_act={sp.n_act}")
+            nu = int(sp.nu)
+        out = out or {}
+        cd = f64 if ctrl_f64 else f32
+        action = self._out(out, "action", (n, A), f32)
+        mu = self._out(out, "mu", (n, A), f32) if want_mu else None
+        ctrl = self._out(out, "ctrl", (n, nu), cd) if want_ctrl else None
+        f = _abi.ILAct(n=n, in_dim=D, act_dim=A, update_stats=int(bool(update_stats)), x=x.data_ptr(),
+                       colstats=colstats.data_ptr(), packed=packed.data_ptr(), log_sigma=log_sigma.data_ptr(),
+                       eps=ptr(eps), action=action.data_ptr(), mu=ptr(mu), ctrl=ptr(ctrl),
+                       out_flags=_abi.OUT_CTRL_F64 if (want_ctrl and ctrl_f64) else 0, pad=0)
+        self.ctx.call("oly_il_act", C.byref(f), self._s())
+        return dict(action=action, mu=mu, ctrl=ctrl)
+
     def trpo_old_distribution(self, ws, n, in_dim, out_dim, hidden=(512, 256)):
         """Views (no copy) of the old distribution the last trpo_step on `ws` left in it: (mu_old [n,out] f32,
         log_sigma_old [out] f32), gail_TRPO.py:132-133."""

@@ -282,10 +282,17 @@ class VecLocoEnv:
         return self._obs
 
     # ----- step
-    def step(self, actions):
+    def step(self, actions, ctrl=None):
+        """ctrl [N,nu]: the control vector of `actions` when the caller already has it (DeviceGaussianPolicy.act forms
+        it with the action): a physics that needs controls then takes it as given and the pre-pass below is skipped."""
         actions = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.num_envs, self.spec.n_act).contiguous()
-        ctrl = None
-        if getattr(self.physics, "needs_ctrl", False):      # un-normalised, clamped, actuator-ordered
+        needs = getattr(self.physics, "needs_ctrl", False)
+        if ctrl is not None and needs:
+            if tuple(ctrl.shape) != (self.num_envs, self.spec.nu):
+                raise OlyError(f"step: ctrl has shape {tuple(ctrl.shape)}, expected {(self.num_envs, self.spec.nu)}")
+        else:
+            ctrl = None
+        if needs and ctrl is None:                          # un-normalised, clamped, actuator-ordered
             pre = self.eng.il_step(self.physics.qpos.unsqueeze(0).contiguous(),
                                    self.physics.qvel.unsqueeze(0).contiguous(), actions.unsqueeze(0),
                                    self._prev.clone(), grf_mean=self._grf_mean(True), want_fall_code=False)

@@ -13,6 +13,8 @@
                                                              oly_trpo_step) on a DeviceGaussianPolicy
   the iteration's diagnostics (_logging_sw, :163, 251-272) -> VAILAgent(iteration_log=True) (K20, oly_iter_log);
                                                              compute_J / compute_episodes_length: episode_stats
+  acting in the collection loop (core.learn / evaluate)   -> DeviceGaussianPolicy.act (K21, oly_il_act); the loop
+                                                             itself is il_core.ILCore
 
 The critic shares the policy's running Standardizer (trpo_standardizer, utils.py:123); every evaluation and every
 fit minibatch adds its rows to it, as Standardizer.forward does (networks.py:68-81).
@@ -765,6 +767,26 @@ class DeviceGaussianPolicy:
         mu = self.predict(x)
         eps = torch.randn(mu.shape, dtype=torch.float32, device=mu.device, generator=generator)
         return mu + torch.exp(self.log_sigma) * eps
+
+    @torch.no_grad()
+    def act(self, obs, generator=None, eps=None, deterministic=False, ctrl=False):
+        """draw_action for the collection loop in one oly_il_act call (K21): the statistics take obs's rows, mu(obs) on
+        the statistics after that, action = mu + exp(log_sigma) eps and, with ctrl=True, the engine's configured
+        model's clamped control vector of that action.  eps None: drawn as draw_action draws it (the same generator
+        state gives the same noise); deterministic=True: action = mu, nothing is drawn.  Returns (action [n,act],
+        ctrl [n,nu] or None)."""
+        x = obs.reshape(-1, self.in_dim).to(torch.float32).contiguous()
+        st = self.stand
+        if getattr(st, "_fresh", False):     # the running sums start from zero; the call adds to them in place
+            st.colstats.zero_()
+            st._fresh = False
+        if deterministic:
+            eps = None
+        elif eps is None:
+            eps = torch.randn((int(x.shape[0]), self.out_dim), dtype=torch.float32, device=x.device, generator=generator)
+        log_sigma = self.theta[self.theta.numel() - self.out_dim:]      # the log_sigma property's view, without the others
+        o = self.eng.il_act(x, self.packed, log_sigma, st.colstats, eps=eps, update_stats=True, want_ctrl=bool(ctrl))
+        return o["action"], o["ctrl"]
 
     @torch.no_grad()
     def log_prob(self, obs, act):
