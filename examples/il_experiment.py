@@ -4,7 +4,8 @@
     for epoch: core.learn(n_steps, n_steps_per_fit); core.evaluate(n_episodes) -> Eval_R / Eval_J / Eval_L
 
 Collection acts through DeviceGaussianPolicy.act (K21: statistics update, mean network, Gaussian sample and the control
-vector in one call), resets every environment whose episode ended, and hands separate state / next_state blocks to
+vector in one call), resets every environment whose episode ended (one launch, K22: VecLocoEnv.reset_where; --host-reset
+selects the former host-driven reset with its flag read-back per step), and hands separate state / next_state blocks to
 GAILAgent.fit or VAILAgent.fit (K12 / K18, K6 + K7, K16, K17, K15 / K18, K19 / K20).  The networks and hyperparameters
 are those of examples/gail_fit.py (--algo gail) and examples/vail_fit.py (--algo vail) with --policy device and
 --disc-fit device.  The physics is the kinematic stand-in; checkpointing (BestAgentSaver) is not part of this loop.
@@ -63,6 +64,8 @@ def main():
     ap.add_argument("--eval_episodes", type=int, default=50)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--horizon", type=int, default=0, help="replace the environment's horizon (0: keep the spec's 1000)")
+    ap.add_argument("--host-reset", action="store_true",
+                    help="reset ended episodes from the host (one read-back per vec step) instead of one launch (K22)")
     ap.add_argument("--log", action="store_true", help="print the agent's own diagnostics (K19 / K20) as well")
     args = ap.parse_args()
     torch.manual_seed(0)
@@ -72,7 +75,7 @@ def main():
         vec.spec.horizon = vec.info.horizon = args.horizon
     gen = torch.Generator(device="cuda").manual_seed(0)
     agent, policy = build_agent(args.algo, env, args.log)
-    core = ILCore(agent, vec, policy, generator=gen)
+    core = ILCore(agent, vec, policy, generator=gen, device_reset=False if args.host_reset else None)
     sw = PrintingWriter()
     for epoch in range(args.epochs):
         outs = core.learn(n_steps=args.steps_per_fit * args.fits_per_epoch, n_steps_per_fit=args.steps_per_fit)

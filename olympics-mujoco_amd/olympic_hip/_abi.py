@@ -223,6 +223,13 @@ class ILAct(C.Structure):
                 ("out_flags", C.c_int32), ("pad", C.c_int32)]
 
 
+class ILReset(C.Structure):
+    """oly_il_reset_args (K22): the reset of the environments whose episode ended, in one launch."""
+    _fields_ = [("n", C.c_int32), ("out_flags", C.c_int32), ("mask", vp), ("traj_no", vp), ("step", vp), ("cur_traj", vp),
+                ("cur_step", vp), ("origin", vp), ("sample", vp), ("qpos", vp), ("qvel", vp), ("qpos_slot", vp),
+                ("qvel_slot", vp), ("obs_in", vp), ("obs_out", vp), ("prev", vp), ("episode_steps", vp)]
+
+
 class TRPOStep(C.Structure):
     """oly_trpo_step_args (K17): one TRPO policy step, or the gradient / FVP pieces."""
     _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32),
@@ -347,6 +354,7 @@ SIGNATURES = {
     "oly_iter_log_ws_floats": (C.c_int64, [C.c_int]),
     "oly_iter_log": (C.c_int, [vp, C.POINTER(IterLog), vp]),
     "oly_il_act": (C.c_int, [vp, C.POINTER(ILAct), vp]),
+    "oly_il_reset_where": (C.c_int, [vp, C.POINTER(ILReset), vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

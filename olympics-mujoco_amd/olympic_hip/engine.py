@@ -1340,6 +1340,107 @@ class Engine:
         self.ctx.call("oly_il_act", C.byref(f), self._s())
         return dict(action=action, mu=mu, ctrl=ctrl)
 
+    # -------------------------------------------------------------- K22 (reset the ended episodes on the device)
+    def il_reset_tables(self):
+        """The inverse address tables of the configured spec as device int32 tensors, cached per spec: (qpos_slot [nq],
+        qvel_slot [nv]) with slot[address] = the spec slot whose qpos_adr / qvel_adr is that address, or -1."""
+        sp = self.il_spec
+        if sp is None:
+            raise OlyError("il_reset_where before il_configure")
+        cached = getattr(self, "_il_reset_tabs", None)
+        if cached is None or cached[0] is not sp:
+            tabs = []
+            for adr, size in ((sp.qpos_adr, sp.nq), (sp.qvel_adr, sp.nv)):
+                inv = np.full(int(size), -1, np.int32)
+                inv[np.asarray(adr, np.int64)] = np.arange(len(adr), dtype=np.int32)
+                tabs.append(torch.as_tensor(inv).to(self.device))
+            cached = self._il_reset_tabs = (sp, tabs[0], tabs[1])
+        return cached[1], cached[2]
+
+    def il_reset_where(self, mask, qpos, qvel, obs_in, obs_out, prev, episode_steps, traj_no=None, step=None, cur_traj=None,
+                       cur_step=None, origin=None, sample=None):
+        """oly_il_reset_where: reset the environments with mask[n] set (mask [N] bool or uint8, None: all) in one launch.
+        qpos [N,nq] / qvel [N,nv] f64, prev [N] f64, episode_steps [N] i32 and, with traj_no / step [N] i32, cur_traj /
+        cur_step [N] i32, origin [N,2] f64, sample [N,n_keys] f64 are updated in place; obs_out [N,n_obs] (f32 or f64, the
+        type of obs_in) takes the created observation of the reset rows and obs_in's rows elsewhere (obs_out may be
+        obs_in).  traj_no None: the state rows are zeroed.  Returns obs_out.  No synchronisation."""
+        if not isinstance(qpos, torch.Tensor) or qpos.dim() != 2:
+            raise OlyError("il_reset_where: qpos is a [N,nq] tensor")
+        N = int(qpos.shape[0])
+        with_traj = traj_no is not None
+        launch = self.il_reset_where_prepare(N, prev, episode_steps, *((cur_traj, cur_step, origin, sample) if with_traj
+                                                                       else ()), with_traj=with_traj)
+        self._il_reset_check(N, mask, qpos, qvel, obs_in, obs_out, traj_no, step)
+        return launch(mask, qpos, qvel, obs_in, obs_out, traj_no, step)
+
+    def _il_reset_check(self, N, mask, qpos, qvel, obs_in, obs_out, traj_no, step):
+        """The per-call tensors of il_reset_where."""
+        sp, dv = self.il_spec, self.device
+        if mask is not None and isinstance(mask, torch.Tensor) and mask.dtype not in (torch.bool, torch.uint8):
+            raise OlyError(f"mask: dtype {mask.dtype}, expected torch.bool or torch.uint8")
+        _req(mask, "mask", (N,), mask.dtype if isinstance(mask, torch.Tensor) else torch.bool, dv, optional=True)
+        _req(qpos, "qpos", (N, sp.nq), torch.float64, dv)
+        _req(qvel, "qvel", (N, sp.nv), torch.float64, dv)
+        if not isinstance(obs_in, torch.Tensor) or obs_in.dtype not in (torch.float32, torch.float64):
+            raise OlyError("obs_in: expected a float32 or float64 tensor")
+        _req(obs_in, "obs_in", (N, sp.n_obs), obs_in.dtype, dv)
+        _req(obs_out, "obs_out", (N, sp.n_obs), obs_in.dtype, dv)
+        if traj_no is not None:
+            _req(traj_no, "traj_no", (N,), torch.int32, dv)
+            _req(step, "step", (N,), torch.int32, dv)
+
+    def il_reset_where_prepare(self, N, prev, episode_steps, cur_traj=None, cur_step=None, origin=None, sample=None,
+                               with_traj=False):
+        """Validate once the buffers a vec environment keeps for its lifetime and return
+        launch(mask, qpos, qvel, obs_in, obs_out, traj_no, step) -> obs_out, which re-points the argument block and
+        launches oly_il_reset_where.  The launch validates NOTHING about its seven tensors (the per-step regime: that is
+        the caller's contract, Engine._il_reset_check is the check); it refuses to run after the engine was configured
+        with another spec or another trajectory table."""
+        from ._ffi import check, lib
+        sp = self.il_spec
+        if sp is None:
+            raise OlyError("il_reset_where before il_configure")
+        N, dv = int(N), self.device
+        i32, f64 = torch.int32, torch.float64
+        _req(prev, "prev", (N,), f64, dv, optional=sp.reward_type == _abi.REWARD_NONE)
+        _req(episode_steps, "episode_steps", (N,), i32, dv)
+        shape = self.traj_shape
+        if with_traj:
+            if shape is None:
+                raise OlyError("il_reset_where: traj_no given before traj_upload")
+            K = shape[0]
+            if K < sp.n_pos + sp.n_vel:
+                raise OlyError(f"il_reset_where: the uploaded table has {K} keys, the model needs {sp.n_pos + sp.n_vel}")
+            _req(cur_traj, "cur_traj", (N,), i32, dv)
+            _req(cur_step, "cur_step", (N,), i32, dv)
+            _req(origin, "origin", (N, 2), f64, dv)
+            _req(sample, "sample", (N, K), f64, dv)
+        qs, vs = self.il_reset_tables()
+        f = _abi.ILReset(n=N, out_flags=0, prev=ptr(prev), episode_steps=ptr(episode_steps), qpos_slot=ptr(qs),
+                         qvel_slot=ptr(vs))
+        if with_traj:
+            f.cur_traj, f.cur_step, f.origin, f.sample = (t.data_ptr() for t in (cur_traj, cur_step, origin, sample))
+        fn, h, ref = lib().oly_il_reset_where, self.ctx.handle, C.byref(f)
+        keep = (prev, episode_steps, cur_traj, cur_step, origin, sample, qs, vs, f)     # alive with the closure
+        f64_flag = _abi.OUT_OBS_F64
+
+        def launch(mask, qpos, qvel, obs_in, obs_out, traj_no=None, step=None):
+            if self.il_spec is not sp or self.traj_shape != shape:
+                raise OlyError("il_reset_where: the engine was configured again after this launch was prepared")
+            if (traj_no is not None) != with_traj:
+                raise OlyError("il_reset_where: prepared " + ("with" if with_traj else "without") + " trajectory indices")
+            f.mask = None if mask is None else mask.data_ptr()
+            f.qpos, f.qvel, f.obs_in, f.obs_out = qpos.data_ptr(), qvel.data_ptr(), obs_in.data_ptr(), obs_out.data_ptr()
+            f.out_flags = f64_flag if obs_in.dtype == f64 else 0
+            if with_traj:
+                f.traj_no, f.step = traj_no.data_ptr(), step.data_ptr()
+            rc = fn(h, ref, self._s())
+            if rc:
+                check(h, rc, "oly_il_reset_where")
+            return obs_out
+        launch.keep = keep
+        return launch
+
     def trpo_old_distribution(self, ws, n, in_dim, out_dim, hidden=(512, 256)):
         """Views (no copy) of the old distribution the last trpo_step on `ws` left in it: (mu_old [n,out] f32,
         log_sigma_old [out] f32), gail_TRPO.py:132-133."""

@@ -83,6 +83,9 @@ class KinematicPhysics:
     nothing.  Used by play_trajectory_from_velocity and as the default stand-in."""
 
     needs_ctrl = False   # a MuJoCo-backed batcher sets this and consumes ctrl in step()
+    # qpos / qvel are [N,nq] / [N,nv] float64 device tensors that a kernel may rewrite in place row by row
+    # (VecLocoEnv.reset_where); a backend whose state lives on the host (mjData) does not set this
+    device_state = True
 
     def __init__(self, spec, num_envs, device):
         self.qpos = torch.zeros((num_envs, spec.nq), dtype=torch.float64, device=device)
@@ -141,6 +144,8 @@ class VecLocoEnv:
     step(actions [N,n_act]) -> (obs [N,n_obs], reward [N], absorbing [N] bool, info) with
     per-env semantics equal to the reference's single-env step."""
 
+    _DRAW_AHEAD = 64     # reset_where draws the environment's own random indices for this many calls at once
+
     def __init__(self, spec, num_envs, device=0, engine=None, trajectory=None, physics=None,
                  random_start=True, init_step_no=None, obs_f64=False, seed=None):
         from .engine import Engine
@@ -156,6 +161,8 @@ class VecLocoEnv:
         self.trajectories = trajectory
         self._random_start, self._init_step_no = random_start, init_step_no
         self._rng = np.random.default_rng(seed)
+        self._seed, self._dev_gen, self._fixed_idx, self._zero_idx = seed, None, None, None   # reset_where's draws
+        self._drawn, self._rw_launch, self._rw_state = {}, None, (None, None)
         N = self.num_envs
         self._prev = torch.zeros(N, dtype=torch.float64, device=self.device)
         self._obs = None
@@ -166,6 +173,7 @@ class VecLocoEnv:
             self._cur_step = torch.zeros(N, dtype=torch.int32, device=self.device)
             self._origin = torch.zeros((N, 2), dtype=torch.float64, device=self.device)
             self._sample = torch.zeros((N, len(trajectory.keys)), dtype=torch.float64, device=self.device)
+        self.eng.il_reset_tables()                   # uploaded once here, so that reset_where never copies
         self._qadr = torch.as_tensor(spec.qpos_adr.astype(np.int64), device=self.device)
         self._vadr = torch.as_tensor(spec.qvel_adr.astype(np.int64), device=self.device)
         self.info = SimpleNamespace(
@@ -280,6 +288,102 @@ class VecLocoEnv:
         self._prev = new_prev.contiguous()
         self._obs = o["obs"][0]
         return self._obs
+
+    # ----- reset of the ended episodes on the device (K22): no read-back, one launch
+    def _reset_indices(self, generator):
+        """(traj_no, step) [N] int32 on the device for every environment, by reset()'s three cases; the random ones from
+        torch's device generator."""
+        N, dev = self.num_envs, self.device
+        if self._init_step_no is not None and self._random_start:
+            raise ValueError("Either use a random start or set an initial step, not both.")
+        L, J = self.trajectories.trajectory_length, self.trajectories.number_of_trajectories
+        own = generator is None
+        if own and self._dev_gen is None:
+            self._dev_gen = torch.Generator(device=dev)
+            if self._seed is not None:
+                self._dev_gen.manual_seed(int(self._seed))
+
+        def draw(which, hi):
+            if not own:
+                return torch.randint(0, int(hi), (N,), dtype=torch.int32, device=dev, generator=generator)
+            # the environment's own stream is drawn for _DRAW_AHEAD resets at once: two launches per that many steps
+            block, i = self._drawn.get(which, (None, self._DRAW_AHEAD))
+            if i == self._DRAW_AHEAD:
+                block, i = torch.randint(0, int(hi), (self._DRAW_AHEAD, N), dtype=torch.int32, device=dev,
+                                         generator=self._dev_gen), 0
+            self._drawn[which] = (block, i + 1)
+            return block[i]
+        if self._random_start:
+            return draw("traj", J), draw("step", L)
+        if self._init_step_no:
+            assert self._init_step_no <= L * J
+            if self._fixed_idx is None:
+                self._fixed_idx = (torch.full((N,), int(self._init_step_no / L), dtype=torch.int32, device=dev),
+                                   torch.full((N,), int(self._init_step_no % L), dtype=torch.int32, device=dev))
+            return self._fixed_idx
+        if self._zero_idx is None:
+            self._zero_idx = torch.zeros(N, dtype=torch.int32, device=dev)
+        return draw("traj", J), self._zero_idx
+
+    def reset_where(self, mask, traj_no=None, step=None, generator=None):
+        """reset(env_mask=mask) without the host: ONE launch (oly_il_reset_where) resets the environments whose mask
+        entry is set (mask [N] bool or uint8 on the device; None: all) and returns the observations [N,n_obs] as a NEW
+        tensor: the created observation of the reset rows, the rows of the last observation elsewhere.  The tensor that
+        step() or reset() returned last is not modified.  Nothing is read back, no boolean-mask indexing, no .any().
+
+        traj_no / step [N] int32 on the device give the trajectory cursors (used only where the mask is set, clamped to
+        the table); indices not supplied are drawn ON THE DEVICE for all N environments by reset()'s three cases
+        (random_start: uniform [0,J) x [0,L); init_step_no: the fixed pair; otherwise a uniform trajectory and step 0).
+        The random stream is torch's device generator - `generator`, or the environment's own device generator seeded
+        with `seed` - NOT the numpy generator of reset(): the distribution is the same, the sequence is not.
+
+        _cur_traj, _cur_step, _origin, _sample, _prev, episode_steps and the physics' qpos / qvel are updated in place,
+        which the physics must allow by declaring `device_state = True`.  Unlike reset(env_mask=), the rows that are
+        not reset keep their observation to the bit, the ground-force columns included.  The sticky contact-overflow
+        flags are not read here (raise_if_contact_overflow() and the full reset() do).  reset(obs=...) has no device
+        twin."""
+        if not getattr(self.physics, "device_state", False):
+            raise OlyError(f"reset_where: {type(self.physics).__name__} does not declare device_state = True (its qpos / "
+                           "qvel must be device tensors a kernel may rewrite in place); use reset(env_mask=)")
+        from .engine import _req
+        N, dev = self.num_envs, self.device
+        od = torch.float64 if self.obs_f64 else torch.float32
+        with_traj = self.trajectories is not None
+        if not with_traj:
+            if self._random_start:
+                raise ValueError("Random start not possible without trajectory data.")
+            if self._init_step_no is not None:
+                raise ValueError("Setting an initial step is not possible without trajectory data.")
+            if traj_no is not None or step is not None:
+                raise OlyError("reset_where: traj_no / step given without trajectory data")
+        else:
+            if traj_no is None or step is None:
+                tn, st = self._reset_indices(generator)
+                traj_no = _req(traj_no, "traj_no", (N,), torch.int32, dev) if traj_no is not None else tn
+                step = _req(step, "step", (N,), torch.int32, dev) if step is not None else st
+            else:
+                _req(traj_no, "traj_no", (N,), torch.int32, dev)
+                _req(step, "step", (N,), torch.int32, dev)
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+                raise OlyError("reset_where: mask is a [N] torch.bool or torch.uint8 tensor on the device, or None")
+            _req(mask, "mask", (N,), mask.dtype, dev)
+        qpos, qvel = self.physics.qpos, self.physics.qvel
+        if qpos is not self._rw_state[0] or qvel is not self._rw_state[1]:       # a physics may hand out new views
+            _req(qpos, "physics.qpos", (N, self.spec.nq), torch.float64, dev)
+            _req(qvel, "physics.qvel", (N, self.spec.nv), torch.float64, dev)
+            self._rw_state = (qpos, qvel)
+        obs_in = self._obs
+        if obs_in is None or obs_in.dtype != od:
+            obs_in = torch.zeros((N, self.spec.n_obs), dtype=od, device=dev)
+        out = torch.empty((N, self.spec.n_obs), dtype=od, device=dev)
+        if self._rw_launch is None or self._rw_launch.prev is not self._prev:
+            args = (self._cur_traj, self._cur_step, self._origin, self._sample) if with_traj else ()
+            self._rw_launch = self.eng.il_reset_where_prepare(N, self._prev, self.episode_steps, *args, with_traj=with_traj)
+            self._rw_launch.prev = self._prev
+        self._rw_launch(mask, qpos, qvel, obs_in, out, traj_no, step)
+        self._obs = out
+        return out
 
     # ----- step
     def step(self, actions, ctrl=None):

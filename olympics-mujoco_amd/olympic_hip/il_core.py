@@ -16,7 +16,8 @@ from ._ffi import OlyError
 class ILCore:
     """Core(agent, mdp) for a vec environment.
 
-    The core touches only: env.num_envs, env.reset(env_mask=None) -> obs [N,D], env.step(actions, ctrl=None) ->
+    The core touches only: env.num_envs, env.reset(env_mask=None) -> obs [N,D], env.reset_where(mask) -> obs [N,D]
+    (a new tensor; device path only), env.step(actions, ctrl=None) ->
     (obs, reward, absorbing, info) with info["last"], env.info.horizon / .gamma; policy.act(obs, generator=, ctrl=) ->
     (action, ctrl or None); agent.fit(dataset, generator=); episode_stats(reward
     [T,N], last [T,N], gamma) -> [8] as il_agent.episode_stats (the default, on the environment's engine).
@@ -28,11 +29,19 @@ class ILCore:
         runs its n_episodes one after the other in one environment;
       * environments past their quota keep stepping until the slowest one is done (their rows do not count), so they
         still add rows to the policy's running statistics, which the reference's single environment would not.
-    One small device-to-host read per step asks whether any episode ended (the reset is host-driven); with host
-    physics every step synchronises anyway."""
+    device_reset selects how the ended episodes are reset.  True: env.reset_where(last) on every step, ONE launch (K22)
+    that resets the environments whose flag is set; the host never reads the flags and runs ahead of the device.  False:
+    one small device-to-host read per step asks whether any episode ended and env.reset(env_mask=last) is driven from
+    the host.  None (default): the device path when the environment has reset_where and its physics declares
+    device_state, the host path otherwise (with host physics every step synchronises anyway)."""
 
-    def __init__(self, agent, env, policy, generator=None, episode_stats=None):
+    def __init__(self, agent, env, policy, generator=None, episode_stats=None, device_reset=None):
         self.agent, self.env, self.policy, self.generator = agent, env, policy, generator
+        able = hasattr(env, "reset_where") and bool(getattr(getattr(env, "physics", None), "device_state", False))
+        if device_reset and not able:
+            raise OlyError("ILCore: device_reset=True needs an environment with reset_where(mask) whose physics declares "
+                           "device_state = True")
+        self.device_reset = able if device_reset is None else bool(device_reset)
         if episode_stats is None:
             from .il_agent import episode_stats as _es
             eng = env.eng
@@ -50,6 +59,9 @@ class ILCore:
         action, ctrl = self.policy.act(obs, generator=self.generator, ctrl=needs_ctrl)
         nobs, reward, absorbing, info = self.env.step(action, ctrl=ctrl)
         last = info["last"]
+        if self.device_reset:           # one launch, nothing read back
+            cur = self.env.reset_where(last)
+            return action, reward, absorbing, last, nobs, cur
         cur = nobs
         if bool(last.any()):            # the one read-back per step
             cur = self.env.reset(env_mask=last)
