@@ -57,11 +57,9 @@ inline const char* pair_error(const oly_disc_pair* pr, int Ds) {
 // P, result scaled by 2^n in two exact steps.  Within 1 ulp of exp over the whole float range (checked
 // against fp64 exp by tests/test_oracle_golden.py), the error class of torch's own float32 exp.
 __device__ __forceinline__ float pow2i(int e) { return __int_as_float((e + 127) << 23); }
-__device__ __forceinline__ float exp32(float x) {
-  if (x != x) return x;
-  if (x > 88.72283935546875f) return __int_as_float(0x7f800000);
-  if (x < -103.97208404541016f) return 0.f;
-  const float n = rintf(x * 1.4426950408889634f);
+// the reduction and the polynomial: n = rint(x log2 e) and e^(x - n ln2), which exp32 and tanh32 scale by 2^n
+__device__ __forceinline__ float exp_reduced(float x, float& n) {
+  n = rintf(x * 1.4426950408889634f);
   float r = fmaf(n, -0.693145751953125f, x);
   r = fmaf(n, -1.428606765330187045e-06f, r);
   float u = 0.000198527617612853646278381f;
@@ -70,7 +68,14 @@ __device__ __forceinline__ float exp32(float x) {
   u = fmaf(u, r, 0.0416664853692054748535156f);
   u = fmaf(u, r, 0.166666671633720397949219f);
   u = fmaf(u, r, 0.5f);
-  u = 1.0f + fmaf(r * r, u, r);
+  return 1.0f + fmaf(r * r, u, r);
+}
+__device__ __forceinline__ float exp32(float x) {
+  if (x != x) return x;
+  if (x > 88.72283935546875f) return __int_as_float(0x7f800000);
+  if (x < -103.97208404541016f) return 0.f;
+  float n;
+  const float u = exp_reduced(x, n);
   const int q = (int)n, q1 = q >> 1;
   return (u * pow2i(q1)) * pow2i(q - q1);
 }
@@ -102,17 +107,8 @@ __device__ __forceinline__ float tanh32(float x) {
   u = fmaf(u, s, 2.0f / 15.0f);
   u = fmaf(u, s, -1.0f / 3.0f);
   const float small = fmaf(x * s, u, x);
-  const float t = 2.0f * fminf(ax, 9.02f);
-  const float n = rintf(t * 1.4426950408889634f);
-  float r = fmaf(n, -0.693145751953125f, t);
-  r = fmaf(n, -1.428606765330187045e-06f, r);
-  float e = 0.000198527617612853646278381f;
-  e = fmaf(e, r, 0.00139304355252534151077271f);
-  e = fmaf(e, r, 0.00833336077630519866943359f);
-  e = fmaf(e, r, 0.0416664853692054748535156f);
-  e = fmaf(e, r, 0.166666671633720397949219f);
-  e = fmaf(e, r, 0.5f);
-  e = (1.0f + fmaf(r * r, e, r)) * pow2i((int)n);          // n in [0, 27]
+  float n;
+  const float e = exp_reduced(2.0f * fminf(ax, 9.02f), n) * pow2i((int)n);          // n in [0, 27]
   const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
   return ax >= 0.25f ? copysignf(big, x) : small;
 }

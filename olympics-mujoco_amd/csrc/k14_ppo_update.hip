@@ -34,6 +34,7 @@
 // difference is summation order (tolerance in tests/test_gpu_update.py).
 #include <cstdlib>
 
+#include "fit_common.h"
 #include "oly_common.h"
 #include "mlp_tiles.h"
 
@@ -1048,14 +1049,15 @@ extern "C" int oly_ppo_adam_step(oly_ctx* ctx, const oly_ppo_adam* a, oly_stream
     if (k.net[n].blocks > ADAM_MAX_BLOCKS) OLY_FAIL(ctx, OLY_ERANGE, "oly_ppo_adam_step: network too large");
   }
   k.sumsq = a->ws;
-  // the step-dependent scalars in fp64 on the host (torch's non-capturable Adam forms them as python floats)
-  const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step), bc2 = 1.0 - pow((double)a->beta2, (double)a->step);
+  // the step-dependent scalars in fp64 on the host (torch's non-capturable Adam forms them as python floats): the bias
+  // corrections are the fits' (fit_common.h); 1 - beta is formed in fp64 here, in float there
+  const oly_fit::AdamK sc = oly_fit::adam_scalars(a->beta1, a->beta2, a->eps, a->lr, a->step);
   k.w1 = (float)(1.0 - (double)a->beta1);
   k.beta2 = a->beta2;
   k.w2 = (float)(1.0 - (double)a->beta2);
   k.eps = a->eps;
-  k.neg_step = (float)(-((double)a->lr / bc1));
-  k.bc2_sqrt = (float)sqrt(bc2);
+  k.neg_step = sc.neg_step;
+  k.bc2_sqrt = sc.bc2_sqrt;
   k.max_norm = a->max_grad_norm;
   if (!a->norm_ready) {       // the finishing launch of oly_ppo_update_grads leaves the same partials (gnorm_ws)
     const int wa = (k.net[0].blocks + 3) / 4, wc = (k.net[1].blocks + 3) / 4;

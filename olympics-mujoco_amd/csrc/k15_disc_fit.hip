@@ -17,7 +17,8 @@
 //                           streams.  Workgroup 0 adds the loss partials, steps beta and writes the per-minibatch
 //                           outputs and colstats += minibatch b; workgroups 1 .. 16 sum minibatch b+1's rows into the
 //                           statistics partials launch A of b+1 reads.
-// Every reduction has a fixed order and there are no atomics: two runs give identical bits.
+// Every reduction has a fixed order and there are no atomics: two runs give identical bits.  What this fit shares with
+// K16 and K18 (Adam, the statistics fold, the weights kernel's tail, the epoch driver's host side) is in fit_common.h.
 //
 // oly_disc_fit_epoch_pair is the same epoch on a paired input (oly_disc_pair: (s, s') with use_next_states, (s, a) with
 // actions; VariationalNet.forward, networks.py:258-278): launch A gathers perm rows from both sources, standardises the
@@ -27,6 +28,7 @@
 #include <cstdlib>
 
 #include "disc_common.h"
+#include "fit_common.h"
 #include "mlp_tiles.h"
 #include "oly_common.h"
 
@@ -39,12 +41,17 @@ using oly_disc::H1;
 using oly_disc::H2;
 using oly_disc::MAX_IN;
 using oly_disc::ZD;
+using oly_fit::adam1;
+using oly_fit::NSP;
+using oly_fit::pt_index;
+using oly_fit::row_at;
+using oly_fit::stats_slice;
+using oly_fit::THREADS;
 using oly_mlp::act16_index;
 using oly_mlp::f32x4;
 using oly_mlp::layer_tiles16;
 
-constexpr int THREADS = 256, MAX_BATCH = 4096;
-constexpr int NSP = 16;          // slices of the statistics partials (fixed: their sum order does not depend on a grid)
+constexpr int MAX_BATCH = 4096;
 
 // flat parameters, oly_disc_pack's argument order
 struct ParamL {
@@ -104,16 +111,7 @@ __device__ __forceinline__ size_t p16_index(size_t base, int groups, int n, int 
   const int lane = (n & 15) | ((k & 3) << 4), q = (k >> 2) & 3;
   return base + ((size_t)((n >> 4) * groups + (k >> 4)) * 64 + lane) * 4 + q;
 }
-// The B operand of the data gradient dX = dY W (a sum over the layer's OUTPUT index n, N outputs):
-//   T[tile][group g][lane][q] = W[n = 16 g + 4 q + (lane >> 4)][k = 16 tile + (lane & 15)]
-__device__ __forceinline__ size_t pt_index(int N, int n, int k) {
-  const int lane = (k & 15) | ((n & 3) << 4), q = (n >> 2) & 3;
-  return ((size_t)((k >> 4) * (N / 16) + (n >> 4)) * 64 + lane) * 4 + q;
-}
-
-struct AdamK {
-  float w1, beta2, w2, eps, neg_step, bc2_sqrt, wd;
-};
+// W1T, WmuT and WlvT are B operands of the data gradients dX = dY W (pt_index, fit_common.h)
 
 struct FitArgs {
   int in_dim, n_rows, n_plcy;
@@ -126,41 +124,14 @@ struct FitArgs {
   double* colstats;
   float *param, *m, *v, *packed, *ws, *beta;
   float info_c, lr_beta;
-  AdamK ad;
+  oly_fit::AdamK ad;
+  float wd;                  // weight_decay
   double *loss_out, *bce_out, *kl_out;   // + b, or NULL
   float* beta_out;
   DiscLayout L;
   ParamL P;
   WsL W;
 };
-
-__device__ __forceinline__ int row_at(const FitArgs& a, long pos) {
-  const int i = a.perm[pos];
-  return i < 0 ? 0 : i >= a.n_rows ? a.n_rows - 1 : i;     // memory safety only: perm is a permutation of [0, n)
-}
-
-// Statistics partial `s` of the minibatch at perm[off .. off + R): its rows split into NSP slices; in each, four
-// row-strided chains (rows g, g + 4, ...) added in order g.  Every thread of the workgroup calls it.
-__device__ void stats_slice(const FitArgs& a, long off, int R, int s, double* part) {
-  const int tid = threadIdx.x, k = tid & (MAX_IN - 1), grp = tid >> 6;
-  const int per = (R + NSP - 1) / NSP, r0 = s * per, r1 = min(R, r0 + per);
-  double sum = 0.0, ss = 0.0;
-  if (k < a.ds || (k < a.in_dim && a.std2))
-    for (int r = r0 + grp; r < r1; r += 4) {
-      const size_t row = row_at(a, off + r);
-      const double v = k < a.ds ? a.x[row * a.ds + k] : a.x2[row * a.stride2 + (k - a.ds)];
-      sum += v;
-      ss += v * v;
-    }
-  part[grp * MAX_IN + k] = sum;
-  part[(4 + grp) * MAX_IN + k] = ss;
-  __syncthreads();
-  if (tid < a.in_dim) {
-    double* out = reinterpret_cast<double*>(a.ws + a.W.statp) + (size_t)s * 2 * MAX_IN;
-    out[tid] = ((part[tid] + part[MAX_IN + tid]) + part[2 * MAX_IN + tid]) + part[3 * MAX_IN + tid];
-    out[MAX_IN + tid] = ((part[4 * MAX_IN + tid] + part[5 * MAX_IN + tid]) + part[6 * MAX_IN + tid]) + part[7 * MAX_IN + tid];
-  }
-}
 
 // grid PRO_BLOCKS: the transposed streams from param (grid-stride) and, workgroups 0 .. NSP-1, minibatch 0's partials
 constexpr int PRO_BLOCKS = 64;
@@ -436,21 +407,6 @@ __global__ __launch_bounds__(THREADS) void fitd_rows_kernel(FitArgs a) {
 // k-tile 0 of each layer also steps the layer's bias.
 __host__ __device__ inline int weight_tiles(int in_dim) { return 16 * ((in_dim + 15) / 16) + 128 + 64 + 64 + 8; }
 
-// torch.optim.Adam.step (amsgrad off) on one element, float32 in K16's order; weight_decay as L2 on the gradient
-__device__ __forceinline__ float adam1(const FitArgs& a, size_t i, float g) {
-  const AdamK& k = a.ad;
-  float p = a.param[i], m = a.m[i], v = a.v[i];
-  if (k.wd != 0.f) g = fmaf(k.wd, p, g);
-  m = m + (g - m) * k.w1;
-  v = v * k.beta2 + (k.w2 * g) * g;
-  a.m[i] = m;
-  a.v[i] = v;
-  const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-  p = p + k.neg_step * (m / denom);
-  a.param[i] = p;
-  return p;
-}
-
 constexpr int RB_UNROLL = 8;
 __global__ __launch_bounds__(THREADS) void fitd_weights_kernel(FitArgs a) {
   __shared__ float red[4 * 256];
@@ -537,29 +493,14 @@ __global__ __launch_bounds__(THREADS) void fitd_weights_kernel(FitArgs a) {
       }
     }
     if (kt == 0 && tid < 16 && n0 + tid < N) {   // the bias: the column sums of delta, lane groups then waves in order
-      float gb = 0.f;
-      for (int w = 0; w < 4; ++w) {
-        const float s = ((bred[w * 64 + tid] + bred[w * 64 + 16 + tid]) + bred[w * 64 + 32 + tid]) + bred[w * 64 + 48 + tid];
-        gb = w == 0 ? s : gb + s;
-      }
+      const float gb = oly_fit::bias_colsum(bred, tid);
       const size_t pb = layer == 0 ? Pl.b0 : layer == 1 ? Pl.b1 : layer == 2 ? Pl.bmu : layer == 3 ? Pl.blv : Pl.bd;
       const size_t kb = layer == 0 ? L.b0 : layer == 1 ? L.b1 : layer == 2 ? L.bmu : layer == 3 ? L.blv : L.bd;
       a.packed[kb + n0 + tid] = adam1(a, pb + n0 + tid, gb);
     }
   }
   if (blockIdx.x == 0) {   // ---- VDBLoss's value and beta's dual update; colstats += minibatch b
-    const int nt_a = (R + 15) / 16;
-    const double* lp = reinterpret_cast<const double*>(a.ws + W.lossp);
-    dred[tid] = tid < nt_a ? lp[2 * tid] : 0.0;
-    dred[THREADS + tid] = tid < nt_a ? lp[2 * tid + 1] : 0.0;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {    // a fixed tree: the same order on every run
-      if (tid < s) {
-        dred[tid] += dred[tid + s];
-        dred[THREADS + tid] += dred[THREADS + tid + s];
-      }
-      __syncthreads();
-    }
+    oly_fit::loss_tree((R + 15) / 16, reinterpret_cast<const double*>(a.ws + W.lossp), dred);
     if (tid == 0) {
       const double bce = dred[0] / R, kl = dred[THREADS] / R;
       const float beta = a.beta[0];
@@ -572,39 +513,12 @@ __global__ __launch_bounds__(THREADS) void fitd_weights_kernel(FitArgs a) {
       if (a.kl_out) a.kl_out[0] = kl;
       if (a.beta_out) a.beta_out[0] = nb;
     }
-    if (tid < a.ds) {
-      const double* d = reinterpret_cast<const double*>(a.ws + W.delta);
-      const int ds = a.ds;
-      double cnt = a.colstats[tid] + (double)R;
-      double sum = a.colstats[ds + tid] + d[tid];
-      double sq = a.colstats[2 * ds + tid] + d[MAX_IN + tid];
-      if (a.std2) {       // the minibatch's next states, taken in after its states
-        cnt += (double)R;
-        sum += d[ds + tid];
-        sq += d[MAX_IN + ds + tid];
-      }
-      a.colstats[tid] = cnt;
-      a.colstats[ds + tid] = sum;
-      a.colstats[2 * ds + tid] = sq;
-    }
+    oly_fit::colstats_add(a, R);
   } else if (blockIdx.x <= NSP && a.Rn > 0) {
     stats_slice(a, a.off_next, a.Rn, blockIdx.x - 1, dred);
   }
 }
 
-AdamK adam_scalars(const oly_disc_fit* f, long step) {
-  // the step-dependent scalars in fp64 as torch's default Adam forms them (as oly_ppo_adam_step)
-  const double bc1 = 1.0 - pow((double)f->beta1, (double)step), bc2 = 1.0 - pow((double)f->beta2, (double)step);
-  AdamK k;
-  k.w1 = 1.0f - f->beta1;
-  k.beta2 = f->beta2;
-  k.w2 = 1.0f - f->beta2;
-  k.eps = f->adam_eps;
-  k.neg_step = (float)(-((double)f->lr / bc1));
-  k.bc2_sqrt = (float)sqrt(bc2);
-  k.wd = f->weight_decay;
-  return k;
-}
 }  // namespace
 
 extern "C" int64_t oly_disc_fit_ws_floats(int batch, int in_dim) {
@@ -626,36 +540,20 @@ extern "C" int oly_disc_fit_epoch_pair(oly_ctx* ctx, const oly_disc_fit* f, cons
                                        int n_rows, int batch, oly_stream stream) {
   if (!ctx) return OLY_EINVAL;
   if (!f || !perm) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch: NULL argument");
-  if (pair) {
-    const char* why = f->in_dim - pair->d2 <= 0 ? "d2 leaves the first part no column"
-                                                : oly_disc::pair_error(pair, f->in_dim - pair->d2);
-    if (!why && pair->mask2) why = "the fit takes the second part already gathered (mask2 NULL)";
-    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch_pair: %s (in_dim %d, d2 %d)", why, f->in_dim, pair->d2);
-  }
-  if (n_rows < 0 || oly_disc_fit_ws_floats(batch, f->in_dim) < 0)
-    OLY_FAIL(ctx, OLY_ERANGE, "oly_disc_fit_epoch: supported: 0 < batch <= %d, 0 < in_dim <= %d (got n %d, batch %d, in %d)",
-             MAX_BATCH, MAX_IN, n_rows, batch, f->in_dim);
-  if (f->n_plcy < 0 || f->n_plcy > n_rows)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch: n_plcy %d outside [0, %d]", f->n_plcy, n_rows);
+  const char* const name = "oly_disc_fit_epoch";
+  int rc = oly_fit::refuse_shape(ctx, name, pair, f->in_dim, oly_disc_fit_ws_floats(batch, f->in_dim) >= 0, OLY_ERANGE, MAX_BATCH,
+                                 n_rows, batch, f->n_plcy);
+  if (rc != OLY_OK) return rc;
   if (!f->x || !f->eps || !f->colstats || !f->param || !f->exp_avg || !f->exp_avg_sq || !f->packed || !f->beta || !f->ws)
     OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch: NULL pointer in the argument block");
   const WsL W = ws_layout(batch);
-  if (f->ws_floats < (int64_t)W.total || (reinterpret_cast<uintptr_t>(f->ws) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(f->packed) & 15) != 0)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch: ws (%ld floats) and packed must be 16-byte aligned", (long)W.total);
   const int nb = (n_rows + batch - 1) / batch;
-  if (f->step < 0 || (long)f->step + nb > 0x7fffffffL) OLY_FAIL(ctx, OLY_EINVAL, "oly_disc_fit_epoch: bad step");
+  rc = oly_fit::refuse_buffers(ctx, name, f->ws_floats, W.total, f->ws, f->packed, f->step, nb);
+  if (rc != OLY_OK) return rc;
   if (nb == 0) return OLY_OK;
   const int in_dim = f->in_dim;
   FitArgs a{};
-  a.in_dim = in_dim;
-  a.ds = in_dim - (pair ? pair->d2 : 0);
-  if (pair) {
-    a.d2 = pair->d2;
-    a.std2 = pair->standardise != 0;
-    a.stride2 = pair->stride2;
-    a.x2 = pair->x2;
-  }
+  oly_fit::set_pair_cols(a, in_dim, pair);
   a.n_rows = n_rows;
   a.n_plcy = f->n_plcy;
   a.perm = perm;
@@ -671,12 +569,13 @@ extern "C" int oly_disc_fit_epoch_pair(oly_ctx* ctx, const oly_disc_fit* f, cons
   a.beta = f->beta;
   a.info_c = f->info_constraint;
   a.lr_beta = f->lr_beta;
+  a.wd = f->weight_decay;
   a.L = disc_layout(in_dim);
   a.P = param_layout(in_dim);
   a.W = W;
   const float* p = f->param;
   const ParamL& P = a.P;
-  int rc = oly_disc_pack(ctx, in_dim, H1, H2, ZD, p + P.w0, p + P.b0, p + P.w1, p + P.b1, p + P.wmu, p + P.bmu,
+  rc = oly_disc_pack(ctx, in_dim, H1, H2, ZD, p + P.w0, p + P.b0, p + P.w1, p + P.b1, p + P.wmu, p + P.bmu,
                          p + P.wlv, p + P.blv, p + P.wd, p + P.bd, f->packed, stream);
   if (rc != OLY_OK) return rc;
   const unsigned bit = in_dim <= 32 ? 1u : 2u;
@@ -685,15 +584,11 @@ extern "C" int oly_disc_fit_epoch_pair(oly_ctx* ctx, const oly_disc_fit* f, cons
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
     ctx->discfit_attr_done |= bit;
   }
-  a.R = min(batch, n_rows);
-  a.off = 0;
+  oly_fit::set_minibatch(a, 0, nb, n_rows, batch);
   hipLaunchKernelGGL(fitd_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   for (int b = 0; b < nb; ++b) {
-    a.off = (long)b * batch;
-    a.R = min(batch, n_rows - b * batch);
-    a.off_next = a.off + a.R;
-    a.Rn = b + 1 < nb ? min(batch, n_rows - (b + 1) * batch) : 0;
-    a.ad = adam_scalars(f, (long)f->step + b + 1);
+    oly_fit::set_minibatch(a, b, nb, n_rows, batch);
+    a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->adam_eps, f->lr, (long)f->step + b + 1);
     a.loss_out = f->loss_out ? f->loss_out + b : nullptr;
     a.bce_out = f->bce_out ? f->bce_out + b : nullptr;
     a.kl_out = f->kl_out ? f->kl_out + b : nullptr;

@@ -16,14 +16,18 @@
 // runs the same chains for layers 1 and 2 on the vector ALU (fmaf, k ascending) and the output layer as one chain over
 // k < 256; gradients are fma chains over the minibatch rows in ascending order, dH1 is the sum of 16 partial chains
 // (16 layer-2 units each) added in slice order.  Every reduction has a fixed order: two runs give identical bits.
+// Adam's scalars and the clamp of a perm entry are the ones K15 and K18 use (fit_common.h).
 #include <cstdlib>
 
+#include "fit_common.h"
 #include "ilmlp_common.h"
 #include "mlp_tiles.h"
 #include "oly_common.h"
 
 namespace {
 using namespace oly_ilmlp;
+using oly_fit::AdamK;
+using oly_fit::row_at;
 
 __global__ void ilmlp_pack_kernel(int in_dim, int out_dim, const float* __restrict__ w1, const float* __restrict__ b1,
                                   const float* __restrict__ w2, const float* __restrict__ b2,
@@ -96,15 +100,11 @@ constexpr size_t WS_DELTA = 0, WS_G3 = 256, WS_H1 = 768, WS_H2 = WS_H1 + (size_t
                  WS_DH1 = WS_H2 + (size_t)MAX_BATCH * H2, WS_XS = WS_DH1 + (size_t)NS2 * MAX_BATCH * H1,
                  WS_TOTAL = WS_XS + (size_t)2 * MAX_BATCH * IN_MAX;
 
-struct AdamK {
-  float w1, beta2, w2, eps, neg_step, bc2_sqrt;
-};
-
 struct FitArgs {
-  int n, in_dim;
+  int n_rows, in_dim;
   int r_prev, r_cur;        // rows of minibatch b-1 / b (0: none)
   int par_prev, par_cur;    // parity of b-1 / b (standardised-row buffers)
-  const int32_t* perm_cur;  // rows of minibatch b
+  const int32_t* perm;      // rows of minibatch b
   const float* x;
   const float* vt;
   double* colstats;
@@ -113,7 +113,8 @@ struct FitArgs {
   AdamK ad_prev, ad_cur;
 };
 
-// torch.optim.Adam.step (amsgrad off, no decay) on one element, float32 in K14's order (k14_ppo_update.hip adam_step_kernel)
+// torch.optim.Adam.step (amsgrad off, no decay) on one element.  Not oly_fit::adam1: this one reads param after it has
+// stored the moments, and the two orders compile to different code.
 __device__ __forceinline__ float adam1(const FitArgs& a, const AdamK& k, size_t i, float g) {
   float m = a.m[i], v = a.v[i];
   m = m + (g - m) * k.w1;
@@ -131,11 +132,6 @@ __device__ __forceinline__ void adam_store(const FitArgs& a, const AdamK& k, con
   const float p = adam1(a, k, i, g);
   a.packed[packed_of_param(L, i)] = p;
   if (keep) *keep = p;
-}
-
-__device__ __forceinline__ int row_of(const FitArgs& a, int r) {
-  const int i = a.perm_cur[r];
-  return i < 0 ? 0 : i >= a.n ? a.n - 1 : i;        // memory safety only: perm is a permutation of [0, n)
 }
 
 constexpr int XP = IN_MAX + 1;     // LDS pitch of [row][k] images
@@ -194,8 +190,9 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_l1_kernel(FitArgs a) {
 
   // ---- minibatch b: Standardizer.update_mean_std then forward (networks.py:68-81).  The rows are gathered into LDS
   // in one parallel pass; the column sums are four row-strided partial chains (rows g, g + 4, ...) added in order g.
+  // (oly_fit::fold_chains' order; that one stores the sums, these stay in registers.)
   const int R = a.r_cur;
-  if (tid < R) rows_s[tid] = row_of(a, tid);
+  if (tid < R) rows_s[tid] = row_at(a, tid);
   __syncthreads();
   for (int e = tid; e < R * in_dim; e += FIT_THREADS) {
     const int r = e / in_dim, k = e - r * in_dim;
@@ -315,7 +312,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_bwd_kernel(FitArgs a) {
   double d2 = 0.0;
   if (tid < R) {
     y += a.param[L.b3];
-    const float d = y - a.vt[row_of(a, tid)];
+    const float d = y - a.vt[row_at(a, tid)];
     dys[tid] = (2.0f / (float)R) * d;     // mse_loss backward: (2 / N) (y - t) * grad_out
     d2 = (double)d * (double)d;
   }
@@ -389,18 +386,6 @@ bool ilmlp_shape_ok(int in_dim, int h1, int h2, int out_dim) {
   return in_dim > 0 && in_dim <= IN_MAX && h1 == H1 && h2 == H2 && out_dim > 0 && out_dim <= OUT_MAX;
 }
 
-AdamK adam_scalars(const oly_il_critic_fit* f, long step) {
-  // the step-dependent scalars in fp64 as torch's default Adam forms them (as oly_ppo_adam_step)
-  const double bc1 = 1.0 - pow((double)f->beta1, (double)step), bc2 = 1.0 - pow((double)f->beta2, (double)step);
-  AdamK k;
-  k.w1 = 1.0f - f->beta1;
-  k.beta2 = f->beta2;
-  k.w2 = 1.0f - f->beta2;
-  k.eps = f->eps;
-  k.neg_step = (float)(-((double)f->lr / bc1));
-  k.bc2_sqrt = (float)sqrt(bc2);
-  return k;
-}
 }  // namespace
 
 extern "C" int64_t oly_ilmlp_packed_floats(int in_dim, int h1, int h2, int out_dim) {
@@ -461,7 +446,7 @@ extern "C" int oly_il_critic_fit_epoch(oly_ctx* ctx, const oly_il_critic_fit* f,
   if (f->step < 0 || (long)f->step + nb > 0x7fffffffL) OLY_FAIL(ctx, OLY_EINVAL, "oly_il_critic_fit_epoch: bad step");
   if (nb == 0) return OLY_OK;
   FitArgs a{};
-  a.n = n_rows;
+  a.n_rows = n_rows;
   a.in_dim = f->in_dim;
   a.x = f->x;
   a.vt = f->v_target;
@@ -476,10 +461,10 @@ extern "C" int oly_il_critic_fit_epoch(oly_ctx* ctx, const oly_il_critic_fit* f,
     a.r_cur = b < nb ? min(batch, n_rows - b * batch) : 0;
     a.par_prev = (b + 1) & 1;
     a.par_cur = b & 1;
-    a.perm_cur = perm + (size_t)min(b, nb - 1) * batch;
+    a.perm = perm + (size_t)min(b, nb - 1) * batch;
     a.loss = f->loss_out + min(b, nb - 1);
     a.ad_prev = a.ad_cur;
-    a.ad_cur = adam_scalars(f, (long)f->step + b + 1);
+    a.ad_cur = oly_fit::adam_scalars(f->beta1, f->beta2, f->eps, f->lr, (long)f->step + b + 1);
     hipLaunchKernelGGL(fit_l1_kernel, dim3(H1 / 16), dim3(FIT_THREADS), 0, oly_s(stream), a);
     if (b == nb) break;
     hipLaunchKernelGGL(fit_l2_kernel, dim3(H2 / 16, (a.r_cur + 63) / 64), dim3(FIT_THREADS), 0, oly_s(stream), a);

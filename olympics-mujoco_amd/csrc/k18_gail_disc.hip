@@ -29,10 +29,12 @@
 //                           param, the moments, the packed stream and the transposed stream.  Workgroup 0 adds the loss
 //                           partials and writes the per-minibatch outputs and colstats += minibatch b; workgroups
 //                           1 .. 16 sum minibatch b+1's rows into the statistics partials launch A of b+1 reads.
-// Every reduction has a fixed order and there are no atomics: two runs give identical bits.
+// Every reduction has a fixed order and there are no atomics: two runs give identical bits.  What the fit shares with
+// K15 and K16 (Adam, the statistics fold, the weights kernel's tail, the epoch driver's host side) is in fit_common.h.
 #include <cstdlib>
 
 #include "disc_common.h"
+#include "fit_common.h"
 #include "ilmlp_common.h"
 #include "mlp_tiles.h"
 #include "oly_common.h"
@@ -40,9 +42,15 @@
 namespace {
 using namespace oly_ilmlp;
 using oly_disc::tanh32;
+using oly_fit::adam1;
+using oly_fit::NSP;
+using oly_fit::pt_index;
+using oly_fit::row_at;
+using oly_fit::stats_slice;
+using oly_fit::THREADS;
+static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
 
-constexpr int THREADS = 256, MAX_BATCH = 4096;
-constexpr int NSP = 16;          // slices of the statistics partials (fixed: their sum order does not depend on a grid)
+constexpr int MAX_BATCH = 4096;
 
 // workspace (floats), BP = batch rounded up to 16 rows; [BP][W] arrays in row quads, element (row, col) at
 // ((row / 4) W + col) 4 + row % 4:
@@ -69,17 +77,7 @@ __host__ __device__ inline WsL ws_layout(int batch) {
   return W;
 }
 
-// The B operand of the data gradient dH1 = dZ2 W2 (a sum over W2's OUTPUT index n, N = 256 outputs):
-//   T[tile][group g][lane][q] = W[n = 16 g + 4 q + (lane >> 4)][k = 16 tile + (lane & 15)]
-__device__ __forceinline__ size_t pt_index(int N, int n, int k) {
-  const int lane = (k & 15) | ((n & 3) << 4), q = (n >> 2) & 3;
-  return ((size_t)((k >> 4) * (N / 16) + (n >> 4)) * 64 + lane) * 4 + q;
-}
-
-struct AdamK {
-  float w1, beta2, w2, eps, neg_step, bc2_sqrt, wd;
-};
-
+// W2T is the B operand of the data gradient dH1 = dZ2 W2 (pt_index, fit_common.h; N = 256 outputs)
 struct FitArgs {
   int in_dim, n_rows, n_plcy;
   int ds, d2, std2, stride2; // x [n_rows, ds] | x2 [n_rows, stride2]'s first d2 columns (d2 = in_dim - ds, 0: none);
@@ -91,39 +89,12 @@ struct FitArgs {
   double* colstats;
   float *param, *m, *v, *packed, *ws;
   float entcoeff;
-  AdamK ad;
+  oly_fit::AdamK ad;
+  float wd;                  // weight_decay
   double *loss_out, *bce_out, *ent_out;   // + b, or NULL
   ParamLayout P;
   WsL W;
 };
-
-__device__ __forceinline__ int row_at(const FitArgs& a, long pos) {
-  const int i = a.perm[pos];
-  return i < 0 ? 0 : i >= a.n_rows ? a.n_rows - 1 : i;     // memory safety only: perm is a permutation of [0, n)
-}
-
-// Statistics partial `s` of the minibatch at perm[off .. off + R), as K15's: its rows split into NSP slices; in each,
-// four row-strided chains (rows g, g + 4, ...) added in order g.  Every thread of the workgroup calls it.
-__device__ void stats_slice(const FitArgs& a, long off, int R, int s, double* part) {
-  const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
-  const int per = (R + NSP - 1) / NSP, r0 = s * per, r1 = min(R, r0 + per);
-  double sum = 0.0, ss = 0.0;
-  if (k < a.ds || (k < a.in_dim && a.std2))
-    for (int r = r0 + grp; r < r1; r += 4) {
-      const size_t row = row_at(a, off + r);
-      const double v = k < a.ds ? a.x[row * a.ds + k] : a.x2[row * a.stride2 + (k - a.ds)];
-      sum += v;
-      ss += v * v;
-    }
-  part[grp * IN_MAX + k] = sum;
-  part[(4 + grp) * IN_MAX + k] = ss;
-  __syncthreads();
-  if (tid < a.in_dim) {
-    double* out = reinterpret_cast<double*>(a.ws + a.W.statp) + (size_t)s * 2 * IN_MAX;
-    out[tid] = ((part[tid] + part[IN_MAX + tid]) + part[2 * IN_MAX + tid]) + part[3 * IN_MAX + tid];
-    out[IN_MAX + tid] = ((part[4 * IN_MAX + tid] + part[5 * IN_MAX + tid]) + part[6 * IN_MAX + tid]) + part[7 * IN_MAX + tid];
-  }
-}
 
 // grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. NSP-1, minibatch 0's partials
 constexpr int PRO_BLOCKS = 64;
@@ -351,21 +322,6 @@ __global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(7, 8))
 // the layer's bias.
 __host__ __device__ inline int weight_tiles(int in_dim) { return 32 * ((in_dim + 15) / 16) + 512 + 16; }
 
-// torch.optim.Adam.step (amsgrad off) on one element, float32 in K15's order; weight_decay as L2 on the gradient
-__device__ __forceinline__ float adam1(const FitArgs& a, size_t i, float g) {
-  const AdamK& k = a.ad;
-  float p = a.param[i], m = a.m[i], v = a.v[i];
-  if (k.wd != 0.f) g = fmaf(k.wd, p, g);
-  m = m + (g - m) * k.w1;
-  v = v * k.beta2 + (k.w2 * g) * g;
-  a.m[i] = m;
-  a.v[i] = v;
-  const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-  p = p + k.neg_step * (m / denom);
-  a.param[i] = p;
-  return p;
-}
-
 constexpr int STEP_UNROLL = 4;      // 16-row steps whose loads are issued together
 __global__ __launch_bounds__(THREADS) void gfit_weights_kernel(FitArgs a) {
   __shared__ float red[4 * 256];
@@ -436,67 +392,24 @@ __global__ __launch_bounds__(THREADS) void gfit_weights_kernel(FitArgs a) {
       }
     }
     if (kt == 0 && tid < 16 && n0 + tid < N) {   // the bias: the column sums of delta, lane groups then waves in order
-      float gb = 0.f;
-      for (int w = 0; w < 4; ++w) {
-        const float s = ((bred[w * 64 + tid] + bred[w * 64 + 16 + tid]) + bred[w * 64 + 32 + tid]) + bred[w * 64 + 48 + tid];
-        gb = w == 0 ? s : gb + s;
-      }
+      const float gb = oly_fit::bias_colsum(bred, tid);
       const size_t pb = layer == 0 ? PL.b1 : layer == 1 ? PL.b2 : PL.b3;
       const size_t kb = layer == 0 ? P_B1 : layer == 1 ? P_B2 : P_B3;
       a.packed[kb + n0 + tid] = adam1(a, pb + n0 + tid, gb);
     }
   }
   if (blockIdx.x == 0) {   // ---- GailDiscriminatorLoss's value; colstats += minibatch b
-    const int nt_a = (R + 15) / 16;
-    const double* lp = reinterpret_cast<const double*>(a.ws + W.lossp);
-    dred[tid] = tid < nt_a ? lp[2 * tid] : 0.0;
-    dred[THREADS + tid] = tid < nt_a ? lp[2 * tid + 1] : 0.0;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {    // a fixed tree: the same order on every run
-      if (tid < s) {
-        dred[tid] += dred[tid + s];
-        dred[THREADS + tid] += dred[THREADS + tid + s];
-      }
-      __syncthreads();
-    }
+    oly_fit::loss_tree((R + 15) / 16, reinterpret_cast<const double*>(a.ws + W.lossp), dred);
     if (tid == 0) {
       const double bce = dred[0] / R, ent = dred[THREADS] / R;
       if (a.loss_out) a.loss_out[0] = bce - (double)a.entcoeff * ent;      // math.py:28-29
       if (a.bce_out) a.bce_out[0] = bce;
       if (a.ent_out) a.ent_out[0] = ent;
     }
-    if (tid < a.ds) {
-      const double* d = reinterpret_cast<const double*>(a.ws + W.delta);
-      const int ds = a.ds;
-      double cnt = a.colstats[tid] + (double)R;
-      double sum = a.colstats[ds + tid] + d[tid];
-      double sq = a.colstats[2 * ds + tid] + d[IN_MAX + tid];
-      if (a.std2) {       // the minibatch's next states, taken in after its states
-        cnt += (double)R;
-        sum += d[ds + tid];
-        sq += d[IN_MAX + ds + tid];
-      }
-      a.colstats[tid] = cnt;
-      a.colstats[ds + tid] = sum;
-      a.colstats[2 * ds + tid] = sq;
-    }
+    oly_fit::colstats_add(a, R);
   } else if (blockIdx.x <= NSP && a.Rn > 0) {
     stats_slice(a, a.off_next, a.Rn, blockIdx.x - 1, dred);
   }
-}
-
-AdamK adam_scalars(const oly_gail_disc_fit* f, long step) {
-  // the step-dependent scalars in fp64 as torch's default Adam forms them (as oly_ppo_adam_step)
-  const double bc1 = 1.0 - pow((double)f->beta1, (double)step), bc2 = 1.0 - pow((double)f->beta2, (double)step);
-  AdamK k;
-  k.w1 = 1.0f - f->beta1;
-  k.beta2 = f->beta2;
-  k.w2 = 1.0f - f->beta2;
-  k.eps = f->adam_eps;
-  k.neg_step = (float)(-((double)f->lr / bc1));
-  k.bc2_sqrt = (float)sqrt(bc2);
-  k.wd = f->weight_decay;
-  return k;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -517,14 +430,7 @@ __global__ __launch_bounds__(THREADS) void gail_stats_partial_kernel(long B, int
       ss += v * v;
     }
   }
-  part[grp * IN_MAX + k] = sum;
-  part[(4 + grp) * IN_MAX + k] = ss;
-  __syncthreads();
-  if (tid < D) {
-    double* out = part_out + (size_t)blockIdx.x * 2 * IN_MAX;
-    out[tid] = ((part[tid] + part[IN_MAX + tid]) + part[2 * IN_MAX + tid]) + part[3 * IN_MAX + tid];
-    out[IN_MAX + tid] = ((part[4 * IN_MAX + tid] + part[5 * IN_MAX + tid]) + part[6 * IN_MAX + tid]) + part[7 * IN_MAX + tid];
-  }
+  oly_fit::fold_chains(sum, ss, D, part, part_out + (size_t)blockIdx.x * 2 * IN_MAX);
 }
 
 __global__ __launch_bounds__(64) void gail_stats_finish_kernel(long B, int D, const double* __restrict__ part,
@@ -711,35 +617,20 @@ extern "C" int oly_gail_disc_fit_epoch_pair(oly_ctx* ctx, const oly_gail_disc_fi
                                             const int32_t* perm, int n_rows, int batch, oly_stream stream) {
   if (!ctx) return OLY_EINVAL;
   if (!f || !perm) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: NULL argument");
-  if (pair) {
-    const char* why = f->in_dim - pair->d2 <= 0 ? "d2 leaves the first part no column" : oly_disc::pair_error(pair, f->in_dim - pair->d2);
-    if (!why && pair->mask2) why = "the fit takes the second part already gathered (mask2 NULL)";
-    if (why) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch_pair: %s (in_dim %d, d2 %d)", why, f->in_dim, pair->d2);
-  }
-  if (n_rows < 0 || oly_gail_disc_fit_ws_floats(batch, f->in_dim) < 0)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: supported: 0 < batch <= %d, 0 < in_dim <= %d (got n %d, batch %d, in %d)",
-             MAX_BATCH, IN_MAX, n_rows, batch, f->in_dim);
-  if (f->n_plcy < 0 || f->n_plcy > n_rows)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: n_plcy %d outside [0, %d]", f->n_plcy, n_rows);
+  const char* const name = "oly_gail_disc_fit_epoch";
+  int rc = oly_fit::refuse_shape(ctx, name, pair, f->in_dim, oly_gail_disc_fit_ws_floats(batch, f->in_dim) >= 0, OLY_EINVAL,
+                                 MAX_BATCH, n_rows, batch, f->n_plcy);
+  if (rc != OLY_OK) return rc;
   if (!f->x || !f->colstats || !f->param || !f->exp_avg || !f->exp_avg_sq || !f->packed || !f->ws)
     OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: NULL pointer in the argument block");
   const WsL W = ws_layout(batch);
-  if (f->ws_floats < (int64_t)W.total || (reinterpret_cast<uintptr_t>(f->ws) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(f->packed) & 15) != 0)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: ws (%ld floats) and packed must be 16-byte aligned", (long)W.total);
   const int nb = (n_rows + batch - 1) / batch;
-  if (f->step < 0 || (long)f->step + nb > 0x7fffffffL) OLY_FAIL(ctx, OLY_EINVAL, "oly_gail_disc_fit_epoch: bad step");
+  rc = oly_fit::refuse_buffers(ctx, name, f->ws_floats, W.total, f->ws, f->packed, f->step, nb);
+  if (rc != OLY_OK) return rc;
   if (nb == 0) return OLY_OK;
   const int in_dim = f->in_dim;
   FitArgs a{};
-  a.in_dim = in_dim;
-  a.ds = in_dim - (pair ? pair->d2 : 0);
-  if (pair) {
-    a.d2 = pair->d2;
-    a.std2 = pair->standardise != 0;
-    a.stride2 = pair->stride2;
-    a.x2 = pair->x2;
-  }
+  oly_fit::set_pair_cols(a, in_dim, pair);
   a.n_rows = n_rows;
   a.n_plcy = f->n_plcy;
   a.perm = perm;
@@ -752,11 +643,12 @@ extern "C" int oly_gail_disc_fit_epoch_pair(oly_ctx* ctx, const oly_gail_disc_fi
   a.packed = f->packed;
   a.ws = f->ws;
   a.entcoeff = f->entcoeff;
+  a.wd = f->weight_decay;
   a.P = param_layout(in_dim, 1);
   a.W = W;
   const float* p = f->param;
   const ParamLayout& P = a.P;
-  const int rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 1, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
+  rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 1, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
                                 stream);
   if (rc != OLY_OK) return rc;
   const unsigned bit = in_dim <= 32 ? 1u << 16 : 1u << 17;
@@ -765,15 +657,11 @@ extern "C" int oly_gail_disc_fit_epoch_pair(oly_ctx* ctx, const oly_gail_disc_fi
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
     ctx->gail_attr_done |= bit;
   }
-  a.R = min(batch, n_rows);
-  a.off = 0;
+  oly_fit::set_minibatch(a, 0, nb, n_rows, batch);
   hipLaunchKernelGGL(gfit_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   for (int b = 0; b < nb; ++b) {
-    a.off = (long)b * batch;
-    a.R = min(batch, n_rows - b * batch);
-    a.off_next = a.off + a.R;
-    a.Rn = b + 1 < nb ? min(batch, n_rows - (b + 1) * batch) : 0;
-    a.ad = adam_scalars(f, (long)f->step + b + 1);
+    oly_fit::set_minibatch(a, b, nb, n_rows, batch);
+    a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->adam_eps, f->lr, (long)f->step + b + 1);
     a.loss_out = f->loss_out ? f->loss_out + b : nullptr;
     a.bce_out = f->bce_out ? f->bce_out + b : nullptr;
     a.ent_out = f->ent_out ? f->ent_out + b : nullptr;
