@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
-"""The imitation-learning launcher's loop (examples/imitation_learning/experiment.py:51-65) on UnitreeH1 with ILCore:
+"""The imitation-learning launcher's loop (examples/imitation_learning/experiment.py:51-67) on UnitreeH1 with ILCore:
 
     for epoch: core.learn(n_steps, n_steps_per_fit); core.evaluate(n_episodes) -> Eval_R / Eval_J / Eval_L
+               agent_saver.save(core.agent, R_mean)
+    agent_saver.save_curr_best_agent()
 
 Collection acts through DeviceGaussianPolicy.act (K21: statistics update, mean network, Gaussian sample and the control
 vector in one call), resets every environment whose episode ended (one launch, K22: VecLocoEnv.reset_where; --host-reset
 selects the former host-driven reset with its flag read-back per step), and hands separate state / next_state blocks to
 GAILAgent.fit or VAILAgent.fit (K12 / K18, K6 + K7, K16, K17, K15 / K18, K19 / K20).  The networks and hyperparameters
 are those of examples/gail_fit.py (--algo gail) and examples/vail_fit.py (--algo vail) with --policy device and
---disc-fit device.  The physics is the kinematic stand-in; checkpointing (BestAgentSaver) is not part of this loop.
+--disc-fit device.  The physics is the kinematic stand-in.
+
+With --results_dir the best agent since the last write is kept by il_checkpoint.BestAgentSaver, the reference's schedule
+(--n_epochs_save, default 500 as experiment.py:25; -1: never), as agent_epoch_%d_J_%f.pt; the files hold the core as well,
+so --resume FILE continues such a run bit for bit at the epoch after the file's (same --algo, --num_envs and --horizon).
 
     python examples/il_experiment.py --algo gail --num_envs 256 --steps_per_fit 20 --fits_per_epoch 3 --eval_episodes 50
 """
@@ -24,12 +30,14 @@ from olympic_hip.gail import (DeviceStandardizer, DiscriminatorReward, GAILDiscr
                               GAILDiscriminatorReward, VariationalDiscriminator, VDBLoss)
 from olympic_hip.il_agent import (DeviceDiscriminatorTrainer, DeviceGAILDiscriminatorTrainer,  # noqa: E402
                                   DeviceGaussianPolicy, DeviceILCritic, DeviceTRPO, GAILAgent, VAILAgent)
+from olympic_hip import il_checkpoint  # noqa: E402
 from olympic_hip.il_core import ILCore  # noqa: E402
 from vail_fit import PrintingWriter, paired_inputs  # noqa: E402  (the examples beside this one)
 
 
-def build_agent(algo, env, log):
-    """(agent, policy) as examples/gail_fit.py / examples/vail_fit.py build them for --policy device --disc-fit device."""
+def build_agent(algo, env, log, sw=None):
+    """(agent, policy) as examples/gail_fit.py / examples/vail_fit.py build them for --policy device --disc-fit device.
+    log: the agent gets a writer (sw, or a PrintingWriter) and runs its diagnostics."""
     vec, eng = env.vec, env.vec.eng
     n_obs, n_act = vec.spec.n_obs, vec.spec.n_act
     mask = vec.get_kinematic_obs_mask()
@@ -39,7 +47,7 @@ def build_agent(algo, env, log):
     trpo_standardizer = DeviceStandardizer(eng, n_obs)
     critic = DeviceILCritic(eng, lins, trpo_standardizer, lr=1e-4)
     pol_lins = [torch.nn.Linear(n_obs, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, n_act)]
-    sw = PrintingWriter() if log else None
+    sw = (sw or PrintingWriter()) if log else None
     common = dict(gamma=0.99, lam=0.97, env_reward_frac=0.0, train_D_n_th_epoch=3,
                   critic_fit_params=dict(n_epochs=3, batch_size=256), sw=sw, iteration_log=log)
     if algo == "gail":       # HumanoidMuscle's confs.yaml values, as examples/gail_fit.py
@@ -67,6 +75,12 @@ def main():
     ap.add_argument("--host-reset", action="store_true",
                     help="reset ended episodes from the host (one read-back per vec step) instead of one launch (K22)")
     ap.add_argument("--log", action="store_true", help="print the agent's own diagnostics (K19 / K20) as well")
+    ap.add_argument("--results_dir", default=None, help="where BestAgentSaver writes agent_epoch_%%d_J_%%f.pt (default: nothing "
+                                                        "is written)")
+    ap.add_argument("--n_epochs_save", type=int, default=500,
+                    help="write the best agent since the last write once this many epochs have passed (-1: never)")
+    ap.add_argument("--resume", default=None, metavar="PATH",
+                    help="a file this launcher wrote: load agent and core and continue at the epoch after the file's")
     args = ap.parse_args()
     torch.manual_seed(0)
     env = LocoEnvBase.make("UnitreeH1.walk.real", num_envs=args.num_envs, seed=0)
@@ -76,8 +90,16 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(0)
     agent, policy = build_agent(args.algo, env, args.log)
     core = ILCore(agent, vec, policy, generator=gen, device_reset=False if args.host_reset else None)
+    saver = il_checkpoint.BestAgentSaver(args.results_dir, args.n_epochs_save) if args.results_dir else None
+    first = 0
+    if args.resume:
+        meta = il_checkpoint.load(args.resume, agent, core)
+        first = int(meta["epoch"]) + 1
+        print(f"resumed from {args.resume}: epoch {meta['epoch']}, J {meta['J']:.6f}; continuing at epoch {first}")
+        if saver is not None:           # the epochs before `first` belong to the run that wrote the file
+            saver.epoch_counter = saver.last_save = first
     sw = PrintingWriter()
-    for epoch in range(args.epochs):
+    for epoch in range(first, args.epochs):
         outs = core.learn(n_steps=args.steps_per_fit * args.fits_per_epoch, n_steps_per_fit=args.steps_per_fit)
         for i, out in enumerate(outs):
             loss = out["critic_loss"]
@@ -88,6 +110,14 @@ def main():
         sw.add_scalar("Eval_R-stochastic", ev["R_mean"], epoch)
         sw.add_scalar("Eval_J-stochastic", ev["J_mean"], epoch)
         sw.add_scalar("Eval_L-stochastic", ev["L"], epoch)
+        if saver is not None:           # experiment.py:65
+            path = saver.save(agent, ev["R_mean"], core=core)
+            if path:
+                print(f"epoch {epoch}: wrote {path}")
+    if saver is not None:               # experiment.py:67
+        path = saver.save_curr_best_agent()
+        if path:
+            print(f"wrote {path}")
 
 
 if __name__ == "__main__":

@@ -86,6 +86,9 @@ class KinematicPhysics:
     # qpos / qvel are [N,nq] / [N,nv] float64 device tensors that a kernel may rewrite in place row by row
     # (VecLocoEnv.reset_where); a backend whose state lives on the host (mjData) does not set this
     device_state = True
+    # A physics that carries more than qpos / qvel from step to step gives itself state_dict() / load_state_dict(d);
+    # VecLocoEnv.state_dict then includes it under "physics".  This one carries nothing else.  ReplayPhysics has none
+    # either: who resumes a replay hands the new object the rows that are left.
 
     def __init__(self, spec, num_envs, device):
         self.qpos = torch.zeros((num_envs, spec.nq), dtype=torch.float64, device=device)
@@ -478,9 +481,18 @@ class VecLocoEnv:
         if self.trajectories is not None:
             d.update(cur_traj=self._cur_traj.clone(), cur_step=self._cur_step.clone(), origin=self._origin.clone(),
                      sample=self._sample.clone())
+        # reset_where's own stream: the device generator (its state is a host byte tensor) and the blocks drawn ahead
+        # (not yet created: the seed it will be created with)
+        d["dev_gen"] = None if self._dev_gen is None else self._dev_gen.get_state().clone()
+        d["dev_seed"] = None if self._seed is None else int(self._seed)
+        d["drawn"] = {k: dict(block=b.clone(), cursor=int(i)) for k, (b, i) in self._drawn.items()}
+        if callable(getattr(self.physics, "state_dict", None)):
+            d["physics"] = self.physics.state_dict()
         return d
 
     def load_state_dict(self, d):
+        """A dict without dev_gen / drawn / physics (one stored before reset_where had a stream of its own) leaves
+        those as they are."""
         self._prev = d["prev"].to(self.device).clone()
         self.episode_steps.copy_(d["episode_steps"])
         self.physics.set_state(d["qpos"].to(self.device), d["qvel"].to(self.device))
@@ -490,6 +502,23 @@ class VecLocoEnv:
             for k, t in (("cur_traj", self._cur_traj), ("cur_step", self._cur_step), ("origin", self._origin),
                          ("sample", self._sample)):
                 t.copy_(d[k])
+        if "dev_gen" in d:
+            self._seed = d.get("dev_seed", self._seed)      # only ever read when the generator is created
+            if d["dev_gen"] is None:
+                self._dev_gen = None
+            else:
+                if self._dev_gen is None:
+                    self._dev_gen = torch.Generator(device=self.device)
+                self._dev_gen.set_state(d["dev_gen"].cpu())
+        if "drawn" in d:
+            for k, v in d["drawn"].items():
+                if tuple(v["block"].shape) != (self._DRAW_AHEAD, self.num_envs):
+                    raise OlyError(f"VecLocoEnv.load_state_dict: the drawn block {k!r} is {tuple(v['block'].shape)} in "
+                                   f"the stored state, {(self._DRAW_AHEAD, self.num_envs)} in this environment")
+            self._drawn = {k: (v["block"].to(device=self.device, dtype=torch.int32).clone(), int(v["cursor"]))
+                           for k, v in d["drawn"].items()}
+        if "physics" in d and callable(getattr(self.physics, "load_state_dict", None)):
+            self.physics.load_state_dict(d["physics"])
 
     def get_kinematic_obs_mask(self):
         return np.arange(self.spec.n_pos + self.spec.n_vel - 2)       # loco_env_base.py:886

@@ -49,6 +49,58 @@ class DeviceStandardizer:
         self.update_mean_std(xm)
         return self.eng.disc_standardize(x, mask, self.mean.contiguous(), self.std.contiguous())
 
+    # ---- checkpoint (il_checkpoint)
+    def state_dict(self):
+        return dict(dim=int(self.dim), colstats=self.colstats.clone(), fresh=bool(self._fresh))
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place: `colstats` keeps its pointer (a prepared reward step or a launch cache may hold it)."""
+        _same("DeviceStandardizer", "dim", int(d["dim"]), int(self.dim))
+        self.colstats.copy_(d["colstats"])
+        self._fresh = bool(d["fresh"])
+
+
+def _same(who, field, stored, own):
+    """A structural field of a loaded state must be the built object's."""
+    if stored != own:
+        from ._ffi import OlyError
+        raise OlyError(f"{who}.load_state_dict: {field} is {stored!r} in the stored state, {own!r} in this object")
+
+
+def _mask_list(m):
+    return None if m is None else [int(v) for v in m.detach().cpu().reshape(-1).tolist()]
+
+
+class DiscriminatorState:
+    """state_dict / load_state_dict of the two discriminator rewards: the network's parameters and the Standardizer."""
+
+    def _structure(self):
+        return dict(kind=type(self).__name__, in_dim=int(self._params()[0].shape[1]), pair=self.pair,
+                    state_mask=_mask_list(self.mask), act_mask=_mask_list(getattr(self, "mask2", None)))
+
+    def state_dict(self):
+        return dict(self._structure(), params=[p.detach().clone() for p in self._params()],
+                    standardizer=self.stand.state_dict())
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """The parameters are copied into the module's own tensors (the pointers a prepared step captured stay valid),
+        the Standardizer in place; then the packed stream is formed again so that the next reward call sees them."""
+        who = type(self).__name__
+        for k, v in self._structure().items():
+            _same(who, k, d[k], v)
+        ps = self._params()
+        _same(who, "number of parameters", len(d["params"]), len(ps))
+        for i, (p, t) in enumerate(zip(ps, d["params"])):
+            _same(who, f"shape of parameter {i}", tuple(t.shape), tuple(p.shape))
+        for p, t in zip(ps, d["params"]):
+            p.data.copy_(t)
+        self.stand.load_state_dict(d["standardizer"])
+        self.invalidate()
+        if self._packed is not None:
+            self.packed()
+
 
 class VariationalDiscriminator(nn.Module):
     """encoder -> (mu, logvar) -> z = mu + exp(logvar/2) eps -> decoder."""
@@ -122,7 +174,7 @@ class PairedInput:
             raise OlyError(f"{type(self).__name__}: {x.shape[1]} columns, the state mask reads column {self._mask_max}")
 
 
-class DiscriminatorReward(PairedInput):
+class DiscriminatorReward(PairedInput, DiscriminatorState):
     """make_discrim_reward for a batch of observations on the device.
 
     pair: what the discriminator looks at besides the states (VariationalNet.forward, networks.py:258-278;
@@ -324,7 +376,7 @@ class GAILDiscriminator(nn.Module):
         return self._linears[-1](h)
 
 
-class GAILDiscriminatorReward(PairedInput):
+class GAILDiscriminatorReward(PairedInput, DiscriminatorState):
     """make_discrim_reward (gail_TRPO.py:320-327) for GAIL's discriminator on the device (K18): the Standardizer's
     update with the masked rows, then in -> 512 -> 256 -> 1 (tanh, tanh, identity) and the reward formula in one launch,
     the state mask (prepare_discrim_inputs, :297-313) applied inside the kernel.

@@ -24,6 +24,7 @@ import torch
 
 from . import _abi
 from ._ffi import OlyError
+from .gail import _same
 
 _H1, _H2 = 512, 256
 
@@ -133,6 +134,33 @@ class DeviceILCritic:
             lin.bias.copy_(views[2 * i + 1].to(lin.bias.device))
         return self.net
 
+    # ---- checkpoint (il_checkpoint); the shared Standardizer is the agent's to store
+    def state_dict(self):
+        return dict(in_dim=self.in_dim, out_dim=self.out_dim, param=self.param.clone(), exp_avg=self.exp_avg.clone(),
+                    exp_avg_sq=self.exp_avg_sq.clone(), step=int(self.step))
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place (param, the moments and `packed` keep their pointers), then the stream is packed again."""
+        _same("DeviceILCritic", "in_dim", int(d["in_dim"]), self.in_dim)
+        _same("DeviceILCritic", "out_dim", int(d["out_dim"]), self.out_dim)
+        for k in ("param", "exp_avg", "exp_avg_sq"):
+            getattr(self, k).copy_(d[k])
+        self.step = int(d["step"])
+        self.eng.ilmlp_pack(*self._views(), packed=self.packed)
+
+
+def _moments_state(tr):
+    return dict(n_par=int(tr.exp_avg.numel()), exp_avg=tr.exp_avg.clone(), exp_avg_sq=tr.exp_avg_sq.clone(),
+                step=int(tr.step))
+
+
+def _load_moments(tr, d):
+    _same(type(tr).__name__, "n_par", int(d["n_par"]), int(tr.exp_avg.numel()))
+    tr.exp_avg.copy_(d["exp_avg"])
+    tr.exp_avg_sq.copy_(d["exp_avg_sq"])
+    tr.step = int(d["step"])
+
 
 class VAILAgent:
     """GAIL_TRPO.fit (gail_TRPO.py:105-165) for VAIL_TRPO with the critic on K16:
@@ -211,6 +239,73 @@ class VAILAgent:
     @property
     def standardizer(self):
         return self.critic.stand
+
+    # ---- checkpoint (il_checkpoint)
+    def _header(self):
+        """What a stored state must share with the agent it is loaded into (the first six), and what is kept for
+        information only."""
+        pol = getattr(self.policy_step, "policy", None)
+        ds = self.disc._structure()
+        return dict(kind="gail" if isinstance(self, GAILAgent) else "vail", in_dim=int(self.critic.in_dim),
+                    out_dim=None if pol is None else int(pol.out_dim), disc_in_dim=ds["in_dim"], pair=ds["pair"],
+                    state_mask=ds["state_mask"], gamma=float(self.post.gamma), lam=float(self.post.lam),
+                    env_reward_frac=self.frac, train_D_n_th_epoch=self.train_D_n_th_epoch,
+                    critic_fit_params={k: v for k, v in self.critic_fit_params.items()
+                                       if isinstance(v, (int, float, str, bool, type(None)))})
+
+    STRUCTURE = ("kind", "in_dim", "out_dim", "disc_in_dim", "pair", "state_mask")
+
+    def state_dict(self):
+        """Everything the agent carries from one fit to the next, as a nested dict of device clones, numbers, strings
+        and None: `iter`, the critic, the policy (when the policy step has one), the discriminator with its own
+        Standardizer, the discriminator trainer's optimiser, and the Standardizer the policy and the critic share,
+        stored once.  The optimisers' hyper-parameters, the writer and the demonstrations are not state."""
+        if not callable(getattr(self.disc_trainer, "state_dict", None)):
+            raise OlyError(f"{type(self).__name__}.state_dict: {type(self.disc_trainer).__name__} has no state_dict (the "
+                           "device trainers have)")
+        pol = getattr(self.policy_step, "policy", None)
+        d = dict(header=self._header(), iter=int(self.iter), standardizer=self.critic.stand.state_dict(),
+                 critic=self.critic.state_dict(), policy=None, policy_standardizer=None,
+                 disc=self.disc.state_dict(), disc_trainer=self.disc_trainer.state_dict())
+        if pol is not None:
+            d["policy"] = pol.state_dict()
+            if pol.stand is not self.critic.stand:
+                d["policy_standardizer"] = pol.stand.state_dict()
+        return d
+
+    def load_state_dict(self, d):
+        """Write a stored state into this agent in place.  The structure is checked before anything is written: a
+        mismatch raises OlyError naming the field and both values."""
+        name = type(self).__name__
+        own = self._header()
+        for k in self.STRUCTURE:
+            _same(name, k, d["header"].get(k), own[k])
+        pol = getattr(self.policy_step, "policy", None)
+        _same(name, "a stored policy", d["policy"] is not None, pol is not None)
+        _same(name, "a separate policy Standardizer", d["policy_standardizer"] is not None,
+              pol is not None and pol.stand is not self.critic.stand)
+        self.critic.stand.load_state_dict(d["standardizer"])
+        self.critic.load_state_dict(d["critic"])
+        if pol is not None:
+            if d["policy_standardizer"] is not None:
+                pol.stand.load_state_dict(d["policy_standardizer"])
+            pol.load_state_dict(d["policy"])
+        self.disc.load_state_dict(d["disc"])
+        self.disc_trainer.load_state_dict(d["disc_trainer"])
+        if callable(getattr(self.policy_step, "load_state_dict", None)):
+            self.policy_step.load_state_dict({})
+        self.iter = int(d["iter"])
+
+    def save(self, path, **meta):
+        """il_checkpoint.save(path, self, **meta)."""
+        from . import il_checkpoint
+        il_checkpoint.save(path, self, **meta)
+
+    def load(self, path):
+        """il_checkpoint.load(path, self): this agent, built with its demonstrations like any other, takes the file's
+        state; returns the file's meta."""
+        from . import il_checkpoint
+        return il_checkpoint.load(path, self)
 
     @staticmethod
     def _blocks(dataset):
@@ -541,6 +636,15 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
         self.loss._beta = float(self.beta)                           # the one host read-back of the call
         return (losses, logs) if log else losses
 
+    # ---- checkpoint (il_checkpoint): `param` and `beta` are scratch, refilled at the start of every fit
+    def state_dict(self):
+        return dict(_moments_state(self), beta=float(self.loss._beta))
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        _load_moments(self, d)
+        self.loss._beta = float(d["beta"])
+
 
 class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
     """_fit_discriminator (gail_TRPO.py:167-220) for GAIL on K18: DeviceDiscriminatorTrainer's semantics with GAIL's
@@ -686,6 +790,14 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
             o += k
         return (losses, logs) if log else losses
 
+    # ---- checkpoint (il_checkpoint): `param` is scratch, refilled at the start of every fit
+    def state_dict(self):
+        return _moments_state(self)
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        _load_moments(self, d)
+
 
 class GAILAgent(VAILAgent):
     """GAIL_TRPO.fit (gail_TRPO.py:105-165) for GAIL_TRPO: VAILAgent's sequence with GAIL's discriminator, i.e.
@@ -825,6 +937,18 @@ class DeviceGaussianPolicy:
             lin.bias.copy_(v[2 * i + 1].to(lin.bias.device))
         return self.net, v[6].detach().cpu().clone()
 
+    # ---- checkpoint (il_checkpoint); the shared Standardizer is the agent's to store
+    def state_dict(self):
+        return dict(in_dim=self.in_dim, out_dim=self.out_dim, theta=self.theta.clone())
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place (theta and `packed` keep their pointers), then repack()."""
+        _same("DeviceGaussianPolicy", "in_dim", int(d["in_dim"]), self.in_dim)
+        _same("DeviceGaussianPolicy", "out_dim", int(d["out_dim"]), self.out_dim)
+        self.theta.copy_(d["theta"])
+        self.repack()
+
 
 class DeviceTRPO:
     """TRPO's policy step (GAIL_TRPO.fit, gail_TRPO.py:131-149) on K17, one oly_trpo_step call, no host
@@ -864,6 +988,14 @@ class DeviceTRPO:
         """`last` read back to the host as a dict (one synchronisation)."""
         v = self.last.cpu().tolist()
         return dict(zip(self.SCALARS, v))
+
+    def state_dict(self):
+        """Nothing: the step carries no state from one call to the next."""
+        return {}
+
+    def load_state_dict(self, d):
+        """After a load no step of this run has happened: old_distribution() raises as before the first one."""
+        self.last = None
 
     @torch.no_grad()
     def __call__(self, obs, act, adv, agent=None):

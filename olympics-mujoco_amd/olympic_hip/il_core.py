@@ -20,7 +20,8 @@ class ILCore:
     (a new tensor; device path only), env.step(actions, ctrl=None) ->
     (obs, reward, absorbing, info) with info["last"], env.info.horizon / .gamma; policy.act(obs, generator=, ctrl=) ->
     (action, ctrl or None); agent.fit(dataset, generator=); episode_stats(reward
-    [T,N], last [T,N], gamma) -> [8] as il_agent.episode_stats (the default, on the environment's engine).
+    [T,N], last [T,N], gamma) -> [8] as il_agent.episode_stats (the default, on the environment's engine); for
+    state_dict / load_state_dict also env.state_dict() / env.load_state_dict(d) and env.device.
 
     Differences from the reference's Core, all consequences of stepping N environments together:
       * n_steps / n_steps_per_fit count VEC steps: every environment contributes that many samples to a fit, so N = 1
@@ -49,6 +50,43 @@ class ILCore:
         self.episode_stats = episode_stats
         self._obs = None
         self.blocks = None      # the last fit's six blocks, `last` as the environment reported it
+
+    # --------------------------------------------------------------------------------------------------- checkpoint
+    def _cuda_index(self):
+        dev = torch.device(getattr(self.env, "device", "cuda"))
+        return torch.cuda.current_device() if dev.index is None else dev.index
+
+    def state_dict(self):
+        """What the loop carries besides the agent: the observation the next learn starts from (None: it resets), the
+        environment's own state_dict and the state of the random stream the loop draws from.  With generator=None that
+        stream is the device's global one (torch.cuda.get_rng_state): a run resumed from such a state continues
+        exactly only if nobody else draws from the global generator in between."""
+        if not callable(getattr(self.env, "state_dict", None)):
+            raise OlyError(f"ILCore.state_dict: {type(self.env).__name__} has no state_dict")
+        own = self.generator is not None
+        rng = self.generator.get_state() if own else torch.cuda.get_rng_state(self._cuda_index())
+        return dict(num_envs=int(self.env.num_envs), obs=None if self._obs is None else self._obs.clone(),
+                    env=self.env.state_dict(), generator="own" if own else "global", generator_state=rng.clone())
+
+    def load_state_dict(self, d):
+        """The counterpart: the environment and the generator are written in place (the caller's torch.Generator object
+        takes the stored state), the observation is a new tensor."""
+        if int(d["num_envs"]) != int(self.env.num_envs):
+            raise OlyError(f"ILCore.load_state_dict: num_envs is {int(d['num_envs'])} in the stored state, "
+                           f"{int(self.env.num_envs)} in this core's environment")
+        kind = "own" if self.generator is not None else "global"
+        if d["generator"] != kind:
+            raise OlyError(f"ILCore.load_state_dict: generator is {d['generator']!r} in the stored state, {kind!r} in this "
+                           "core (own: a torch.Generator was passed; global: generator=None)")
+        self.env.load_state_dict(d["env"])
+        rng = d["generator_state"].cpu()
+        if kind == "own":
+            self.generator.set_state(rng)
+        else:
+            torch.cuda.set_rng_state(rng, self._cuda_index())
+        obs = d["obs"]
+        self._obs = None if obs is None else obs.to(getattr(self.env, "device", obs.device)).clone()
+        self.blocks = None
 
     # ----------------------------------------------------------------------------------------------------- stepping
     def _needs_ctrl(self):
