@@ -3,6 +3,14 @@
 (reference: examples/reinforcement_learning_ppo/a3/train_a3_walk.py).
 
     python examples/train_a3_walk.py train --num_procs 4096 --n_itr 10 --logdir ./logs_dir/
+    python examples/train_a3_walk.py train ... --checkpoint_every 100        # LOGDIR/checkpoint.pt, replaced every 100 iterations
+    python examples/train_a3_walk.py train ... --resume ./logs_dir/          # the stopped run goes on, bit for bit
+    python examples/train_a3_walk.py train ... --continued ./logs_dir/       # its weights, a new run from iteration 0
+
+--resume continues a run exactly (weights, Adam, environment, random streams, logs: olympic_hip.ppo_checkpoint) and needs the
+same command line as the run that wrote the file.  --continued has the reference's meaning (train_a3_walk.py:54-64): the
+weights and input-normalisation tables of an earlier run, a fresh optimiser, iteration 0; it reads checkpoint.pt (a file, or
+the one in a directory), never a pickled module.  Either one skips the normalisation pre-pass, as the reference does.
 
 `--num_procs` is the number of environments stepped in lock step on the GPU (the reference starts
 that many ray workers).  MuJoCo is not part of this repository: `make_physics(num_envs)` below
@@ -43,14 +51,18 @@ def run_experiment(args):
     np.random.seed(args.seed)
     policy = MLPGaussianActor(obs_dim, action_dim, fixed_std=torch.exp(torch.tensor(float(args.std_dev)))).cuda()
     critic = MLPCritic(obs_dim).cuda()
-    if args.input_norm_steps > 0:
+    if args.continued:
+        from olympic_hip import ppo_checkpoint
+        ppo_checkpoint.load_policy(args.continued, policy, critic)
+    if args.input_norm_steps > 0 and not (args.resume or args.continued):
         env = env_fn()
         mean, std = get_normalization_params(args.input_norm_steps, policy, env, 1.0)
         policy.obs_mean = torch.as_tensor(mean, dtype=torch.float32, device="cuda")
         policy.obs_std = torch.as_tensor(std, dtype=torch.float32, device="cuda")
     algo = PPO(vars(args), args.logdir)
     algo.use_graph = algo.use_graph_rollout = not args.no_graph
-    return algo.train(env_fn, policy, critic, args.n_itr, anneal_rate=args.anneal)
+    return algo.train(env_fn, policy, critic, args.n_itr, anneal_rate=args.anneal, resume=args.resume,
+                      checkpoint_every=args.checkpoint_every)
 
 
 if __name__ == "__main__":
@@ -80,5 +92,15 @@ if __name__ == "__main__":
     parser.add_argument("--mirror_coeff", default=0.4, type=float)
     parser.add_argument("--eval_freq", default=100, type=int)
     parser.add_argument("--no_graph", action="store_true", help="op-by-op PyTorch update / rollout instead of HIP graphs")
-    hist = run_experiment(parser.parse_args())
-    print("done:", len(hist), "iterations; last return", hist[-1]["ep_return"], "fps", round(hist[-1]["fps"]))
+    parser.add_argument("--continued", default=None, type=str,
+                        help="checkpoint.pt (or its directory) to take weights and normalisation tables from")
+    parser.add_argument("--resume", default=None, type=str, help="checkpoint.pt (or its directory) to continue exactly")
+    parser.add_argument("--checkpoint_every", default=None, type=int, help="write LOGDIR/checkpoint.pt every K iterations")
+    args = parser.parse_args()
+    if args.resume and args.continued:
+        raise SystemExit("--resume continues a run, --continued starts a new one from its weights: give one of them")
+    hist = run_experiment(args)
+    if hist:
+        print("done:", len(hist), "iterations; last return", hist[-1]["ep_return"], "fps", round(hist[-1]["fps"]))
+    else:
+        print("done: the checkpoint already holds iteration", args.n_itr - 1, "or later; nothing left to run")

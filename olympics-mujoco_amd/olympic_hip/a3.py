@@ -165,13 +165,38 @@ class VecA3Env:
         self.state["goal"][idx] = 0.0
 
     def state_dict(self):
-        """Task state carried between steps (phase counters, target indices, sequences, goals)."""
-        return dict(iteration_count=self.iteration_count, **{k: v.clone() for k, v in self.state.items()})
+        """Task state carried between steps (phase counters, target indices, sequences, goals), and what a training run
+        carries from one iteration to the next: the reset stream, the physics readback cursor (or the physics' own
+        state_dict where it offers one) and the device rollout's state once there is one."""
+        from .ppo_checkpoint import numpy_stream_state
+        d = dict(iteration_count=self.iteration_count, **{k: v.clone() for k, v in self.state.items()})
+        d["rs"] = numpy_stream_state(self._reset_one.rs)
+        if hasattr(self.physics, "state_dict"):
+            d["physics"] = self.physics.state_dict()
+        elif hasattr(self.physics, "k"):
+            d["physics_k"] = int(self.physics.k)
+        roll = getattr(self, "_dev_rollout", None)
+        d["device_rollout"] = None if roll is None else roll.state_dict()
+        return d
 
     def load_state_dict(self, d):
+        """In place.  A dict with the task state alone leaves the stream, the physics and the rollout as they are."""
+        from .ppo_checkpoint import set_numpy_stream
+        roll = d.get("device_rollout")
+        if roll is not None:
+            if getattr(self, "_dev_rollout", None) is None:
+                from .vecstep import A3DeviceRollout
+                self._dev_rollout = A3DeviceRollout(self, self.physics.blocks, rs=self._reset_one.rs)
+            self._dev_rollout.load_state_dict(roll)         # compares its sizes before anything is written
         self.iteration_count = d["iteration_count"]
         for k, v in self.state.items():
             v.copy_(d[k])
+        if "physics" in d and hasattr(self.physics, "load_state_dict"):
+            self.physics.load_state_dict(d["physics"])
+        elif d.get("physics_k") is not None and hasattr(self.physics, "k"):
+            self.physics.k = int(d["physics_k"])
+        if d.get("rs") is not None:
+            set_numpy_stream(self._reset_one.rs, d["rs"])
 
     @property
     def has_device_physics(self):
@@ -300,6 +325,19 @@ class StickFigureA3:
         """PPO.sample on the device (vecstep.A3DeviceRollout) when the physics readback lives there."""
         self.vec.iteration_count = self.robot.iteration_count if np.isfinite(self.robot.iteration_count) else 10 ** 9
         return self.vec.device_rollout(*args, **kw)
+
+    def state_dict(self):
+        """The wrapped VecA3Env's state, this object's own reset stream (reset_model's draws) and robot.iteration_count."""
+        from .ppo_checkpoint import numpy_stream_state
+        return dict(vec=self.vec.state_dict(), rs=numpy_stream_state(self.rs),
+                    robot_iteration_count=float(self.robot.iteration_count))
+
+    def load_state_dict(self, d):
+        from .ppo_checkpoint import set_numpy_stream
+        self.vec.load_state_dict(d["vec"])
+        it = d["robot_iteration_count"]
+        self.robot.iteration_count = it if not np.isfinite(it) or it != int(it) else int(it)
+        set_numpy_stream(self.rs, d["rs"])
 
     def _draw_init_state(self):
         """reset_model's draws, in the reference's order (StickFigureA3.py:213-228)."""

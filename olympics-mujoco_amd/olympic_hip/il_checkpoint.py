@@ -44,17 +44,39 @@ def to_host(state):
                    f"{type(state).__name__}")
 
 
-def save_state(path, agent_state, core_state=None, **meta):
-    """Write state_dicts that were taken earlier (BestAgentSaver's snapshot).  The file appears under its name only once
-    it is complete."""
-    obj = dict(format=FORMAT, version=VERSION, agent=to_host(agent_state),
-               core=None if core_state is None else to_host(core_state), meta=to_host(meta))
+def write_file(path, obj):
+    """torch.save of a nest of host values (to_host's output) under `path`: written beside it as .part and renamed, so
+    the name never shows a half-written file and a previous file of that name is replaced in one step."""
     path = os.fspath(path)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".part"
     torch.save(obj, tmp)
     os.replace(tmp, path)
     return path
+
+
+def read_file(path, fmt, version, who="il_checkpoint.load"):
+    """The content of a file written by write_file, read with weights_only=True and checked for its format name and
+    version (`who` opens the messages: ppo_checkpoint reads its files through here as well)."""
+    try:
+        obj = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
+    except pickle.UnpicklingError as e:
+        raise OlyError(f"{who}: {path} is not a checkpoint of tensors, numbers and strings: reading it "
+                       f"would unpickle an object, which is refused ({str(e).splitlines()[0]})") from None
+    if not isinstance(obj, dict) or obj.get("format") != fmt:
+        got = obj.get("format") if isinstance(obj, dict) else type(obj).__name__
+        raise OlyError(f"{who}: {path}: format is {got!r}, expected {fmt!r}")
+    if obj.get("version") != version:
+        raise OlyError(f"{who}: {path}: version is {obj.get('version')!r}, this reader takes {version!r}")
+    return obj
+
+
+def save_state(path, agent_state, core_state=None, **meta):
+    """Write state_dicts that were taken earlier (BestAgentSaver's snapshot).  The file appears under its name only once
+    it is complete."""
+    obj = dict(format=FORMAT, version=VERSION, agent=to_host(agent_state),
+               core=None if core_state is None else to_host(core_state), meta=to_host(meta))
+    return write_file(path, obj)
 
 
 def save(path, agent, core=None, **meta):
@@ -65,17 +87,7 @@ def save(path, agent, core=None, **meta):
 
 def read(path):
     """The checked content of a checkpoint file: dict(format, version, agent, core, meta), tensors on the host."""
-    try:
-        obj = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
-    except pickle.UnpicklingError as e:
-        raise OlyError(f"il_checkpoint.load: {path} is not a checkpoint of tensors, numbers and strings: reading it "
-                       f"would unpickle an object, which is refused ({str(e).splitlines()[0]})") from None
-    if not isinstance(obj, dict) or obj.get("format") != FORMAT:
-        got = obj.get("format") if isinstance(obj, dict) else type(obj).__name__
-        raise OlyError(f"il_checkpoint.load: {path}: format is {got!r}, expected {FORMAT!r}")
-    if obj.get("version") != VERSION:
-        raise OlyError(f"il_checkpoint.load: {path}: version is {obj.get('version')!r}, this reader takes {VERSION!r}")
-    return obj
+    return read_file(path, FORMAT, VERSION)
 
 
 def load(path, agent, core=None):

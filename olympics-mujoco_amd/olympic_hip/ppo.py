@@ -14,6 +14,7 @@ update_policy is the plain-torch evaluation of the same terms).  Actor / critic 
 `forward(state, deterministic, anneal)`, `distribution(obs)` and a critic `forward(obs)`).
 """
 import os
+import shutil
 import time
 from copy import deepcopy
 
@@ -460,6 +461,7 @@ class PPO:
         self.vf_coeff = 0.5
         self.target_kl = None
         self.total_steps, self.highest_reward, self.iteration_count = 0, -1, 0
+        self.curr_anneal = 1.0
         self.save_path = save_path
         os.makedirs(save_path, exist_ok=True)
         self.eval_fn = os.path.join(save_path, "eval.txt")
@@ -588,7 +590,13 @@ class PPO:
         return terms["actor"], terms["entropy"], terms["critic"], terms["kl"], mirror, terms["clipped"]
 
     # ------------------------------------------------------------------ training loop
-    def train(self, env_fn, policy, critic, n_itr, anneal_rate=1.0, verbose=True):
+    def train(self, env_fn, policy, critic, n_itr, anneal_rate=1.0, verbose=True, resume=None, checkpoint_every=None,
+              checkpoint_keep=False):
+        """The reference's training loop (ppo.py:284-477).  checkpoint_every=k: after every k-th iteration the whole run
+        goes to save_path/checkpoint.pt (ppo_checkpoint.save; checkpoint_keep also keeps checkpoint_<itr>.pt) as the last
+        action of that iteration.  resume=path: the run stored there is loaded into the fresh objects of this call and
+        iterations file's + 1 .. n_itr - 1 run, bit for bit as the uninterrupted run would have; the returned history holds
+        the iterations of this call."""
         self.old_policy = deepcopy(policy)
         self.policy, self.critic = policy, critic
         use_graph = bool(getattr(self, "use_graph", False))
@@ -610,6 +618,11 @@ class PPO:
         env = env_fn()
         from . import dist as odist
         multi_rank = odist.is_dist() and torch.distributed.get_world_size() > 1
+        if multi_rank and (resume is not None or checkpoint_every):
+            from ._ffi import OlyError
+            raise OlyError(f"PPO.train: resume / checkpoint_every are single-rank only; this process group has "
+                           f"{torch.distributed.get_world_size()} ranks (every rank holds environment and random-stream "
+                           "state of its own)")
         if multi_rank:
             # one learner, replicated: same initial weights everywhere, gradients averaged before every step;
             # the advantage statistics are already global (PPORollout).  The graph-captured update holds no
@@ -639,16 +652,39 @@ class PPO:
         device_perm = getattr(self, "device_permutation", None)
         device_perm = use_kernel if device_perm is None else bool(device_perm)
         T = max(1, self.batch_size // env.num_envs)
-        curr_anneal, start = 1.0, time.time()
+        self.curr_anneal, start = 1.0, time.time()
         history = []
-        for itr in range(n_itr):
+
+        def kernel_update():
+            """The K14 update object of this run, made when first needed (the first iteration, or a load before it)."""
+            nonlocal kupd
+            if not use_kernel:
+                from ._ffi import OlyError
+                raise OlyError("PPO: this run's update path is not the kernel one")
+            if kupd is None:
+                kupd = self.kupd = KernelUpdate(env.eng, policy, critic, self.old_policy, self.clip, self.vf_coeff,
+                                                self.mirror_coeff, obs_mirr, act_src, act_sign, lr=self.lr, eps=self.eps,
+                                                max_grad_norm=self.grad_clip)
+            return kupd
+        # what a checkpoint's header states about this run (ppo_checkpoint.header)
+        self._ensure_kernel_update = kernel_update
+        self._run = dict(update="kernel" if use_kernel else "fused" if fused else "torch", T=T,
+                         mirror=obs_mirr is not None and act_mirr is not None, device_permutation=device_perm,
+                         rollout="device" if getattr(self, "use_device_rollout", True)
+                         and getattr(env, "has_device_physics", False) else "host")
+        first = 0
+        if resume is not None:
+            from . import ppo_checkpoint
+            ppo_checkpoint.load(ppo_checkpoint.resolve(resume), self, env)
+            first = self.iteration_count + 1
+        for itr in range(first, n_itr):
             self.iteration_count = itr
             if hasattr(env, "iteration_count"):
                 env.iteration_count = itr
             t0 = time.time()
-            if self.highest_reward > (2 / 3) * self.max_traj_len and curr_anneal > 0.5:
-                curr_anneal *= anneal_rate
-            buf = self.sample_vec(env, self.policy, self.critic, T, self.max_traj_len, anneal=curr_anneal)
+            if self.highest_reward > (2 / 3) * self.max_traj_len and self.curr_anneal > 0.5:
+                self.curr_anneal *= anneal_rate
+            buf = self.sample_vec(env, self.policy, self.critic, T, self.max_traj_len, anneal=self.curr_anneal)
             returns, advantages = post.finish(buf, normalize=True)       # finish_path + (adv-mean)/(std+eps)
             sample_s = time.time() - t0
             n = buf.T * buf.N
@@ -679,11 +715,7 @@ class PPO:
             kernel = None
             if use_kernel:
                 # K14: forward + losses + backward of a minibatch in one launch; gradient clipping and Adam stay torch's
-                if kupd is None:
-                    kupd = KernelUpdate(env.eng, policy, critic, self.old_policy, self.clip, self.vf_coeff,
-                                        self.mirror_coeff, obs_mirr, act_src, act_sign, lr=self.lr, eps=self.eps,
-                                        max_grad_norm=self.grad_clip)
-                kernel = self.kupd = kupd
+                kernel = self.kupd = kernel_update()
                 kernel.begin(observations, buf.mu.reshape(n, -1) if getattr(buf, "mu", None) is not None
                              and getattr(buf, "mu_from_fused_forward", False) else None)
                 kstats = torch.zeros((self.epochs * max(n_batches, 1), 6), dtype=torch.float64, device=observations.device)
@@ -830,4 +862,11 @@ class PPO:
             if verbose:
                 print("itr {itr}: return {ep_return:.3f} len {ep_len:.1f} sampling {sample_s:.2f}s "
                       "optimizer {optim_s:.2f}s fps {fps:.0f}".format(**rec))
+            if checkpoint_every and (itr + 1) % checkpoint_every == 0:
+                from . import ppo_checkpoint
+                path = ppo_checkpoint.save(os.path.join(self.save_path, ppo_checkpoint.FILE), self, env, iteration=itr)
+                if checkpoint_keep:
+                    kept = os.path.join(self.save_path, "checkpoint_" + repr(itr) + ".pt")
+                    shutil.copyfile(path, kept + ".part")
+                    os.replace(kept + ".part", kept)
         return history

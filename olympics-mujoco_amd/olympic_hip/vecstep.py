@@ -305,6 +305,60 @@ class A3DeviceRollout:
         for t, s in zip(self._mutable(), snap):
             t.copy_(s)
 
+    # ------------------------------------------------------------------ checkpoints
+    def _named(self):
+        """The tensors a rollout leaves behind for the next one, by name: the task state, _mutable()'s own (the side list's
+        exist once a rollout has sized them, and every rollout rewinds them), the PD target and the reset-record pool."""
+        d = {f"task.{k}": self.env.state[k] for k in _abi.A3_STATE_FIELDS}
+        d.update(state_obs=self.state_obs, traj_len=self.traj_len, pool_count=self.pool_count, ctr=self.ctr,
+                 pd_target=self.pd_target, pool=self.pool)
+        if self._shape is not None:
+            d.update(side_count=self.side_count, side_t=self.side_t)
+        return d
+
+    def state_dict(self):
+        """What carries over from one rollout to the next (clones on the device): the tensors of _named(), the used part
+        of the current pinned stash with its cursors, the readback cursor of the physics, the iteration count the step
+        heights follow, and the numpy stream the reset records are drawn from.  Draws nothing."""
+        from .ppo_checkpoint import numpy_stream_state
+        used = self._stash_n * REC.itemsize
+        phys = getattr(self.env, "physics", None)
+        return dict(num_envs=self.N, pool_depth=self.depth, tensors={k: v.clone() for k, v in self._named().items()},
+                    stash=self._stash_t[self._stash_i][:used].clone(), stash_n=int(self._stash_n),
+                    stash_i=int(self._stash_i), last_total=int(self._last_total),
+                    physics_k=int(phys.k) if phys is not None and hasattr(phys, "k") else None,
+                    iteration_count=getattr(self.env, "iteration_count", None), rs=numpy_stream_state(self.rs))
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place: every tensor by copy_ (prepared launches and captured graphs hold their addresses).  Sizes are
+        compared before the first write."""
+        from .gail import _same
+        from .ppo_checkpoint import set_numpy_stream
+        _same("A3DeviceRollout", "num_envs", d["num_envs"], self.N)
+        _same("A3DeviceRollout", "pool_depth", d["pool_depth"], self.depth)
+        own = self._named()
+        rewound = ("side_count", "side_t")                  # sized by (T, max_traj_len) and reset by every rollout
+        for k, v in own.items():
+            if k in d["tensors"]:
+                if tuple(d["tensors"][k].shape) != tuple(v.shape) and k not in rewound:
+                    _same("A3DeviceRollout", f"{k}'s shape", list(d["tensors"][k].shape), list(v.shape))
+            elif k not in rewound:
+                _same("A3DeviceRollout", f"tensor {k}", None, list(v.shape))
+        torch.cuda.synchronize(self.eng.device)             # the last upload from a stash has finished
+        for k, v in own.items():
+            t = d["tensors"].get(k)
+            if t is not None and tuple(t.shape) == tuple(v.shape):
+                v.copy_(t)
+        self._stash_n, self._stash_i, self._last_total = int(d["stash_n"]), int(d["stash_i"]), int(d["last_total"])
+        self._stash_t[self._stash_i][:d["stash"].numel()].copy_(d["stash"])
+        phys = getattr(self.env, "physics", None)
+        if d["physics_k"] is not None and phys is not None and hasattr(phys, "k"):
+            phys.k = int(d["physics_k"])
+        if d["iteration_count"] is not None and hasattr(self.env, "iteration_count"):
+            self.env.iteration_count = d["iteration_count"]
+        set_numpy_stream(self.rs, d["rs"])
+
     def _finalize(self, fw, critic):
         """next_values: V(s_{t+1}) is the next row's value for an uncut step; for a cut that is not
         terminal it is the critic on the side-list row (the observation BEFORE the reset)."""

@@ -88,6 +88,13 @@ class SymmetricEnv:
     def __getattr__(self, attr):
         return getattr(self.env, attr)
 
+    def state_dict(self):
+        """The wrapped env's: the mirror tables are constants of the construction."""
+        return self.env.state_dict()
+
+    def load_state_dict(self, d):
+        self.env.load_state_dict(d)
+
     def _on(self, name, device):
         """Mirror tables cached per device (no host->device copy per call; graph-capturable)."""
         cache = self.__dict__.setdefault("_dev_tables", {})
