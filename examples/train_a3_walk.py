@@ -6,6 +6,7 @@
     python examples/train_a3_walk.py train ... --checkpoint_every 100        # LOGDIR/checkpoint.pt, replaced every 100 iterations
     python examples/train_a3_walk.py train ... --resume ./logs_dir/          # the stopped run goes on, bit for bit
     python examples/train_a3_walk.py train ... --continued ./logs_dir/       # its weights, a new run from iteration 0
+    python examples/train_a3_walk.py train ... --reset_draw device           # reset records drawn on the device (K23)
 
 --resume continues a run exactly (weights, Adam, environment, random streams, logs: olympic_hip.ppo_checkpoint) and needs the
 same command line as the run that wrote the file.  --continued has the reference's meaning (train_a3_walk.py:54-64): the
@@ -40,7 +41,8 @@ def make_physics(num_envs, seed=1):
 
 def run_experiment(args):
     env_fn = partial(StickFigureA3, algorithm_type=AlgorithmType.REINFORCEMENT_LEARNING, num_envs=args.num_procs,
-                     physics=make_physics(args.num_procs))
+                     physics=make_physics(args.num_procs), reset_draw=getattr(args, "reset_draw", "host"),
+                     reset_pool_depth=getattr(args, "reset_pool_depth", None))
     if not args.no_mirror:
         probe = env_fn()
         env_fn = partial(SymmetricEnv, env_fn, mirrored_obs=probe.robot.mirrored_obs,
@@ -95,6 +97,11 @@ if __name__ == "__main__":
     parser.add_argument("--continued", default=None, type=str,
                         help="checkpoint.pt (or its directory) to take weights and normalisation tables from")
     parser.add_argument("--resume", default=None, type=str, help="checkpoint.pt (or its directory) to continue exactly")
+    parser.add_argument("--reset_draw", default="host", choices=["host", "device"],
+                        help="where the walking task's reset records are drawn: numpy on the host, or K23 on the device")
+    parser.add_argument("--reset_pool_depth", default=None, type=lambda v: v if v == "rollout" else int(v),
+                        help="reset records kept per environment (default 4 on the host, 32 on the device); with "
+                             "--reset_draw device, 'rollout' keeps one per step so that none is used twice")
     parser.add_argument("--checkpoint_every", default=None, type=int, help="write LOGDIR/checkpoint.pt every K iterations")
     args = parser.parse_args()
     if args.resume and args.continued:

@@ -355,6 +355,7 @@ SIGNATURES = {
     "oly_iter_log": (C.c_int, [vp, C.POINTER(IterLog), vp]),
     "oly_il_act": (C.c_int, [vp, C.POINTER(ILAct), vp]),
     "oly_il_reset_where": (C.c_int, [vp, C.POINTER(ILReset), vp]),
+    "oly_a3_reset_draw": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, C.c_double, C.c_int, vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

@@ -125,10 +125,12 @@ def yaw_of_quat(q):
 
 class VecA3Env:
     """N StickFigureA3 environments in RL mode.  `physics` supplies, per step, the dict of
-    device tensors named in oly_a3_inputs (minus the K3 outputs) plus the contact slots."""
+    device tensors named in oly_a3_inputs (minus the K3 outputs) plus the contact slots.
+    reset_draw / reset_seed / reset_pool_depth: how the device rollout gets its reset records (A3DeviceRollout's draw,
+    reset_seed and pool_depth): "host" draws them from `rs`, "device" generates them with K23."""
 
     def __init__(self, spec, num_envs, engine, physics, geom_bodyid, floor_body, rfoot_body, lfoot_body,
-                 lut=None, obs_f64=False, rs=None):
+                 lut=None, obs_f64=False, rs=None, reset_draw="host", reset_seed=None, reset_pool_depth=None):
         self.spec, self.num_envs, self.eng, self.physics = spec, int(num_envs), engine, physics
         self.lut = clock_lut(spec.swing_duration, spec.stance_duration, 0.1, "grounded", 1 / spec.control_dt,
                              spec.period) if lut is None else lut
@@ -136,6 +138,7 @@ class VecA3Env:
         engine.contact_configure(geom_bodyid, floor_body, rfoot_body, lfoot_body)
         self.obs_f64 = obs_f64
         self._reset_one = WalkingTaskReset(spec, rs)
+        self.reset_draw, self.reset_seed, self.reset_pool_depth = reset_draw, reset_seed, reset_pool_depth
         N, dev = self.num_envs, engine.device
         z = lambda dt, *shape: torch.zeros((N,) + shape, dtype=dt, device=dev)
         self.state = dict(phase=z(torch.int32), t1=z(torch.int32), t2=z(torch.int32),
@@ -184,9 +187,7 @@ class VecA3Env:
         from .ppo_checkpoint import set_numpy_stream
         roll = d.get("device_rollout")
         if roll is not None:
-            if getattr(self, "_dev_rollout", None) is None:
-                from .vecstep import A3DeviceRollout
-                self._dev_rollout = A3DeviceRollout(self, self.physics.blocks, rs=self._reset_one.rs)
+            self._make_device_rollout()
             self._dev_rollout.load_state_dict(roll)         # compares its sizes before anything is written
         self.iteration_count = d["iteration_count"]
         for k, v in self.state.items():
@@ -204,11 +205,15 @@ class VecA3Env:
         rollout loop can then stay on the device (vecstep.A3DeviceRollout)."""
         return isinstance(self.physics, ReplayA3Physics)
 
-    def device_rollout(self, policy, critic, T, max_traj_len, deterministic=False, anneal=1.0, graph=True, **kw):
-        """PPO.sample for all N environments with one fused launch per vec step (K10)."""
+    def _make_device_rollout(self):
         if getattr(self, "_dev_rollout", None) is None:
             from .vecstep import A3DeviceRollout
-            self._dev_rollout = A3DeviceRollout(self, self.physics.blocks, rs=self._reset_one.rs)
+            self._dev_rollout = A3DeviceRollout(self, self.physics.blocks, pool_depth=self.reset_pool_depth,
+                                                rs=self._reset_one.rs, draw=self.reset_draw, reset_seed=self.reset_seed)
+
+    def device_rollout(self, policy, critic, T, max_traj_len, deterministic=False, anneal=1.0, graph=True, **kw):
+        """PPO.sample for all N environments with one fused launch per vec step (K10)."""
+        self._make_device_rollout()
         return self._dev_rollout.rollout(policy, critic, T, max_traj_len, deterministic, anneal, graph, **kw)
 
     def step(self, actions):
@@ -278,7 +283,7 @@ class StickFigureA3:
                     "upper_body_reward")                                   # walking_task.py:96-103
 
     def __init__(self, algorithm_type=AlgorithmType.REINFORCEMENT_LEARNING, num_envs=1, physics=None, mass=None,
-                 device=0, engine=None, rs=None, **unused):
+                 device=0, engine=None, rs=None, reset_draw="host", reset_seed=None, reset_pool_depth=None, **unused):
         from types import SimpleNamespace
         from .engine import Engine
         from .robot_data import ROBOTS
@@ -292,7 +297,8 @@ class StickFigureA3:
         spec = A3Spec(mass=float(mass if mass is not None else physics.mass))
         self.spec, self.physics = spec, physics
         self.vec = VecA3Env(spec, num_envs, engine or Engine(device), physics, np.asarray(d["geom_bodyid"], np.int32),
-                            d["bodies"]["world"], d["bodies"]["right_foot"], d["bodies"]["left_foot"], obs_f64=True, rs=rs)
+                            d["bodies"]["world"], d["bodies"]["right_foot"], d["bodies"]["left_foot"], obs_f64=True, rs=rs,
+                            reset_draw=reset_draw, reset_seed=reset_seed, reset_pool_depth=reset_pool_depth)
         self.rs = rs if rs is not None else np.random
         self.robot = SimpleNamespace(mirrored_obs=list(spec.mirrored_obs), mirrored_acts=list(spec.mirrored_acts),
                                      clock_inds=list(spec.clock_inds), iteration_count=np.inf,      # robot.py:55

@@ -393,6 +393,28 @@ class Engine:
         launch.structs = (cb, cst, cr)       # the C structs of this launch (tests call the C entry points with them)
         return launch
 
+    # -------------------------------------------------------------- K23 (reset records drawn on the device)
+    def a3_reset_draw(self, pool, base, pool_count, pool_depth, seed, step_height_abs, period):
+        """oly_a3_reset_draw: base += pool_count, pool_count = 0 (pool_count None: base as it is), then slot j of
+        environment n of the ring `pool` (uint8 [N*pool_depth*656]) holds record(seed, n, base[n] + j).  base [N] i64 and
+        pool_count [N] i32 are updated in place.  One launch on the current stream, no synchronisation."""
+        dv = self.device
+        if not isinstance(base, torch.Tensor) or base.dim() != 1:
+            raise OlyError("a3_reset_draw: base is a [N] int64 tensor")
+        N, depth, seed = int(base.shape[0]), int(pool_depth), int(seed)
+        if N < 1 or depth < 1:
+            raise OlyError(f"a3_reset_draw: N = {N}, pool_depth = {depth}")
+        if not 0 <= seed < 2 ** 64:
+            raise OlyError(f"a3_reset_draw: seed {seed} is not an unsigned 64-bit number")
+        h = float(step_height_abs)
+        if not h >= 0.0 or int(period) < 0:
+            raise OlyError(f"a3_reset_draw: step_height_abs = {h}, period = {period}")
+        _req(pool, "pool", (N * depth * C.sizeof(_abi.A3ResetRecord),), torch.uint8, dv)
+        _req(base, "base", (N,), torch.int64, dv)
+        _req(pool_count, "pool_count", (N,), torch.int32, dv, optional=True)
+        self.ctx.call("oly_a3_reset_draw", ptr(pool), N, depth, seed, ptr(base), ptr(pool_count), h, int(period), self._s())
+        return pool
+
     def a3_pd_target(self, action):
         sp = self.a3_spec
         N = int(action.shape[0])

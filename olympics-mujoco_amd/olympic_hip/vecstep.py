@@ -18,6 +18,11 @@ Random draws are inputs: the action noise is a [T,N,nu] block drawn 
 the reset records (mode, phase, local step sequence: walking_task.py:137-182,353-392) are drawn on
 the host into a per-environment ring of `pool_depth` records; an environment that resets more than
 pool_depth times within ONE rollout re-uses its oldest record (counted in `last_info`).
+
+draw="device" (K23, oly_a3_reset_draw) fills the same ring on the device instead: record(seed, n, k), the k-th reset of
+environment n, is a pure function of a counter-based generator, so a ring of any depth costs no host draw, no pinned
+memory and no upload, and a ring of T + 1 records (pool_depth="rollout") never re-uses one.  The same distribution as
+the host's draws, another sequence.  The kernels that read the ring are the same in both modes.
 """
 import ctypes as C
 
@@ -103,26 +108,63 @@ class TorchForward:
         return mu.contiguous(), self.critic(state).reshape(state.shape[0]).contiguous()
 
 
-class A3DeviceRollout:
-    """PPO.sample for a VecA3Env whose physics readback is a set of [K,N,...] device blocks."""
+def step_height_abs(iter_count):
+    """h(iteration) of WalkingTask.reset's step height +-h, as draw_reset_records forms it (float64)."""
+    return float(np.clip((iter_count - 3000) / 8000, 0, 1) * 0.1)
 
-    def __init__(self, env, blocks, pool_depth=4, rs=None, keep_rew6=False):
+
+class A3DeviceRollout:
+    """PPO.sample for a VecA3Env whose physics readback is a set of [K,N,...] device blocks.
+
+    draw="host" (default): the reset records are drawn from `rs` with numpy and uploaded into a ring of `pool_depth`
+    records per environment (None: 4).
+    draw="device": the ring is filled by oly_a3_reset_draw (K23) from (seed, environment, ordinal) at construction and
+    after every rollout, on the rollout's stream; nothing is drawn, pinned or uploaded.  seed is `reset_seed`, or one
+    rs.randint draw at construction; `base` [N] int64 is the ordinal in slot 0 of every ring.  pool_depth None: 32 (656 B
+    per record: 86 MB at 4096 environments).  pool_depth="rollout": T + 1 records, sized when the first rollout gives T,
+    so that no record is ever re-used (1.08 GB at 4096 environments x T = 400)."""
+
+    def __init__(self, env, blocks, pool_depth=None, rs=None, keep_rew6=False, draw="host", reset_seed=None):
+        if draw not in ("host", "device"):
+            raise OlyError(f"A3DeviceRollout: draw is 'host' or 'device', not {draw!r}")
         self.env, self.eng, self.spec = env, env.eng, env.spec
         self.blocks = blocks
         self.N = int(blocks["qpos"].shape[1])
         if self.N != env.num_envs:
             raise OlyError(f"blocks hold {self.N} environments, the env {env.num_envs}")
         self.rs = rs if rs is not None else np.random
-        self.depth = int(pool_depth)
+        self.draw = draw
         self.keep_rew6 = keep_rew6
         dev, N = self.eng.device, self.N
-        self.pool = torch.zeros(N * self.depth * REC.itemsize, dtype=torch.uint8, device=dev)
+        device_draw = draw == "device"
+        if pool_depth == "rollout":
+            if not device_draw:
+                raise OlyError("A3DeviceRollout: pool_depth='rollout' needs draw='device'")
+            self.depth = None                                  # T + 1, once _ensure learns T
+        else:
+            self.depth = (32 if device_draw else 4) if pool_depth is None else int(pool_depth)
+            if self.depth < 1:
+                raise OlyError(f"A3DeviceRollout: pool_depth = {self.depth}")
+        self.pool_depth = "rollout" if self.depth is None else self.depth     # as configured: what a checkpoint compares
+        self.pool = None if self.depth is None else torch.zeros(N * self.depth * REC.itemsize, dtype=torch.uint8, device=dev)
         self.pool_count = torch.zeros(N, dtype=torch.int32, device=dev)
         self.ctr = torch.zeros(self.eng.a3_vec_ctr_len(N), dtype=torch.int32, device=dev)
         self.state_obs = torch.zeros((N, self.spec.n_obs), dtype=torch.float32, device=dev)
         self.pd_target = torch.zeros((N, self.spec.nu), dtype=torch.float64, device=dev)
         self.traj_len = torch.zeros(N, dtype=torch.int32, device=dev)
         self.scale = torch.zeros(self.spec.nu, dtype=torch.float32, device=dev)
+        self._shape = None
+        self._graphs = {}
+        self.last_info = {}
+        if device_draw:
+            self.seed = int(self.rs.randint(0, 2 ** 63, dtype=np.int64) if reset_seed is None else reset_seed)
+            if not 0 <= self.seed < 2 ** 64:
+                raise OlyError(f"A3DeviceRollout: reset_seed {self.seed} is not an unsigned 64-bit number")
+            self.base = torch.zeros(N, dtype=torch.int64, device=dev)
+            self._h = None                                     # the step height the ring was last filled with
+            if self.pool is not None:
+                self._fill(advance=False)
+            return
         # two pinned stashes of pre-drawn records, used alternately: one is being uploaded (asynchronously) while the
         # other is refilled on the host behind the next rollout's kernels
         cap = N * self.depth
@@ -131,12 +173,22 @@ class A3DeviceRollout:
         self._stash_n, self._stash_i = 0, 0
         self._last_total = N
         self._env_ids = torch.arange(N, device=dev)
-        self._shape = None
-        self._graphs = {}
-        self.last_info = {}
         self._refill(np.full(N, self.depth))
 
     # ------------------------------------------------------------------ reset-record pool
+    def _fill(self, advance=True, h=None):
+        """draw="device": ONE launch (oly_a3_reset_draw) on the current stream.  advance: base += pool_count, pool_count = 0
+        first, i.e. the ring moves past the records the last rollout consumed.  h: the step height, default the one that
+        follows the environment's iteration count (read where the host path reads it for its draws)."""
+        self._h = step_height_abs(getattr(self.env, "iteration_count", 0)) if h is None else float(h)
+        self.eng.a3_reset_draw(self.pool, self.base, self.pool_count if advance else None, self.depth, self.seed, self._h,
+                               self.spec.period)
+
+    def _draw_ahead(self):
+        """draw="host": the next refill's records, drawn while the rollout's kernels run.  draw="device" has nothing to do."""
+        if self.draw == "host":
+            self._predraw(1.15 * self._last_total + 64)
+
     def _predraw(self, want):
         """Top the current stash up to `want` records (host RNG: the random part of WalkingTask.reset)."""
         want = min(int(want), len(self._stash[0]))
@@ -174,6 +226,10 @@ class A3DeviceRollout:
             g.reset()
         self._graphs = {}
         dev, N, sp = self.eng.device, self.N, self.spec
+        if self.pool_depth == "rollout" and self.depth != T + 1:
+            self.depth = T + 1
+            self.pool = torch.empty(N * self.depth * REC.itemsize, dtype=torch.uint8, device=dev)
+            self._fill(advance=False, h=self._h)               # the same records: record() is pure
         self.buf = RolloutBuffer(T, N, sp.n_obs, sp.nu, dev, reward_dtype=torch.float64)
         nv = torch.zeros(T * N + 1, dtype=torch.float32, device=dev)      # + one dummy slot for unused side rows
         self._nv_flat, self.buf.next_values = nv, nv[:T * N].view(T, N)
@@ -232,7 +288,7 @@ class A3DeviceRollout:
                 raise OlyError("persistent rollout needs the fused MLP forward (2 x 256 relu actor / critic)")
             mu, v = fw.outputs(N)
             self.launch.persistent(fw.packed_a, fw.norm_a, fw.packed_c, fw.norm_c, mu, v)
-            self._predraw(1.15 * self._last_total + 64)       # host work behind the kernel
+            self._draw_ahead()                                # host work behind the kernel
             self._finalize(fw, critic)
             return buf
 
@@ -249,7 +305,7 @@ class A3DeviceRollout:
         while t < T:
             one_step()
             t += 1
-        self._predraw(1.15 * self._last_total + 64)           # host work behind the queued launches
+        self._draw_ahead()                                    # host work behind the queued launches
         self._finalize(fw, critic)
         if U and not fused:
             # A graph that holds torch GEMM / elementwise nodes lives for ONE rollout.  profiles/r02/graph_drift: a
@@ -311,7 +367,11 @@ class A3DeviceRollout:
         exist once a rollout has sized them, and every rollout rewinds them), the PD target and the reset-record pool."""
         d = {f"task.{k}": self.env.state[k] for k in _abi.A3_STATE_FIELDS}
         d.update(state_obs=self.state_obs, traj_len=self.traj_len, pool_count=self.pool_count, ctr=self.ctr,
-                 pd_target=self.pd_target, pool=self.pool)
+                 pd_target=self.pd_target)
+        if self.draw == "device":
+            d.update(base=self.base)                            # the ring itself follows from (seed, base)
+        else:
+            d.update(pool=self.pool)
         if self._shape is not None:
             d.update(side_count=self.side_count, side_t=self.side_t)
         return d
@@ -321,8 +381,14 @@ class A3DeviceRollout:
         of the current pinned stash with its cursors, the readback cursor of the physics, the iteration count the step
         heights follow, and the numpy stream the reset records are drawn from.  Draws nothing."""
         from .ppo_checkpoint import numpy_stream_state
-        used = self._stash_n * REC.itemsize
         phys = getattr(self.env, "physics", None)
+        if self.draw == "device":
+            # no pool and no stash: (draw, seed, base, pool_count) and the step height of the last fill give the ring back
+            return dict(num_envs=self.N, pool_depth=self.pool_depth, draw="device", seed=int(self.seed),
+                        step_height_abs=self._h, tensors={k: v.clone() for k, v in self._named().items()},
+                        physics_k=int(phys.k) if phys is not None and hasattr(phys, "k") else None,
+                        iteration_count=getattr(self.env, "iteration_count", None))
+        used = self._stash_n * REC.itemsize
         return dict(num_envs=self.N, pool_depth=self.depth, tensors={k: v.clone() for k, v in self._named().items()},
                     stash=self._stash_t[self._stash_i][:used].clone(), stash_n=int(self._stash_n),
                     stash_i=int(self._stash_i), last_total=int(self._last_total),
@@ -335,8 +401,9 @@ class A3DeviceRollout:
         compared before the first write."""
         from .gail import _same
         from .ppo_checkpoint import set_numpy_stream
+        _same("A3DeviceRollout", "draw", d.get("draw", "host"), self.draw)
         _same("A3DeviceRollout", "num_envs", d["num_envs"], self.N)
-        _same("A3DeviceRollout", "pool_depth", d["pool_depth"], self.depth)
+        _same("A3DeviceRollout", "pool_depth", d["pool_depth"], self.pool_depth)
         own = self._named()
         rewound = ("side_count", "side_t")                  # sized by (T, max_traj_len) and reset by every rollout
         for k, v in own.items():
@@ -350,13 +417,19 @@ class A3DeviceRollout:
             t = d["tensors"].get(k)
             if t is not None and tuple(t.shape) == tuple(v.shape):
                 v.copy_(t)
-        self._stash_n, self._stash_i, self._last_total = int(d["stash_n"]), int(d["stash_i"]), int(d["last_total"])
-        self._stash_t[self._stash_i][:d["stash"].numel()].copy_(d["stash"])
+        if self.draw == "host":
+            self._stash_n, self._stash_i, self._last_total = int(d["stash_n"]), int(d["stash_i"]), int(d["last_total"])
+            self._stash_t[self._stash_i][:d["stash"].numel()].copy_(d["stash"])
         phys = getattr(self.env, "physics", None)
         if d["physics_k"] is not None and phys is not None and hasattr(phys, "k"):
             phys.k = int(d["physics_k"])
         if d["iteration_count"] is not None and hasattr(self.env, "iteration_count"):
             self.env.iteration_count = d["iteration_count"]
+        if self.draw == "device":
+            self.seed, self._h = int(d["seed"]), d["step_height_abs"]
+            if self.pool is not None:                           # a "rollout" ring not yet sized is filled by _ensure
+                self._fill(advance=False, h=self._h)
+            return
         set_numpy_stream(self.rs, d["rs"])
 
     def _finalize(self, fw, critic):
@@ -386,7 +459,10 @@ class A3DeviceRollout:
         phys = getattr(self.env, "physics", None)
         if phys is not None and hasattr(phys, "k"):
             phys.k = k % int(self.blocks["qpos"].shape[0])
-        self._refill(consumed)
+        if self.draw == "device":
+            self._fill()
+        else:
+            self._refill(consumed)
 
     def close(self):
         for g in self._graphs.values():
