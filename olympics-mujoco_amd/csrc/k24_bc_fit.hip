@@ -1,0 +1,530 @@
+// K24: behavioural cloning (BehavioralCloning.fit_offline, imitation_lib/imitation/offline/behavioral_cloning.py:46-80)
+// of the squashed-Gaussian policy IQ_Learn_Policy (imitation_lib/imitation/iq_sac.py:18-167): a
+// FullyConnectedNetwork(in -> [512, 256] -> 2A, relu / relu / identity) whose output columns [0, A) are mu and [A, 2A)
+// log_sigma, trained by Adam over torch.nn.GaussianNLLLoss() on the un-squashed demonstration actions.
+//
+//   oly_bc_targets    atanh(clip((a - central) / delta, -+(1 - 1e-7))) over the whole action table (:63-66), one launch.
+//   oly_bc_fit_steps  n_steps iterations of fit_offline in one call.  Per call: oly_ilmlp_pack (the stream from param),
+//                     bc_prologue_kernel (the transposed W2 and W3 streams of the backward, the statistics partials of
+//                     step 0), then per step s
+//   A  bc_rows_kernel     one 16-row tile per workgroup (8 waves): gather idx[s] rows, standardise with the statistics
+//                         that include them (networks.py:68-81), the forward on the f32 matrix cores
+//                         (v_mfma_f32_16x16x4_f32) in the forward kernel's chain order (ilmlp_common.h) with relu, the
+//                         output layer's one or two column tiles by waves 0 / 1 as one chain over k < 256 each, the
+//                         loss terms and dZ3 per element in fp64, dH2 = dZ3 W3 (matrix cores, transposed W3 stream),
+//                         dZ2 = dH2 [h2 > 0], dH1 = dZ2 W2 (transposed W2 stream), dZ1 = dH1 [h1 > 0].  Activations and
+//                         deltas go to the workspace in row quads ([row / 4][column][row % 4]); the tile's three loss
+//                         sums to fixed slots.
+//   B  bc_weights_kernel  one 16 x 16 weight tile per workgroup over W1, W2 and W3: dW = sum over the minibatch's rows of
+//                         delta^T a (4 waves x a quarter of the 16-row steps each, added in wave order), weight decay,
+//                         Adam, the stepped values into param, the moments, the packed stream and the transposed
+//                         streams.  Workgroup 0 adds the loss partials, writes out[s] and colstats += minibatch s;
+//                         workgroups 1 .. 16 sum step s+1's rows into the statistics partials launch A of s+1 reads.
+// Every reduction has a fixed order and there are no atomics: two runs give identical bits, and a call of n steps
+// leaves the bits of n calls of one step (the prologue rebuilds from param exactly what launch B keeps current).
+// Adam, the statistics fold and the weights kernel's tail are fit_common.h's, shared with K15, K16 and K18.
+#include <cstdlib>
+
+#include "fit_common.h"
+#include "ilmlp_common.h"
+#include "mlp_tiles.h"
+#include "oly_common.h"
+
+namespace {
+using namespace oly_ilmlp;
+using oly_fit::adam1;
+using oly_fit::NSP;
+using oly_fit::pt_index;
+using oly_fit::row_at;
+using oly_fit::stats_slice;
+using oly_fit::THREADS;
+static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
+
+constexpr int MAX_BATCH = OLY_BC_MAX_BATCH;   // loss_tree folds at most THREADS = 256 tiles of 16 rows
+constexpr int MAX_ACT = OLY_BC_MAX_ACT;
+constexpr int OUTP = OUT_MAX;                 // pitch of the output layer's delta: two column tiles
+static_assert(MAX_BATCH <= 16 * THREADS && 2 * MAX_ACT <= OUTP, "one loss partial per thread; 2A output columns");
+
+// workspace (floats), BP = batch rounded up to 16 rows; [BP][W] arrays in row quads, element (row, col) at
+// ((row / 4) W + col) 4 + row % 4:
+//   xs [BP][64] standardised rows | h1 [BP][512] | h2 [BP][256] | dZ1 [BP][512] | dZ2 [BP][256] | dZ3 [BP][32] |
+//   loss partials [2][BP / 16][2] f64 ((nll, sum log_sigma), (squared error, 0)) | statistics partials [NSP][2][64] f64 |
+//   the minibatch's column sums [2][64] f64 | the transposed streams W2T, W3T
+struct WsL {
+  size_t xs, h1, h2, dz1, dz2, dz3, lossp, statp, delta, w2t, w3t, total;
+};
+__host__ __device__ inline WsL ws_layout(int batch) {
+  const size_t BP = (size_t)(batch + 15) / 16 * 16;
+  WsL W;
+  W.xs = 0;
+  W.h1 = W.xs + BP * IN_MAX;
+  W.h2 = W.h1 + BP * H1;
+  W.dz1 = W.h2 + BP * H2;
+  W.dz2 = W.dz1 + BP * H1;
+  W.dz3 = W.dz2 + BP * H2;
+  W.lossp = W.dz3 + BP * OUTP;
+  W.statp = W.lossp + BP / 16 * 8;
+  W.delta = W.statp + (size_t)NSP * 2 * IN_MAX * 2;
+  W.w2t = W.delta + 2 * IN_MAX * 2;
+  W.w3t = W.w2t + (size_t)H2 * H1;
+  W.total = W.w3t + (size_t)OUTP * H2;
+  return W;
+}
+
+// W2T / W3T are the B operands of the data gradients dH1 = dZ2 W2 (N = 256 outputs) and dH2 = dZ3 W3 (N = 32, rows
+// n >= 2A zero) in pt_index's layout (fit_common.h)
+struct FitArgs {
+  int in_dim, n_rows, act_dim, out_dim;
+  int ds, d2, std2, stride2;   // fit_common.h's two-source members: one source here (ds = in_dim, no x2)
+  const float* x2;
+  int R, Rn;                   // rows of step s / s+1 (0: none)
+  long off, off_next;          // first position of step s / s+1 in perm
+  const int32_t* perm;         // idx [n_steps, batch]
+  const float *x, *targets;
+  double* colstats;            // or NULL: the rows go in as they are
+  float *param, *m, *v, *packed, *ws;
+  float ls_min, ls_max, nll_eps;
+  oly_fit::AdamK ad;
+  float wd;                    // weight_decay
+  double* out;                 // + 3 s
+  ParamLayout P;
+  WsL W;
+};
+
+// grid PRO_BLOCKS: the transposed streams from param (grid-stride) and, workgroups 0 .. NSP-1, step 0's partials
+constexpr int PRO_BLOCKS = 64;
+__global__ __launch_bounds__(THREADS) void bc_prologue_kernel(FitArgs a) {
+  __shared__ double part[8 * IN_MAX];
+  for (int e = blockIdx.x * THREADS + threadIdx.x; e < H2 * H1; e += PRO_BLOCKS * THREADS)
+    a.ws[a.W.w2t + pt_index(H2, e / H1, e % H1)] = a.param[a.P.w2 + e];
+  for (int e = blockIdx.x * THREADS + threadIdx.x; e < OUTP * H2; e += PRO_BLOCKS * THREADS)
+    a.ws[a.W.w3t + pt_index(OUTP, e / H2, e % H2)] = e / H2 < a.out_dim ? a.param[a.P.w3 + e] : 0.f;
+  if (a.colstats && blockIdx.x < NSP) stats_slice(a, a.off, a.R, blockIdx.x, part);
+}
+
+__device__ __forceinline__ float relu32(float v) { return (v > 0.f || v != v) ? v : 0.f; }   // NaN kept like torch
+
+// ---------------------------------------------------------------------------------------------------------------
+// Launch A.  512 threads = 8 waves, two per SIMD (as K18: at the batches of this fit a CU holds one workgroup, so the
+// second wave per SIMD is what covers the other's weight loads).  Chains: layer 1 wave w -> column tiles 4w .. 4w+3,
+// layer 2 -> 2w, 2w+1, the output layer's tile t by wave t.  Backward: dH2 (wave w -> tiles 2w, 2w+1, the chain over the
+// 32 padded outputs) and dH1 (wave w -> tiles 4w .. 4w+3, the chain over the 256 layer-2 units).
+constexpr int RTHREADS = 512;
+constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16 + 2 * OUTP * 16;
+constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (2 * IN_MAX + 3 * 256 + 48);
+static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
+
+template <int G1>
+__global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xT = lds;                       // [64 x 16]   standardised input (act16 images, mlp_tiles.h)
+  float* hA = xT + IN_MAX * 16;          // [512 x 16]  h1
+  float* hB = hA + H1 * 16;              // [256 x 16]  h2
+  float* gz = hB + H2 * 16;              // [256 x 16]  dZ2
+  float* z3 = gz + H2 * 16;              // [16][32]    the raw outputs by row
+  float* gz3 = z3 + 16 * OUTP;           // [32 x 16]   dZ3
+  double* st = reinterpret_cast<double*>(lds + ROWS_LDS_FLOATS);   // [2][IN_MAX] mean, std
+  double* red = st + 2 * IN_MAX;         // [3][16][16] nll, clamped log_sigma, squared error by (row, action)
+  double* rsum = red + 3 * 256;          // [3][16]     their sums by row
+  __shared__ int rows_x[16];             // the tile's data rows (-1 beyond the minibatch)
+  const float* P = a.packed;
+  const float4* P4 = reinterpret_cast<const float4*>(P);
+  const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, h4 = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int row0 = blockIdx.x * 16, R = a.R, in_dim = a.in_dim, A = a.act_dim;
+  const bool standardise = a.colstats != nullptr;
+  float* ws = a.ws;
+  float4* ws4 = reinterpret_cast<float4*>(ws);
+  const size_t quad = (size_t)(row0 >> 2) + h4;      // this lane's accumulator rows: 4 h4 + i = one row quad
+
+  if (standardise && tid < in_dim) {   // Standardizer.update_mean_std with the minibatch's rows (networks.py:76-81), as K18
+    const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
+    double s = 0.0, ss = 0.0;
+    for (int p = 0; p < NSP; ++p) {
+      s += sp[p * 2 * IN_MAX + tid];
+      ss += sp[p * 2 * IN_MAX + IN_MAX + tid];
+    }
+    const double cnt = a.colstats[tid] + (double)R + 1e-2;
+    const double mean = (a.colstats[in_dim + tid] + s) / cnt;
+    st[tid] = mean;
+    st[IN_MAX + tid] = sqrt(fmax((a.colstats[2 * in_dim + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    if (blockIdx.x == 0) {
+      double* d = reinterpret_cast<double*>(ws + a.W.delta);
+      d[tid] = s;
+      d[IN_MAX + tid] = ss;
+    }
+  }
+  if (tid < 16) rows_x[tid] = row0 + tid < R ? row_at(a, a.off + row0 + tid) : -1;
+  __syncthreads();
+  for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
+    const int m = e / IN_MAX, k = e & (IN_MAX - 1), row = rows_x[m];
+    float v = 0.f;
+    if (row >= 0 && k < in_dim) {
+      v = a.x[(size_t)row * in_dim + k];
+      // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
+      if (standardise) v = (float)(((double)v - st[k]) / st[IN_MAX + k]);
+    }
+    xT[act16_index(k, m)] = v;
+    ws[a.W.xs + ((size_t)((row0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
+  }
+  __syncthreads();
+  {  // ---- layer 1: [16, in] x [in, 512]
+    f32x4 acc[1][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float4* a4[1] = {reinterpret_cast<const float4*>(xT)};
+    tiles<G1, 4, 1>(a4, P4 + P_W1 / 4 + (size_t)(4 * wave) * (IN_MAX / 16) * 64, (IN_MAX / 16) * 64, lane, acc);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int col = 16 * (4 * wave + t) + c;
+      const float bv = P[P_B1 + col];
+      float4 h;
+      h.x = relu32(acc[0][t][0] + bv);
+      h.y = relu32(acc[0][t][1] + bv);
+      h.z = relu32(acc[0][t][2] + bv);
+      h.w = relu32(acc[0][t][3] + bv);
+      hA[act16_index(col, 4 * h4)] = h.x;
+      hA[act16_index(col, 4 * h4 + 1)] = h.y;
+      hA[act16_index(col, 4 * h4 + 2)] = h.z;
+      hA[act16_index(col, 4 * h4 + 3)] = h.w;
+      ws4[(a.W.h1 >> 2) + quad * H1 + col] = h;
+    }
+  }
+  __syncthreads();
+  float4 h2r[2];
+  {  // ---- layer 2: [16, 512] x [512, 256]
+    f32x4 acc[1][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float4* a4[1] = {reinterpret_cast<const float4*>(hA)};
+    tiles<H1 / 16, 2, 1>(a4, P4 + P_W2 / 4 + (size_t)(2 * wave) * (H1 / 16) * 64, (H1 / 16) * 64, lane, acc);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int col = 16 * (2 * wave + t) + c;
+      const float bv = P[P_B2 + col];
+      float4 h;
+      h.x = relu32(acc[0][t][0] + bv);
+      h.y = relu32(acc[0][t][1] + bv);
+      h.z = relu32(acc[0][t][2] + bv);
+      h.w = relu32(acc[0][t][3] + bv);
+      hB[act16_index(col, 4 * h4)] = h.x;
+      hB[act16_index(col, 4 * h4 + 1)] = h.y;
+      hB[act16_index(col, 4 * h4 + 2)] = h.z;
+      hB[act16_index(col, 4 * h4 + 3)] = h.w;
+      h2r[t] = h;
+      ws4[(a.W.h2 >> 2) + quad * H2 + col] = h;
+    }
+  }
+  __syncthreads();
+  if (wave < (a.out_dim > 16 ? 2 : 1)) {  // ---- the output layer's column tile `wave`: one chain over k < 256, as the forward kernel
+    f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
+    const float4* a4[1] = {reinterpret_cast<const float4*>(hB)};
+    tiles<H2 / 16, 1, 1>(a4, P4 + P_W3 / 4 + (size_t)wave * (H2 / 16) * 64, 0, lane, acc);
+    const int col = 16 * wave + c;
+    const float bv = P[P_B3 + col];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) z3[(4 * h4 + i) * OUTP + col] = acc[0][0][i] + bv;
+  }
+  __syncthreads();
+  {  // ---- GaussianNLLLoss(full=False, eps, 'mean')'s terms and dZ3, thread (row m, output column col)
+    const int m = tid >> 5, col = tid & (OUTP - 1), row = rows_x[m];
+    float g = 0.f;
+    if (col < 2 * A) {
+      const int j = col < A ? col : col - A;
+      double t0 = 0.0, t1 = 0.0;
+      if (row >= 0) {
+        const float raw = z3[m * OUTP + A + j];
+        const float ls = fminf(fmaxf(raw, a.ls_min), a.ls_max);                 // iq_sac.py:146
+        const double sg = exp((double)ls), var = sg * sg, vc = fmax(var, (double)a.nll_eps);
+        const double d = (double)z3[m * OUTP + j] - (double)a.targets[(size_t)row * A + j];
+        const double r = d * d / vc, invn = 1.0 / ((double)R * (double)A);
+        if (col < A) {
+          g = (float)(d / vc * invn);
+          t0 = 0.5 * (log(vc) + r);
+          t1 = d * d;
+        } else {
+          // the variance floor is applied under no_grad, so the gradient passes through it: var / vc; the clamp's
+          // mask is inclusive
+          g = (raw >= a.ls_min && raw <= a.ls_max) ? (float)((1.0 - r) * (var / vc) * invn) : 0.f;
+          t0 = (double)ls;
+        }
+      }
+      if (col < A) {
+        red[m * 16 + j] = t0;
+        red[512 + m * 16 + j] = t1;
+      } else {
+        red[256 + m * 16 + j] = t0;
+      }
+    }
+    gz3[act16_index(col, m)] = g;
+    ws[a.W.dz3 + ((size_t)((row0 + m) >> 2) * OUTP + col) * 4 + (m & 3)] = g;
+  }
+  __syncthreads();
+  if (tid < 48) {       // the three sums of row tid & 15, actions in order
+    double s = 0.0;
+    for (int j = 0; j < A; ++j) s += red[tid * 16 + j];
+    rsum[tid] = s;
+  }
+  {  // ---- dZ2 = (dZ3 W3) [h2 > 0]
+    f32x4 acc[1][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float4* a4[1] = {reinterpret_cast<const float4*>(gz3)};
+    tiles<OUTP / 16, 2, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.w3t >> 2) + (size_t)(2 * wave) * (OUTP / 16) * 64,
+                           (OUTP / 16) * 64, lane, acc);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int col = 16 * (2 * wave + t) + c;
+      float4 g;
+      g.x = h2r[t].x > 0.f ? acc[0][t][0] : 0.f;
+      g.y = h2r[t].y > 0.f ? acc[0][t][1] : 0.f;
+      g.z = h2r[t].z > 0.f ? acc[0][t][2] : 0.f;
+      g.w = h2r[t].w > 0.f ? acc[0][t][3] : 0.f;
+      gz[act16_index(col, 4 * h4)] = g.x;
+      gz[act16_index(col, 4 * h4 + 1)] = g.y;
+      gz[act16_index(col, 4 * h4 + 2)] = g.z;
+      gz[act16_index(col, 4 * h4 + 3)] = g.w;
+      ws4[(a.W.dz2 >> 2) + quad * H2 + col] = g;
+    }
+  }
+  __syncthreads();
+  if (tid < 3) {        // this tile's loss partials, rows in order
+    double s = 0.0;
+    for (int r = 0; r < 16; ++r) s += rsum[tid * 16 + r];
+    double* lp = reinterpret_cast<double*>(ws + a.W.lossp);
+    const size_t tiles_n = (size_t)gridDim.x;
+    if (tid < 2) {
+      lp[2 * blockIdx.x + tid] = s;
+    } else {
+      lp[2 * tiles_n + 2 * blockIdx.x] = s;
+      lp[2 * tiles_n + 2 * blockIdx.x + 1] = 0.0;
+    }
+  }
+  {  // ---- dZ1 = (dZ2 W2) [h1 > 0]
+    f32x4 acc[1][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float4* a4[1] = {reinterpret_cast<const float4*>(gz)};
+    tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
+                         (H2 / 16) * 64, lane, acc);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int col = 16 * (4 * wave + t) + c;
+      float4 g;
+      g.x = hA[act16_index(col, 4 * h4)] > 0.f ? acc[0][t][0] : 0.f;
+      g.y = hA[act16_index(col, 4 * h4 + 1)] > 0.f ? acc[0][t][1] : 0.f;
+      g.z = hA[act16_index(col, 4 * h4 + 2)] > 0.f ? acc[0][t][2] : 0.f;
+      g.w = hA[act16_index(col, 4 * h4 + 3)] > 0.f ? acc[0][t][3] : 0.f;
+      ws4[(a.W.dz1 >> 2) + quad * H1 + col] = g;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Launch B.  Tiles (n-tile x k-tile): W1 32 x ceil(in / 16), W2 16 x 32, W3 (1 or 2) x 16; the k-tile 0 of each layer also
+// steps the layer's bias.
+__host__ __device__ inline int weight_tiles(int in_dim, int out_dim) {
+  return 32 * ((in_dim + 15) / 16) + 512 + 16 * ((out_dim + 15) / 16);
+}
+
+constexpr int STEP_UNROLL = 4;      // 16-row steps whose loads are issued together
+constexpr double HALF_LOG_2PI_P1 = 0.5 + 0.5 * 1.8378770664093454835606594728112;   // 0.5 + 0.5 log(2 pi)
+__global__ __launch_bounds__(THREADS) void bc_weights_kernel(FitArgs a) {
+  __shared__ float red[4 * 256];
+  __shared__ float bred[4 * 64];
+  __shared__ double dred[2 * THREADS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, h4 = lane >> 4;
+  const WsL& W = a.W;
+  const ParamLayout& PL = a.P;
+  const int kt0 = (a.in_dim + 15) / 16;
+  int t = blockIdx.x, layer, nt, kt;
+  if (t < 32 * kt0) {
+    layer = 0, nt = t / kt0, kt = t % kt0;
+  } else if ((t -= 32 * kt0) < 512) {
+    layer = 1, nt = t / 32, kt = t % 32;
+  } else {
+    layer = 2, nt = (t - 512) / 16, kt = (t - 512) % 16;
+  }
+  // delta [R][dw] (N columns used) and activation [R][aw] (K columns used) of the layer, both in row quads
+  const int dw = layer == 0 ? H1 : layer == 1 ? H2 : OUTP;
+  const int N = layer == 2 ? a.out_dim : dw;
+  const int aw = layer == 0 ? IN_MAX : layer == 1 ? H1 : H2;
+  const int K = layer == 0 ? a.in_dim : aw;
+  const float4* dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.dz1 : layer == 1 ? W.dz2 : W.dz3));
+  const float4* al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.xs : layer == 1 ? W.h1 : W.h2));
+  const int n0 = 16 * nt, k0 = 16 * kt, R = a.R;
+  const bool n_ok = n0 + c < N, k_ok = k0 + c < K;
+  // a step = the 16 rows of one tile of launch A (which wrote all 16: zeros in the deltas beyond the minibatch); lane
+  // group h4 takes the step's row quad h4.  Wave w: steps [w Q, min(steps, (w + 1) Q))
+  const int steps = (R + 15) / 16, Q = (steps + 3) / 4, s0 = wave * Q, s1 = min(steps, s0 + Q);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int s = s0; s < s1; s += STEP_UNROLL) {
+    float4 dv[STEP_UNROLL], av[STEP_UNROLL];
+#pragma unroll
+    for (int u = 0; u < STEP_UNROLL; ++u) {
+      const size_t q = (size_t)4 * (s + u) + h4;
+      const bool in = s + u < s1;
+      dv[u] = (in && n_ok) ? dl[q * dw + n0 + c] : zero4;
+      av[u] = (in && k_ok) ? al[q * aw + k0 + c] : zero4;
+    }
+#pragma unroll
+    for (int u = 0; u < STEP_UNROLL; ++u) {
+      // A[i = lane & 15][r = lane >> 4] = delta[row 4 q + r][n0 + i], B[r][j = lane & 15] = a[row 4 q + r][k0 + j]
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].x, av[u].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].y, av[u].y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].z, av[u].z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].w, av[u].w, acc, 0, 0, 0);
+      bsum += ((dv[u].x + dv[u].y) + dv[u].z) + dv[u].w;
+    }
+  }
+  // D[n = 4 (lane >> 4) + i][k = lane & 15]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[wave * 256 + (4 * h4 + i) * 16 + c] = acc[i];
+  bred[wave * 64 + lane] = bsum;
+  __syncthreads();
+  {
+    const int nn = tid >> 4, kk = tid & 15, ne = n0 + nn, ke = k0 + kk;
+    if (ne < N && ke < K) {
+      const float g = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
+      if (layer == 0) {
+        a.packed[pk_index(P_W1, IN_MAX / 16, ne, ke)] = adam1(a, PL.w1 + (size_t)ne * a.in_dim + ke, g);
+      } else if (layer == 1) {
+        const float p = adam1(a, PL.w2 + (size_t)ne * H1 + ke, g);
+        a.packed[pk_index(P_W2, H1 / 16, ne, ke)] = p;
+        a.ws[W.w2t + pt_index(H2, ne, ke)] = p;
+      } else {
+        const float p = adam1(a, PL.w3 + (size_t)ne * H2 + ke, g);
+        a.packed[pk_index(P_W3, H2 / 16, ne, ke)] = p;
+        a.ws[W.w3t + pt_index(OUTP, ne, ke)] = p;
+      }
+    }
+    if (kt == 0 && tid < 16 && n0 + tid < N) {   // the bias: the column sums of delta, lane groups then waves in order
+      const float gb = oly_fit::bias_colsum(bred, tid);
+      const size_t pb = layer == 0 ? PL.b1 : layer == 1 ? PL.b2 : PL.b3;
+      const size_t kb = layer == 0 ? P_B1 : layer == 1 ? P_B2 : P_B3;
+      a.packed[kb + n0 + tid] = adam1(a, pb + n0 + tid, gb);
+    }
+  }
+  if (blockIdx.x == 0) {   // ---- the step's three scalars (logging(), behavioral_cloning.py:82-94); colstats += minibatch s
+    const double* lp = reinterpret_cast<const double*>(a.ws + W.lossp);
+    oly_fit::loss_tree(steps, lp, dred);
+    const double nll = dred[0], lsum = dred[THREADS];
+    __syncthreads();
+    oly_fit::loss_tree(steps, lp + 2 * (size_t)steps, dred);
+    if (tid == 0) {
+      const double n = (double)R * (double)a.act_dim;
+      a.out[0] = nll / n;                                                       // GaussianNLLLoss
+      a.out[1] = (double)a.act_dim * HALF_LOG_2PI_P1 + lsum / (double)R;         // entropy_from_logsigma, mean over rows
+      a.out[2] = dred[0] / n;                                                   // F.mse_loss(mu, target)
+    }
+    if (a.colstats) oly_fit::colstats_add(a, R);
+  } else if (blockIdx.x <= NSP && a.colstats && a.Rn > 0) {
+    stats_slice(a, a.off_next, a.Rn, blockIdx.x - 1, dred);
+  }
+}
+
+// targets = atanhf(clip((a - central) / delta, -+f32(1 - 1e-7)))   (behavioral_cloning.py:63-66, float32 as torch)
+__global__ __launch_bounds__(256) void bc_targets_kernel(long n, int A, const float* __restrict__ act,
+                                                         const float* __restrict__ central, const float* __restrict__ delta,
+                                                         float* __restrict__ out) {
+  const float hi = 0x1.fffffcp-1f;    // float32(1 - 1e-7) = 1 - 2^-23 = 0.99999988
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n * A; e += (long)gridDim.x * 256) {
+    const int j = (int)(e % A);
+    float u = (act[e] - central[j]) / delta[j];
+    u = u < -hi ? -hi : u > hi ? hi : u;     // NaN passes through, as torch.clip
+    out[e] = (float)atanh((double)u);        // correctly rounded: one launch per demonstration table, not per step
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t oly_bc_fit_ws(int batch, int in_dim, int act_dim) {
+  if (batch <= 0 || batch > MAX_BATCH || in_dim <= 0 || in_dim > IN_MAX || act_dim <= 0 || act_dim > MAX_ACT) return -1;
+  return (int64_t)ws_layout(batch).total;
+}
+
+extern "C" int oly_bc_targets(oly_ctx* ctx, int64_t n, int act_dim, const float* actions, const float* central,
+                              const float* delta, float* targets, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (n < 0 || n > 0x7fffffffL || act_dim <= 0 || act_dim > MAX_ACT)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_targets: bad shape (n %ld, act_dim %d; 1 <= act_dim <= %d)", (long)n, act_dim, MAX_ACT);
+  if (!actions || !central || !delta || !targets) OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_targets: NULL argument");
+  if (n == 0) return OLY_OK;
+  const long total = (long)n * act_dim;
+  const long blocks = (total + 255) / 256;
+  const unsigned grid = (unsigned)(blocks < 1024 ? blocks : 1024);
+  hipLaunchKernelGGL(bc_targets_kernel, dim3(grid), dim3(256), 0, oly_s(stream), (long)n, act_dim, actions, central, delta,
+                     targets);
+  OLY_LAUNCH_CHECK(ctx, "behavioural cloning targets kernel");
+  return OLY_OK;
+}
+
+extern "C" int oly_bc_fit_steps(oly_ctx* ctx, const oly_bc_fit* f, int n_steps, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (!f) OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: NULL argument");
+  const int in_dim = f->in_dim, A = f->act_dim, batch = f->batch;
+  if (n_steps < 0 || f->n_rows <= 0 || oly_bc_fit_ws(batch, in_dim, A) < 0)
+    OLY_FAIL(ctx, OLY_EINVAL,
+             "oly_bc_fit_steps: supported: 0 < batch <= %d, 0 < in_dim <= %d, 0 < act_dim <= %d, n_rows > 0, n_steps >= 0 "
+             "(got batch %d, in %d, act %d, n_rows %d, n_steps %d)",
+             MAX_BATCH, IN_MAX, MAX_ACT, batch, in_dim, A, f->n_rows, n_steps);
+  if (!f->states || !f->targets || !f->idx || !f->param || !f->m || !f->v || !f->packed || !f->ws || !f->out)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: NULL pointer in the argument block");
+  if (!(f->log_std_min <= f->log_std_max) || !(f->nll_eps > 0.f))
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: log_std_min <= log_std_max and nll_eps > 0 are required");
+  const WsL W = ws_layout(batch);
+  int rc = oly_fit::refuse_buffers(ctx, "oly_bc_fit_steps", f->ws_floats, W.total, f->ws, f->packed, f->step, n_steps);
+  if (rc != OLY_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(f->out) & 7) != 0 || (reinterpret_cast<uintptr_t>(f->colstats) & 7) != 0)
+    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: out and colstats must be 8-byte aligned");
+  if (n_steps == 0) return OLY_OK;
+  FitArgs a{};
+  a.in_dim = a.ds = in_dim;
+  a.n_rows = f->n_rows;
+  a.act_dim = A;
+  a.out_dim = 2 * A;
+  a.perm = f->idx;
+  a.x = f->states;
+  a.targets = f->targets;
+  a.colstats = f->colstats;
+  a.param = f->param;
+  a.m = f->m;
+  a.v = f->v;
+  a.packed = f->packed;
+  a.ws = f->ws;
+  a.ls_min = f->log_std_min;
+  a.ls_max = f->log_std_max;
+  a.nll_eps = f->nll_eps;
+  a.wd = f->weight_decay;
+  a.P = param_layout(in_dim, 2 * A);
+  a.W = W;
+  a.R = batch;
+  const float* p = f->param;
+  const ParamLayout& P = a.P;
+  rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 2 * A, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
+                      stream);
+  if (rc != OLY_OK) return rc;
+  const unsigned bit = in_dim <= 32 ? 1u : 2u;
+  if (!(ctx->bcfit_attr_done & bit)) {
+    OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(in_dim <= 32 ? bc_rows_kernel<2> : bc_rows_kernel<4>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
+    ctx->bcfit_attr_done |= bit;
+  }
+  a.off = 0;
+  hipLaunchKernelGGL(bc_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
+  const dim3 grid_a((unsigned)((batch + 15) / 16)), grid_b((unsigned)weight_tiles(in_dim, 2 * A));
+  for (int s = 0; s < n_steps; ++s) {
+    a.off = (long)s * batch;
+    a.off_next = a.off + batch;
+    a.Rn = s + 1 < n_steps ? batch : 0;
+    a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->eps, f->lr, (long)f->step + s + 1);
+    a.out = f->out + 3 * (size_t)s;
+    if (in_dim <= 32) hipLaunchKernelGGL(bc_rows_kernel<2>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
+    else hipLaunchKernelGGL(bc_rows_kernel<4>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
+    hipLaunchKernelGGL(bc_weights_kernel, grid_b, dim3(THREADS), 0, oly_s(stream), a);
+  }
+  OLY_LAUNCH_CHECK(ctx, "behavioural cloning fit kernels");
+  return OLY_OK;
+}

@@ -79,6 +79,7 @@ struct oly_ctx {
   unsigned gail_attr_done = 0;  // same for GAIL's discriminator: the forward's instantiations and the fit's row kernels (K18)
   int num_cu;
   unsigned ilact_attr_done = 0; // same for the acting step's instantiations (K21)
+  unsigned bcfit_attr_done = 0; // same for the behavioural-cloning fit's row kernels (K24)
 };
 
 #define OLY_FAIL(ctx, code, ...)                                \

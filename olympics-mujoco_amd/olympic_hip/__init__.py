@@ -4,4 +4,12 @@ Nothing here imports the CPU oracle; the HIP library is loaded lazily by olympic
 its absence is an error, not a fallback."""
 from . import _abi, specs  # noqa: F401
 
-__all__ = ["_abi", "specs"]
+__all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy"]
+
+
+def __getattr__(name):
+    # behavioural cloning (bc.py, K24); resolved on first use so that importing the package stays free of torch
+    if name in ("DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy"):
+        from . import bc
+        return getattr(bc, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -240,6 +240,21 @@ class TRPOStep(C.Structure):
                 ("ws_floats", C.c_int64), ("stepdir_out", vp), ("full_step_out", vp), ("scal_out", vp)]
 
 
+class BCFit(C.Structure):
+    """oly_bc_fit (K24): the behavioural-cloning fit state for oly_bc_fit_steps."""
+    _fields_ = [("in_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32), ("n_rows", C.c_int32),
+                ("step", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("nll_eps", C.c_float), ("pad", C.c_int32), ("states", vp), ("targets", vp), ("idx", vp),
+                ("colstats", vp), ("param", vp), ("m", vp), ("v", vp), ("packed", vp), ("ws", vp),
+                ("ws_floats", C.c_int64), ("out", vp)]
+
+
+OLY_BC_MAX_BATCH, OLY_BC_MAX_ACT = 4096, 16
+# out [n_steps, 3] of oly_bc_fit_steps: the reference's tags (behavioral_cloning.py:85,88,94)
+BC_LOG_TAGS = ("GaussianNLLLoss", "Squashed Gaussian Entropy", "MSELoss (between mean & target actions)")
+
+
 SIGNATURES = {
     "oly_strerror": (C.c_char_p, [C.c_int]),
     "oly_last_error": (C.c_char_p, [vp]),
@@ -356,6 +371,9 @@ SIGNATURES = {
     "oly_il_act": (C.c_int, [vp, C.POINTER(ILAct), vp]),
     "oly_il_reset_where": (C.c_int, [vp, C.POINTER(ILReset), vp]),
     "oly_a3_reset_draw": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, C.c_double, C.c_int, vp]),
+    "oly_bc_fit_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "oly_bc_targets": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp]),
+    "oly_bc_fit_steps": (C.c_int, [vp, C.POINTER(BCFit), C.c_int, vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

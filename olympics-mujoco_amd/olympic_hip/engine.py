@@ -910,6 +910,78 @@ class Engine:
         self.ctx.call("oly_disc_fit_epoch_pair", C.byref(f), C.byref(pair), ptr(perm), n, batch, self._s())
         return loss_out
 
+    # -------------------------------------------------------------- K24 (behavioural cloning: targets, fit)
+    def bc_targets(self, actions, central, delta, out=None):
+        """oly_bc_targets: atanh(clip((actions - central) / delta, -+0.99999988)) for the whole table in one launch
+        (behavioral_cloning.py:63-66).  actions [n,A] f32, central / delta [A] f32; returns targets [n,A] f32."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(actions, torch.Tensor) or actions.dim() != 2:
+            raise OlyError("bc_targets: actions is a [n,A] tensor")
+        n, A = (int(v) for v in actions.shape)
+        if not 0 < A <= _abi.OLY_BC_MAX_ACT:
+            raise OlyError(f"bc_targets: unsupported act_dim={A} (0 < act_dim <= {_abi.OLY_BC_MAX_ACT})")
+        _req(actions, "actions", (n, A), f32, dv)
+        _req(central, "central", (A,), f32, dv)
+        _req(delta, "delta", (A,), f32, dv)
+        out = _req(out if out is not None else self._new((n, A), f32), "targets", (n, A), f32, dv)
+        self.ctx.call("oly_bc_targets", C.c_int64(n), A, ptr(actions), ptr(central), ptr(delta), ptr(out), self._s())
+        return out
+
+    def bc_fit_ws(self, batch, in_dim, act_dim):
+        """A workspace for bc_fit_steps with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_bc_fit_ws(int(batch), int(in_dim), int(act_dim)))
+        if n < 0:
+            raise OlyError(f"bc_fit: unsupported batch={batch} in={in_dim} act={act_dim} (0 < batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, in <= 64, act <= {_abi.OLY_BC_MAX_ACT})")
+        return self._new((n,), torch.float32)
+
+    def bc_fit_steps(self, states, targets, idx, colstats, param, m, v, packed, ws, step, lr, beta1=0.9, beta2=0.999,
+                     eps=1e-8, weight_decay=0.0, log_std_min=-20.0, log_std_max=2.0, nll_eps=1e-6, out=None):
+        """oly_bc_fit_steps: idx.shape[0] iterations of BehavioralCloning.fit_offline in one call.  states [n,in] f32 raw
+        rows, targets [n,A] f32 (bc_targets), idx [n_steps,batch] int32 the rows of every step, colstats [3,in] f64 the
+        Standardizer's running sums or None (no Standardizer), param / m / v flat in torch order (W1 | b1 | W2 | b2 |
+        W3 [2A,256] | b3), packed the ilmlp_pack stream (re-packed from param, then kept current); step = Adam steps
+        taken before.  Returns out [n_steps,3] f64: the loss, the Gaussian entropy, the mean squared error."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(states, torch.Tensor) or states.dim() != 2:
+            raise OlyError("bc_fit_steps: states is a [n,in] tensor")
+        if not isinstance(targets, torch.Tensor) or targets.dim() != 2:
+            raise OlyError("bc_fit_steps: targets is a [n,A] tensor")
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
+            raise OlyError("bc_fit_steps: idx is a [n_steps,batch] tensor")
+        n, in_dim = (int(t) for t in states.shape)
+        A = int(targets.shape[1])
+        n_steps, batch = (int(t) for t in idx.shape)
+        nws = int(lib().oly_bc_fit_ws(batch, in_dim, A))
+        if nws < 0 or n < 1:
+            raise OlyError(f"bc_fit_steps: unsupported batch={batch} in={in_dim} act={A} n={n} (0 < batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, in <= 64, act <= {_abi.OLY_BC_MAX_ACT}, n >= 1)")
+        if not float(log_std_min) <= float(log_std_max) or not float(nll_eps) > 0.0:
+            raise OlyError("bc_fit_steps: log_std_min <= log_std_max and nll_eps > 0 are required")
+        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 2 * A * 256 + 2 * A
+        _req(states, "states", (n, in_dim), f32, dv)
+        _req(targets, "targets", (n, A), f32, dv)
+        _req(idx, "idx", (n_steps, batch), torch.int32, dv)
+        _req(colstats, "colstats", (3, in_dim), f64, dv, optional=True)
+        for t, name in ((param, "param"), (m, "m"), (v, "v")):
+            _req(t, name, (n_par,), f32, dv)
+        npk = int(lib().oly_ilmlp_packed_floats(in_dim, 512, 256, 2 * A))
+        _req(packed, "packed", (npk,), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        out = _req(out if out is not None else self._new((n_steps, 3), f64), "out", (n_steps, 3), f64, dv)
+        if n_steps == 0:
+            return out
+        f = _abi.BCFit(in_dim=in_dim, act_dim=A, batch=batch, n_rows=n, step=int(step), lr=float(lr), beta1=float(beta1),
+                       beta2=float(beta2), eps=float(eps), weight_decay=float(weight_decay),
+                       log_std_min=float(log_std_min), log_std_max=float(log_std_max), nll_eps=float(nll_eps),
+                       states=states.data_ptr(), targets=targets.data_ptr(), idx=idx.data_ptr(), colstats=ptr(colstats),
+                       param=param.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(),
+                       ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr())
+        self.ctx.call("oly_bc_fit_steps", C.byref(f), n_steps, self._s())
+        return out
+
     # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
     def _gail_packed_floats(self, D):
         from ._ffi import lib
