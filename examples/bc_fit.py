@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--eval-episodes", type=int, default=0, help="episodes per ILCore.evaluate (default: one per environment)")
     ap.add_argument("--horizon", type=int, default=20, help="the environment's horizon for this example (0: the spec's 1000)")
     ap.add_argument("--log", action="store_true", help="print the trainer's scalars under the reference's names")
+    ap.add_argument("--fused-act", action="store_true", help="the student acts through one oly_sg_act call per vec step (K25)")
+    ap.add_argument("--empirical-entropy", action="store_true",
+                    help="the whole of the reference's logging(): the sampled second forward of the logged iterations (K25)")
     ap.add_argument("--json", default=None, metavar="FILE", help="write the run's figures to FILE")
     args = ap.parse_args()
     torch.manual_seed(0)
@@ -69,9 +72,10 @@ def main():
     # ---- the student: in -> [512, 256] -> 2A with its own Standardizer, the reference's defaults
     s_lins = [torch.nn.Linear(n_obs, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 2 * n_act)]
     student = DeviceSquashedGaussianPolicy(eng, s_lins, np.asarray(space.low), np.asarray(space.high),
-                                           standardizer=DeviceStandardizer(eng, n_obs))
+                                           standardizer=DeviceStandardizer(eng, n_obs), fused_act=args.fused_act)
     bc = DeviceBehavioralCloning(eng, student, demo, lr=1e-3, batch_size=args.batch,
-                                 logging_iter=max(1, args.steps // 10), sw=PrintingWriter() if args.log else None)
+                                 logging_iter=max(1, args.steps // 10), sw=PrintingWriter() if args.log else None,
+                                 empirical_entropy=args.empirical_entropy)
     calls = max(1, min(args.calls, args.steps))
     outs = [bc.fit_offline(args.steps // calls + (i < args.steps % calls), generator=gen) for i in range(calls)]
     out = torch.cat(outs).cpu().numpy()

@@ -23,12 +23,17 @@
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits, and a call of n steps
 // leaves the bits of n calls of one step (the prologue rebuilds from param exactly what launch B keeps current).
 // Adam, the statistics fold and the weights kernel's tail are fit_common.h's, shared with K15, K16 and K18.
+//
+//   oly_bc_fit_steps_log  the same with the whole of logging() (:82-94): on a logging step, after launch B,
+//   L  K25's kernel (k25_sg_act.hip) on the rows idx[s] with the stepped stream and the statistics that hold them twice
+//   F  bc_log_fold_kernel  -mean(log_prob) into the step's fourth scalar; colstats += minibatch s a second time.
 #include <cstdlib>
 
 #include "fit_common.h"
 #include "ilmlp_common.h"
 #include "mlp_tiles.h"
 #include "oly_common.h"
+#include "sg_act.h"
 
 namespace {
 using namespace oly_ilmlp;
@@ -438,6 +443,25 @@ __global__ __launch_bounds__(256) void bc_targets_kernel(long n, int A, const fl
   }
 }
 
+// The logged fit's fourth scalar and the Standardizer's second take of the minibatch (logging(), behavioral_cloning.py:90-92).
+// One workgroup: thread t adds the log-probabilities of rows 16 t .. 16 t + 15 in order (K25 left them after the
+// workspace), the partials meet by loss_tree's halving tree, out[3] = -sum / R; colstats += the minibatch's sums again.
+__global__ __launch_bounds__(THREADS) void bc_log_fold_kernel(FitArgs a) {
+  __shared__ double dred[THREADS];
+  const int tid = threadIdx.x, R = a.R;
+  const float* lp = a.ws + a.W.total;
+  double s = 0.0;
+  for (int r = 16 * tid; r < min(R, 16 * tid + 16); ++r) s += (double)lp[r];
+  dred[tid] = s;
+  __syncthreads();
+  for (int h = THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) dred[tid] += dred[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) a.out[3] = -dred[0] / (double)R;      // "Squashed Gaussian Entropy (Empirical)"
+  if (a.colstats) oly_fit::colstats_add(a, R);
+}
+
 }  // namespace
 
 extern "C" int64_t oly_bc_fit_ws(int batch, int in_dim, int act_dim) {
@@ -461,24 +485,34 @@ extern "C" int oly_bc_targets(oly_ctx* ctx, int64_t n, int act_dim, const float*
   return OLY_OK;
 }
 
-extern "C" int oly_bc_fit_steps(oly_ctx* ctx, const oly_bc_fit* f, int n_steps, oly_stream stream) {
-  if (!ctx) return OLY_EINVAL;
-  if (!f) OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: NULL argument");
+// What oly_bc_fit_steps and oly_bc_fit_steps_log share.  lg == NULL: oly_bc_fit_steps (out [n_steps, 3], its launches
+// alone).  lg: out [n_steps, 4], and a step s with (iter0 + s) % logging_iter == 0 runs two more launches after launch B.
+static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_steps, const oly_bc_fit_log* lg,
+                     oly_stream stream) {
   const int in_dim = f->in_dim, A = f->act_dim, batch = f->batch;
   if (n_steps < 0 || f->n_rows <= 0 || oly_bc_fit_ws(batch, in_dim, A) < 0)
     OLY_FAIL(ctx, OLY_EINVAL,
-             "oly_bc_fit_steps: supported: 0 < batch <= %d, 0 < in_dim <= %d, 0 < act_dim <= %d, n_rows > 0, n_steps >= 0 "
+             "%s: supported: 0 < batch <= %d, 0 < in_dim <= %d, 0 < act_dim <= %d, n_rows > 0, n_steps >= 0 "
              "(got batch %d, in %d, act %d, n_rows %d, n_steps %d)",
-             MAX_BATCH, IN_MAX, MAX_ACT, batch, in_dim, A, f->n_rows, n_steps);
+             name, MAX_BATCH, IN_MAX, MAX_ACT, batch, in_dim, A, f->n_rows, n_steps);
   if (!f->states || !f->targets || !f->idx || !f->param || !f->m || !f->v || !f->packed || !f->ws || !f->out)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: NULL pointer in the argument block");
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL pointer in the argument block", name);
   if (!(f->log_std_min <= f->log_std_max) || !(f->nll_eps > 0.f))
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: log_std_min <= log_std_max and nll_eps > 0 are required");
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: log_std_min <= log_std_max and nll_eps > 0 are required", name);
   const WsL W = ws_layout(batch);
-  int rc = oly_fit::refuse_buffers(ctx, "oly_bc_fit_steps", f->ws_floats, W.total, f->ws, f->packed, f->step, n_steps);
+  const size_t ws_need = lg ? (size_t)oly_bc_fit_log_ws(batch, in_dim, A) : W.total;
+  int rc = oly_fit::refuse_buffers(ctx, name, f->ws_floats, ws_need, f->ws, f->packed, f->step, n_steps);
   if (rc != OLY_OK) return rc;
   if ((reinterpret_cast<uintptr_t>(f->out) & 7) != 0 || (reinterpret_cast<uintptr_t>(f->colstats) & 7) != 0)
-    OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: out and colstats must be 8-byte aligned");
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: out and colstats must be 8-byte aligned", name);
+  if (lg) {
+    if (lg->logging_iter < 1 || lg->iter0 < 0 || (long)lg->iter0 + n_steps > 0x7fffffffL)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: logging_iter >= 1 and iter0 >= 0 are required (got %d, %d)", name, lg->logging_iter,
+               lg->iter0);
+    // the first logging step of the call, if it has one
+    const long first = ((long)lg->logging_iter - lg->iter0 % lg->logging_iter) % lg->logging_iter;
+    if (first < n_steps && !lg->eps) OLY_FAIL(ctx, OLY_EINVAL, "%s: a step of the call logs and eps is NULL", name);
+  }
   if (n_steps == 0) return OLY_OK;
   FitArgs a{};
   a.in_dim = a.ds = in_dim;
@@ -515,16 +549,60 @@ extern "C" int oly_bc_fit_steps(oly_ctx* ctx, const oly_bc_fit* f, int n_steps, 
   a.off = 0;
   hipLaunchKernelGGL(bc_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   const dim3 grid_a((unsigned)((batch + 15) / 16)), grid_b((unsigned)weight_tiles(in_dim, 2 * A));
+  const size_t out_w = lg ? 4 : 3;
+  long logged = 0;
   for (int s = 0; s < n_steps; ++s) {
     a.off = (long)s * batch;
     a.off_next = a.off + batch;
     a.Rn = s + 1 < n_steps ? batch : 0;
     a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->eps, f->lr, (long)f->step + s + 1);
-    a.out = f->out + 3 * (size_t)s;
+    a.out = f->out + out_w * (size_t)s;
     if (in_dim <= 32) hipLaunchKernelGGL(bc_rows_kernel<2>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
     else hipLaunchKernelGGL(bc_rows_kernel<4>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
     hipLaunchKernelGGL(bc_weights_kernel, grid_b, dim3(THREADS), 0, oly_s(stream), a);
+    if (lg && ((long)lg->iter0 + s) % lg->logging_iter == 0) {
+      // logging() (behavioral_cloning.py:82-94): compute_action_and_log_prob on the minibatch.  colstats holds idx[s] once
+      // (launch B) and the workspace's delta its column sums (launch A): the forward standardises with colstats + delta,
+      // the fold adds delta to colstats.
+      oly_sg::Args g{};
+      g.N = batch;
+      g.in_dim = in_dim;
+      g.act_dim = A;
+      g.x = f->states;
+      g.rows = f->idx + a.off;
+      g.n_rows = f->n_rows;
+      g.colstats = f->colstats;
+      g.extra = f->colstats ? reinterpret_cast<const double*>(f->ws + W.delta) : nullptr;
+      g.extra_cnt = (double)batch;
+      g.packed = f->packed;
+      g.ls_min = f->log_std_min;
+      g.ls_max = f->log_std_max;
+      g.eps = lg->eps + (size_t)logged * batch * A;
+      g.log_prob = f->ws + W.total;
+      rc = oly_sg::launch(ctx, g, stream);
+      if (rc != OLY_OK) return rc;
+      hipLaunchKernelGGL(bc_log_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), a);
+      ++logged;
+    }
   }
   OLY_LAUNCH_CHECK(ctx, "behavioural cloning fit kernels");
   return OLY_OK;
+}
+
+extern "C" int oly_bc_fit_steps(oly_ctx* ctx, const oly_bc_fit* f, int n_steps, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (!f) OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps: NULL argument");
+  return fit_steps(ctx, "oly_bc_fit_steps", f, n_steps, nullptr, stream);
+}
+
+// the logged fit's workspace: oly_bc_fit_steps' and the minibatch's log-probabilities [batch rounded up to 16] f32
+extern "C" int64_t oly_bc_fit_log_ws(int batch, int in_dim, int act_dim) {
+  const int64_t n = oly_bc_fit_ws(batch, in_dim, act_dim);
+  return n < 0 ? n : n + (batch + 15) / 16 * 16;
+}
+
+extern "C" int oly_bc_fit_steps_log(oly_ctx* ctx, const oly_bc_fit_log* f, int n_steps, oly_stream stream) {
+  if (!ctx) return OLY_EINVAL;
+  if (!f) OLY_FAIL(ctx, OLY_EINVAL, "oly_bc_fit_steps_log: NULL argument");
+  return fit_steps(ctx, "oly_bc_fit_steps_log", &f->fit, n_steps, f, stream);
 }

@@ -80,6 +80,7 @@ struct oly_ctx {
   int num_cu;
   unsigned ilact_attr_done = 0; // same for the acting step's instantiations (K21)
   unsigned bcfit_attr_done = 0; // same for the behavioural-cloning fit's row kernels (K24)
+  unsigned sgact_attr_done = 0; // same for the squashed-Gaussian act's instantiations (K25)
 };
 
 #define OLY_FAIL(ctx, code, ...)                                \

@@ -253,6 +253,21 @@ class BCFit(C.Structure):
 OLY_BC_MAX_BATCH, OLY_BC_MAX_ACT = 4096, 16
 # out [n_steps, 3] of oly_bc_fit_steps: the reference's tags (behavioral_cloning.py:85,88,94)
 BC_LOG_TAGS = ("GaussianNLLLoss", "Squashed Gaussian Entropy", "MSELoss (between mean & target actions)")
+# column 3 of oly_bc_fit_steps_log's out [n_steps, 4] (behavioral_cloning.py:92)
+BC_LOG_TAG_EMPIRICAL = "Squashed Gaussian Entropy (Empirical)"
+
+
+class BCFitLog(C.Structure):
+    """oly_bc_fit_log (K24 + K25): oly_bc_fit with the sampled second forward of logging()."""
+    _fields_ = [("fit", BCFit), ("logging_iter", C.c_int32), ("iter0", C.c_int32), ("eps", vp)]
+
+
+class SGAct(C.Structure):
+    """oly_sg_act_args (K25): the squashed-Gaussian policy's act and log-probability in one call."""
+    _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("act_dim", C.c_int32), ("update_stats", C.c_int32), ("x", vp),
+                ("colstats", vp), ("packed", vp), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("central", vp),
+                ("delta", vp), ("eps", vp), ("action", vp), ("log_prob", vp), ("mu", vp), ("log_sigma", vp), ("ctrl", vp),
+                ("out_flags", C.c_int32), ("pad", C.c_int32)]
 
 
 SIGNATURES = {
@@ -374,6 +389,9 @@ SIGNATURES = {
     "oly_bc_fit_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "oly_bc_targets": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp]),
     "oly_bc_fit_steps": (C.c_int, [vp, C.POINTER(BCFit), C.c_int, vp]),
+    "oly_bc_fit_log_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "oly_bc_fit_steps_log": (C.c_int, [vp, C.POINTER(BCFitLog), C.c_int, vp]),
+    "oly_sg_act": (C.c_int, [vp, C.POINTER(SGAct), vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

@@ -4,7 +4,8 @@ policy it trains (IQ_Learn_Policy, imitation_lib/imitation/iq_sac.py:18-167).
   IQ_Learn_Policy(Regressor(FullyConnectedNetwork(in -> [512, 256] -> 2A)), min_a, max_a, log_std_min, log_std_max)
       get_mu_log_sigma / distribution / compute_action_and_log_prob / entropy_from_logsigma / get_central_delta
                                                          -> DeviceSquashedGaussianPolicy (K16's forward, oly_ilmlp_forward,
-                                                            then torch elementwise operations; acting is not a hot path)
+                                                            then torch elementwise operations; fused_act=True: one
+                                                            oly_sg_act call, K25)
   BehavioralCloning.fit_offline (:46-80) and logging (:82-94)
                                                          -> DeviceBehavioralCloning.fit_offline (K24, oly_bc_fit_steps:
                                                             every step of a call on the device, no host synchronisation)
@@ -14,7 +15,9 @@ policy it trains (IQ_Learn_Policy, imitation_lib/imitation/iq_sac.py:18-167).
 Stated differences from the reference: a minibatch is the first `batch_size` entries of a fresh device permutation, as
 next(minibatch_generator(...)) gives (rows within a step are distinct): the same distribution, another sequence than
 numpy's; a given `idx` is used as it is.  "Squashed Gaussian Entropy (Empirical)" needs a sampled second forward per
-step and is not logged.  Entropy projection (use_entropy_projec, off by default in the reference) is not built.
+logged step, which also feeds the Standardizer the minibatch a second time: it is opt-in (empirical_entropy=True, K25);
+without it a fit with a Standardizer holds every minibatch once where the reference holds a logged one twice.  Entropy
+projection (use_entropy_projec, off by default in the reference) is not built.
 """
 import numpy as np
 import torch
@@ -36,9 +39,12 @@ class DeviceSquashedGaussianPolicy:
     net: the reference's FullyConnectedNetwork (its `_linears`) or a list of its three nn.Linear layers, in <= 64 -> 512
     -> 256 -> 2A, A <= 16.  standardizer: a DeviceStandardizer or None; with one, every forward the reference runs through
     FullyConnectedNetwork.forward adds its rows to the statistics first (networks.py:68-81): get_mu_log_sigma and what
-    is built on it do, predict does not."""
+    is built on it do, predict does not.  fused_act=True: act and compute_action_and_log_prob are one oly_sg_act call
+    (K25) instead of the forward and torch's elementwise operations; the contract, the arguments and the draws from
+    `generator` are the same, the values agree to float32 rounding (the tanh is correctly rounded, the log-probability
+    is summed in float64)."""
 
-    def __init__(self, engine, net, min_a, max_a, standardizer=None, log_std_min=-20, log_std_max=2):
+    def __init__(self, engine, net, min_a, max_a, standardizer=None, log_std_min=-20, log_std_max=2, fused_act=False):
         lins = list(getattr(net, "_linears", net))
         if len(lins) != 3:
             raise OlyError(f"DeviceSquashedGaussianPolicy: expected three Linear layers, got {len(lins)}")
@@ -66,6 +72,7 @@ class DeviceSquashedGaussianPolicy:
         self.central = torch.as_tensor((0.5 * (max_a + min_a)).astype(np.float32), device=dev)
         self.log_std_min, self.log_std_max = float(log_std_min), float(log_std_max)
         self.eps_log_prob = 1e-6
+        self.fused_act = bool(fused_act)
         with torch.no_grad():
             self.param = torch.cat([t.detach().reshape(-1).to(device=dev, dtype=torch.float32)
                                     for lin in lins for t in (lin.weight, lin.bias)]).contiguous()
@@ -123,12 +130,27 @@ class DeviceSquashedGaussianPolicy:
             return torch.randn((n, self.act_dim), dtype=torch.float32, device=self.eng.device, generator=generator)
         return eps.reshape(n, self.act_dim).to(torch.float32)
 
+    def _fused(self, obs, eps, want):
+        """One oly_sg_act call on obs's rows: the statistics take them first, as get_mu_log_sigma does."""
+        colstats = self._colstats()
+        o = self.eng.sg_act(self._rows(obs), self.packed, self.central, self.delta, colstats=colstats,
+                            eps=None if eps is None else eps.contiguous(), update_stats=colstats is not None,
+                            log_std_min=self.log_std_min, log_std_max=self.log_std_max, want=want)
+        if colstats is not None:
+            self.stand._fresh = False
+        return o
+
     @torch.no_grad()
     def act(self, obs, generator=None, eps=None, deterministic=False, ctrl=False):
         """draw_action for the collection loop (ILCore's contract): the statistics take obs's rows, action =
         tanh(mu + exp(log_sigma) eps) delta + central (iq_sac.py:102-130); deterministic=True: the squashed mean,
         nothing is drawn (use_mean).  eps None: drawn from `generator`.  With ctrl=True the engine's configured model's
         clamped control vector of that action (oly_il_ctrl).  Returns (action [n,A], ctrl [n,nu] or None)."""
+        if self.fused_act:
+            x = self._rows(obs)
+            noise = None if deterministic else self._noise(int(x.shape[0]), eps, generator)
+            o = self._fused(x, noise, ("ctrl",) if ctrl else ())
+            return o["action"], o["ctrl"]
         mu, log_sigma = self.get_mu_log_sigma(obs)
         a_raw = mu if deterministic else mu + log_sigma.exp() * self._noise(int(mu.shape[0]), eps, generator)
         action = (torch.tanh(a_raw) * self.delta + self.central).contiguous()
@@ -138,6 +160,10 @@ class DeviceSquashedGaussianPolicy:
     def compute_action_and_log_prob(self, obs, generator=None, eps=None):
         """compute_action_and_log_prob_t (iq_sac.py:102-130): the sampled action and its log-probability [n] with the
         tanh correction log(1 - a^2 + 1e-6), device tensors."""
+        if self.fused_act:
+            x = self._rows(obs)
+            o = self._fused(x, self._noise(int(x.shape[0]), eps, generator), ("log_prob",))
+            return o["action"], o["log_prob"]
         mu, log_sigma = self.get_mu_log_sigma(obs)
         dist = torch.distributions.Normal(mu, log_sigma.exp())
         a_raw = mu + log_sigma.exp() * self._noise(int(mu.shape[0]), eps, generator)
@@ -198,10 +224,15 @@ class DeviceBehavioralCloning:
     `states` [n,in] and `actions` [n,A] (device tensors or numpy arrays); `next_states` and `absorbing` are accepted and
     ignored, as the reference ignores them.  The optimiser is torch.optim.Adam(lr, betas, eps, weight_decay) (amsgrad
     off) over torch.nn.GaussianNLLLoss(); its step count persists across fit_offline calls.  sw: an object with
-    add_scalar(name, value, iteration), or None."""
+    add_scalar(name, value, iteration), or None.
+
+    empirical_entropy=True: the whole of logging() (:82-94).  Every logging_iter iterations the reference calls
+    policy.compute_action_and_log_prob on the minibatch: the Standardizer takes the minibatch's rows a second time, the
+    forward runs with the weights Adam has just stepped, and -mean(log_prob) of a sample is logged as "Squashed Gaussian
+    Entropy (Empirical)".  fit_offline then goes through oly_bc_fit_steps_log (K24 + K25) and returns four columns."""
 
     def __init__(self, engine, policy, demonstrations, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, batch_size=32,
-                 logging_iter=1, sw=None):
+                 logging_iter=1, sw=None, empirical_entropy=False):
         if not isinstance(policy, DeviceSquashedGaussianPolicy):
             raise OlyError("DeviceBehavioralCloning: policy must be a DeviceSquashedGaussianPolicy")
         for k in ("states", "actions"):
@@ -235,7 +266,9 @@ class DeviceBehavioralCloning:
         self.exp_avg_sq = torch.zeros_like(policy.param)
         self.step = 0
         self.iter = 0
-        self._ws = engine.bc_fit_ws(self.batch, policy.in_dim, policy.act_dim)
+        self.empirical_entropy = bool(empirical_entropy)
+        self._ws = (engine.bc_fit_log_ws if self.empirical_entropy else engine.bc_fit_ws)(self.batch, policy.in_dim,
+                                                                                         policy.act_dim)
 
     def fit(self, dataset):
         raise AttributeError("This is a behavior cloning algorithms, which is meant to run offline. It is not supposed"
@@ -253,10 +286,15 @@ class DeviceBehavioralCloning:
         return out
 
     @torch.no_grad()
-    def fit_offline(self, n_steps, generator=None, idx=None):
+    def fit_offline(self, n_steps, generator=None, idx=None, eps=None):
         """n_steps iterations of fit_offline in ONE oly_bc_fit_steps call.  idx: [n_steps, batch] int32 device rows, or
         None (drawn from `generator`).  Returns the [n_steps, 3] f64 device block of LOG_NAMES' scalars; with a writer
-        they go to sw.add_scalar under the reference's names every logging_iter iterations (which reads them back)."""
+        they go to sw.add_scalar under the reference's names every logging_iter iterations (which reads them back).
+
+        With empirical_entropy the call is ONE oly_bc_fit_steps_log and the block is [n_steps, 4]: column 3 is "Squashed
+        Gaussian Entropy (Empirical)" on the iterations that log (self.iter + s a multiple of logging_iter) and NaN on
+        the others.  eps: [n_logged, batch, A] f32 standard normal noise of the logging steps in order, or None: drawn
+        from `generator` AFTER idx (first every step's permutation keys, then one randn of that shape)."""
         n_steps = int(n_steps)
         if n_steps < 0:
             raise OlyError(f"DeviceBehavioralCloning.fit_offline: n_steps={n_steps}")
@@ -266,6 +304,10 @@ class DeviceBehavioralCloning:
             raise OlyError(f"DeviceBehavioralCloning.fit_offline: idx must be a [{n_steps}, {self.batch}] int32 tensor")
         p = self.policy
         colstats = p._colstats()
+        if self.empirical_entropy:
+            return self._fit_logged(n_steps, generator, idx, eps, colstats)
+        if eps is not None:
+            raise OlyError("DeviceBehavioralCloning.fit_offline: eps is the noise of empirical_entropy=True")
         out = self.eng.bc_fit_steps(self.states, self.targets, idx, colstats, p.param, self.exp_avg, self.exp_avg_sq,
                                     p.packed, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
                                     eps=self.eps, weight_decay=self.weight_decay, log_std_min=p.log_std_min,
@@ -278,6 +320,31 @@ class DeviceBehavioralCloning:
                 if (self.iter + s) % self.logging_iter == 0:
                     for k, name in enumerate(LOG_NAMES):
                         self.sw.add_scalar(name, float(host[s, k]), self.iter + s)
+        self.step += n_steps
+        self.iter += n_steps
+        return out
+
+    def _fit_logged(self, n_steps, generator, idx, eps, colstats):
+        p = self.policy
+        logged = self.eng.bc_logged_steps(n_steps, self.logging_iter, self.iter)
+        shape = (len(logged), self.batch, p.act_dim)
+        if eps is None:
+            eps = torch.randn(shape, dtype=torch.float32, device=self.eng.device, generator=generator)
+        elif not isinstance(eps, torch.Tensor) or tuple(eps.shape) != shape:
+            raise OlyError(f"DeviceBehavioralCloning.fit_offline: eps must be a {list(shape)} float32 tensor "
+                           f"({len(logged)} of the {n_steps} steps log)")
+        out = self.eng.bc_fit_steps_log(self.states, self.targets, idx, colstats, p.param, self.exp_avg, self.exp_avg_sq,
+                                        p.packed, self._ws, self.step, self.lr, self.logging_iter, self.iter,
+                                        eps.to(torch.float32).contiguous(), beta1=self.betas[0], beta2=self.betas[1],
+                                        eps=self.eps, weight_decay=self.weight_decay, log_std_min=p.log_std_min,
+                                        log_std_max=p.log_std_max, nll_eps=self.nll_eps)
+        if colstats is not None and n_steps > 0:
+            p.stand._fresh = False
+        if self.sw is not None and n_steps > 0:
+            host = out.cpu().numpy()
+            for s in logged:
+                for k, name in enumerate(LOG_NAMES + (_abi.BC_LOG_TAG_EMPIRICAL,)):
+                    self.sw.add_scalar(name, float(host[s, k]), self.iter + s)
         self.step += n_steps
         self.iter += n_steps
         return out

@@ -982,6 +982,130 @@ class Engine:
         self.ctx.call("oly_bc_fit_steps", C.byref(f), n_steps, self._s())
         return out
 
+    def bc_fit_log_ws(self, batch, in_dim, act_dim):
+        """A workspace for bc_fit_steps_log with minibatches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_bc_fit_log_ws(int(batch), int(in_dim), int(act_dim)))
+        if n < 0:
+            raise OlyError(f"bc_fit: unsupported batch={batch} in={in_dim} act={act_dim} (0 < batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, in <= 64, act <= {_abi.OLY_BC_MAX_ACT})")
+        return self._new((n,), torch.float32)
+
+    @staticmethod
+    def bc_logged_steps(n_steps, logging_iter, iter0):
+        """The steps s < n_steps of a call that log: (iter0 + s) % logging_iter == 0."""
+        return [s for s in range(int(n_steps)) if (int(iter0) + s) % int(logging_iter) == 0]
+
+    def bc_fit_steps_log(self, states, targets, idx, colstats, param, m, v, packed, ws, step, lr, logging_iter, iter0, noise,
+                         beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, log_std_min=-20.0, log_std_max=2.0,
+                         nll_eps=1e-6, out=None):
+        """oly_bc_fit_steps_log: bc_fit_steps with the sampled second forward of BehavioralCloning.logging() on every
+        step s with (iter0 + s) % logging_iter == 0.  noise [n_logged, batch, A] f32: the standard normal draws of the
+        logging steps in order; ws from bc_fit_log_ws.  Returns out [n_steps,4] f64: bc_fit_steps' three scalars and
+        -mean(log_prob); column 3 of a step that does not log is not written (NaN in a buffer made here)."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(states, torch.Tensor) or states.dim() != 2:
+            raise OlyError("bc_fit_steps_log: states is a [n,in] tensor")
+        if not isinstance(targets, torch.Tensor) or targets.dim() != 2:
+            raise OlyError("bc_fit_steps_log: targets is a [n,A] tensor")
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
+            raise OlyError("bc_fit_steps_log: idx is a [n_steps,batch] tensor")
+        n, in_dim = (int(t) for t in states.shape)
+        A = int(targets.shape[1])
+        n_steps, batch = (int(t) for t in idx.shape)
+        nws = int(lib().oly_bc_fit_log_ws(batch, in_dim, A))
+        if nws < 0 or n < 1:
+            raise OlyError(f"bc_fit_steps_log: unsupported batch={batch} in={in_dim} act={A} n={n} (0 < batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, in <= 64, act <= {_abi.OLY_BC_MAX_ACT}, n >= 1)")
+        if not float(log_std_min) <= float(log_std_max) or not float(nll_eps) > 0.0:
+            raise OlyError("bc_fit_steps_log: log_std_min <= log_std_max and nll_eps > 0 are required")
+        if int(logging_iter) < 1 or int(iter0) < 0:
+            raise OlyError(f"bc_fit_steps_log: logging_iter={logging_iter} (>= 1), iter0={iter0} (>= 0)")
+        n_logged = len(self.bc_logged_steps(n_steps, logging_iter, iter0))
+        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 2 * A * 256 + 2 * A
+        _req(states, "states", (n, in_dim), f32, dv)
+        _req(targets, "targets", (n, A), f32, dv)
+        _req(idx, "idx", (n_steps, batch), torch.int32, dv)
+        _req(colstats, "colstats", (3, in_dim), f64, dv, optional=True)
+        for t, name in ((param, "param"), (m, "m"), (v, "v")):
+            _req(t, name, (n_par,), f32, dv)
+        npk = int(lib().oly_ilmlp_packed_floats(in_dim, 512, 256, 2 * A))
+        _req(packed, "packed", (npk,), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        _req(noise, "noise", (n_logged, batch, A), f32, dv, optional=n_logged == 0)
+        if out is None:
+            out = torch.full((n_steps, 4), float("nan"), dtype=f64, device=dv)
+        _req(out, "out", (n_steps, 4), f64, dv)
+        if n_steps == 0:
+            return out
+        fit = _abi.BCFit(in_dim=in_dim, act_dim=A, batch=batch, n_rows=n, step=int(step), lr=float(lr), beta1=float(beta1),
+                         beta2=float(beta2), eps=float(eps), weight_decay=float(weight_decay),
+                         log_std_min=float(log_std_min), log_std_max=float(log_std_max), nll_eps=float(nll_eps),
+                         states=states.data_ptr(), targets=targets.data_ptr(), idx=idx.data_ptr(), colstats=ptr(colstats),
+                         param=param.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(),
+                         ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr())
+        f = _abi.BCFitLog(fit=fit, logging_iter=int(logging_iter), iter0=int(iter0), eps=ptr(noise))
+        self.ctx.call("oly_bc_fit_steps_log", C.byref(f), n_steps, self._s())
+        return out
+
+    # -------------------------------------------------------------- K25 (the squashed-Gaussian act and log-probability)
+    def sg_act(self, x, packed, central, delta, colstats=None, eps=None, update_stats=True, log_std_min=-20.0,
+               log_std_max=2.0, want=("log_prob",), ctrl_f64=False, out=None):
+        """oly_sg_act: compute_action_and_log_prob (iq_sac.py:102-151) on x [n,in] f32 in one call.  colstats [3,in] f64
+        takes the rows first (update_stats) and standardises them, None: no Standardizer.  packed: ilmlp_pack's stream of
+        the network in -> 512 -> 256 -> 2A; central / delta [A] f32; eps [n,A] f32 (None: the squashed mean).  want: which
+        of "log_prob" [n], "mu" [n,A], "log_sigma" [n,A] (clamped), "ctrl" [n,nu] (il_ctrl of the action, from the
+        configured model) to return beside "action" [n,A].  Returns a dict (absent outputs None); `out` may supply the
+        buffers.  No synchronisation."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(central, torch.Tensor) or central.dim() != 1:
+            raise OlyError("sg_act: x [n,in] and central [A] must be tensors")
+        n, D = (int(v) for v in x.shape)
+        A = int(central.shape[0])
+        if n < 1:
+            raise OlyError(f"sg_act: n={n} rows (n >= 1)")
+        if not 0 < D <= 64 or not 0 < A <= _abi.OLY_BC_MAX_ACT:
+            raise OlyError(f"sg_act: unsupported shape in={D} act={A} (in <= 64, act <= {_abi.OLY_BC_MAX_ACT})")
+        if not float(log_std_min) <= float(log_std_max):
+            raise OlyError("sg_act: log_std_min <= log_std_max is required")
+        unknown = set(want) - {"log_prob", "mu", "log_sigma", "ctrl"}
+        if unknown:
+            raise OlyError(f"sg_act: unknown outputs {sorted(unknown)}")
+        if colstats is None and update_stats:
+            update_stats = False
+        npk = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 2 * A))
+        _req(x, "x", (n, D), f32, dv)
+        _req(packed, "packed", (npk,), f32, dv)
+        _req(central, "central", (A,), f32, dv)
+        _req(delta, "delta", (A,), f32, dv)
+        _req(colstats, "colstats", (3, D), f64, dv, optional=True)
+        _req(eps, "eps", (n, A), f32, dv, optional=True)
+        nu = 0
+        if "ctrl" in want:
+            sp = self.il_spec
+            if sp is None:
+                raise OlyError("sg_act: ctrl before il_configure")
+            if int(sp.n_act) != A:
+                raise OlyError(f"sg_act: ctrl for {A} actions, the configured model has n_act={sp.n_act}")
+            nu = int(sp.nu)
+        out = out or {}
+        cd = f64 if ctrl_f64 else f32
+        o = dict(action=self._out(out, "action", (n, A), f32),
+                 log_prob=self._out(out, "log_prob", (n,), f32) if "log_prob" in want else None,
+                 mu=self._out(out, "mu", (n, A), f32) if "mu" in want else None,
+                 log_sigma=self._out(out, "log_sigma", (n, A), f32) if "log_sigma" in want else None,
+                 ctrl=self._out(out, "ctrl", (n, nu), cd) if "ctrl" in want else None)
+        f = _abi.SGAct(n=n, in_dim=D, act_dim=A, update_stats=int(bool(update_stats)), x=x.data_ptr(),
+                       colstats=ptr(colstats), packed=packed.data_ptr(), log_std_min=float(log_std_min),
+                       log_std_max=float(log_std_max), central=central.data_ptr(), delta=delta.data_ptr(), eps=ptr(eps),
+                       action=o["action"].data_ptr(), log_prob=ptr(o["log_prob"]), mu=ptr(o["mu"]),
+                       log_sigma=ptr(o["log_sigma"]), ctrl=ptr(o["ctrl"]),
+                       out_flags=_abi.OUT_CTRL_F64 if ("ctrl" in want and ctrl_f64) else 0, pad=0)
+        self.ctx.call("oly_sg_act", C.byref(f), self._s())
+        return o
+
     # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
     def _gail_packed_floats(self, D):
         from ._ffi import lib
