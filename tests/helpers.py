@@ -251,7 +251,7 @@ def torch_ppo_update_grads(c, idx=None, clip=0.2, vf_coeff=0.5, mirror_coeff=0.4
 
 
 # ------------------------------------------------------------------------------ K13 against the oracle, directly
-def check_persistent_rollout_against_oracle(eng, orc, N=70, T=12, max_len=5, K=5, seed=3, det=False, normalize=True):
+def check_persistent_rollout_against_oracle(eng, orc, N=70, T=12, max_len=5, K=5, seed=3, det=False, normalize=True, put=None):
     """oly_a3_rollout_persistent (K13: all T steps of PPO.sample, rl/algos/ppo.py:169-196, in ONE launch) against a loop
     of the oracle's own functions: oly_mlp_forward_cpu (actor, critic) + oly_a3_vec_step_cpu, step by step.
 
@@ -259,7 +259,9 @@ def check_persistent_rollout_against_oracle(eng, orc, N=70, T=12, max_len=5, K=5
     row the KERNEL stored (checked to be within one float32 ulp of the oracle's own: device libm vs glibc in the
     observation's trigonometric terms), so that every later comparison of the step is exact where the arithmetic is:
     mu / value / sampled action / stored value / PD target BIT-EXACT (k-ordered fma chains, f32 mul + add), flags,
-    counters, integer task state, cursors BIT-EXACT, float64 rewards 1e-11, goal / sequence 1e-11.  Returns a summary."""
+    counters, integer task state, cursors BIT-EXACT, float64 rewards 1e-11, goal / sequence 1e-11.  Returns a summary.
+    put(name, array) -> device tensor, for a test that wants every buffer somewhere of its own (tests/test_gpu_fences.py);
+    the default is a plain copy."""
     import torch
     from olympic_hip import _abi, specs
     from olympic_hip.a3 import clock_lut
@@ -294,18 +296,21 @@ def check_persistent_rollout_against_oracle(eng, orc, N=70, T=12, max_len=5, K=5
                                                                  (0.1, (1, 256)), (0.1, (1,)))]
     mean = rng.normal(0, 0.1, nobs).astype(np.float32) if normalize else None
     std = rng.uniform(0.8, 1.3, nobs).astype(np.float32) if normalize else None
-    d = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a)).cuda()
-    d_blocks = {k: d(v) for k, v in blocks.items()}
-    d_state = {k: d(v) for k, v in state.items()}
-    d_ro = {k: (d(v) if isinstance(v, np.ndarray) else v) for k, v in ro.items()}
-    ctr = torch.zeros(eng.a3_vec_ctr_len(N), dtype=torch.int32, device="cuda")
+    put = put or (lambda name, a: torch.as_tensor(np.ascontiguousarray(a)).cuda())
+    d_blocks = {k: put("blocks." + k, v) for k, v in blocks.items()}
+    d_state = {k: put("state." + k, v) for k, v in state.items()}
+    d_ro = {k: (put("ro." + k, v) if isinstance(v, np.ndarray) else v) for k, v in ro.items() if k != "ctr"}
+    ctr = put("ro.ctr", np.zeros(eng.a3_vec_ctr_len(N), np.int32))
     ctr[1:-2:2] = int(ro["ctr"][1])
     d_ro["ctr"] = ctr
     launch = eng.a3_vec_prepare(d_blocks, d_state, d_ro)
-    pa, pc = eng.mlp_pack(*[d(a) for a in wa], d(mean), d(std)), eng.mlp_pack(*[d(a) for a in wc])
+    d = lambda name, arrays: [None if a is None else put(f"{name}[{i}]", a) for i, a in enumerate(arrays)]
+    pa = eng.mlp_pack(*d("actor", wa), *d("actor.norm", (mean, std)),
+                      packed=put("packed_actor", np.zeros(eng._mlp_floats(nobs, nu), np.float32)))
+    pc = eng.mlp_pack(*d("critic", wc), packed=put("packed_critic", np.zeros(eng._mlp_floats(nobs, 1), np.float32)))
     launch(_abi.VSTEP_RESET_ALL)
-    mu_out = torch.zeros((N, nu), dtype=torch.float32, device="cuda")
-    value_out = torch.zeros(N, dtype=torch.float32, device="cuda")
+    mu_out = put("mu_out", np.zeros((N, nu), np.float32))
+    value_out = put("value_out", np.zeros(N, np.float32))
     launch.persistent(pa, normalize, pc, False, mu_out, value_out)     # the whole rollout: ONE launch
     torch.cuda.synchronize()
     h = lambda t_: t_.cpu().numpy()

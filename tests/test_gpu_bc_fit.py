@@ -75,7 +75,11 @@ def same_state(a, b):
 @pytest.mark.parametrize("c", br.CASES, ids=IDS)
 def test_fit_against_float64(eng, c):
     k, ref = br.yardstick(c)
-    st = run_kernel(eng, c, k)
+    assert_fit_matches_float64(eng, c, run_kernel(eng, c, k), ref)
+
+
+def assert_fit_matches_float64(eng, c, st, ref):
+    """The device state `st` of case c after the fit (run_kernel's keys) against the float64 restatement `ref`."""
     got = [t.double().cpu().numpy() for t in split(st["param"], c.in_dim, c.A)]
     for name, a, r in zip(NAMES, got, ref["params"][-1]):
         err = float(np.abs(a - r).max())

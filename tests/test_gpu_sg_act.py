@@ -349,12 +349,17 @@ def test_logged_fit_against_float64(eng, golden, c):
     float32 log-probability is no function of its float64 value, in torch as here (test_policy_log_prob_against_float64's
     docstring, tests/test_gpu_bc_fit.py): there the parameters, the statistics and the first three scalars are held to
     the restatement and the entropy to be finite; the entropy tolerance is held on the plain cases."""
-    saturated = c.saturated
     k = br.build(c)
     li = blr.logging_iter_of(c)
     eps = blr.noise(c, li)
     ref = blr.restate(c.in_dim, c.A, k, c.steps, c.lr, c.standardizer, eps, li)
     st = run_logged(eng, c.in_dim, c.A, k, c.steps, c.lr, c.standardizer, eps, li)
+    assert_logged_fit_matches_float64(c, k, li, st, ref, float(golden("bc_log/bc_log.npz")["ent_spread"]))
+
+
+def assert_logged_fit_matches_float64(c, k, li, st, ref, spread):
+    """The device state `st` of run c after the logged fit (run_logged's keys) against the float64 restatement `ref`."""
+    saturated = c.saturated
     got = [t.double().cpu().numpy() for t in split(st["param"], c.in_dim, c.A)]
     for name, a, r in zip(NAMES, got, ref["params"][-1]):
         err = float(np.abs(a - r).max())
@@ -367,7 +372,6 @@ def test_logged_fit_against_float64(eng, golden, c):
     out = st["out"].cpu().numpy()
     rel = np.abs(out[:, :3] - ref["out"][:, :3]) / np.abs(ref["out"][:, :3])
     assert rel.max() <= TOL, rel
-    spread = float(golden("bc_log/bc_log.npz")["ent_spread"])
     for t in range(c.steps):
         if t not in blr.logged_steps(c.steps, li):
             assert np.isnan(out[t, 3])

@@ -55,15 +55,39 @@ def _host_rollout(spec, N, K, T, max_traj_len, depth, seed, det=False, p_bad=0.0
     return blocks, state, ro, rng
 
 
-def _to_device(eng, blocks, state, ro):
+def _to_device(eng, blocks, state, ro, put=None):
+    """put(name, array) -> device tensor: where a test wants the buffers somewhere of its own (tests/test_gpu_fences.py);
+    the default is a plain copy."""
+    put = put or (lambda name, a: dev(a))
     N = len(state["phase"])
-    d_blocks = {k: dev(v) for k, v in blocks.items()}
-    d_state = {k: dev(v) for k, v in state.items()}
-    d_ro = {k: (dev(v) if isinstance(v, np.ndarray) else v) for k, v in ro.items()}
-    ctr = torch.zeros(eng.a3_vec_ctr_len(N), dtype=torch.int32, device="cuda")
+    d_blocks = {k: put("blocks." + k, v) for k, v in blocks.items()}
+    d_state = {k: put("state." + k, v) for k, v in state.items()}
+    d_ro = {k: (put("ro." + k, v) if isinstance(v, np.ndarray) else v) for k, v in ro.items() if k != "ctr"}
+    ctr = put("ro.ctr", np.zeros(eng.a3_vec_ctr_len(N), np.int32))
     ctr[0:-2:2], ctr[1:-2:2] = int(ro["ctr"][0]), int(ro["ctr"][1])      # the last pair is (overrun mark, pad)
     d_ro["ctr"] = ctr
     return d_blocks, d_state, d_ro
+
+
+def _compare(d_state, d_ro, state, ro, step):
+    """The device's buffers against the oracle's after the same calls, at test_vec_step_vs_oracle's bars."""
+    h = lambda t_: t_.cpu().numpy()
+    for k in ("phase", "t1", "t2", "reached_frames", "target_reached", "mode", "seq_len"):
+        assert np.array_equal(h(d_state[k]), state[k]), (step, k)
+    np.testing.assert_allclose(h(d_state["sequence"]), state["sequence"], rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(h(d_state["goal"]), state["goal"], rtol=1e-11, atol=1e-12)
+    for k in ("traj_len", "side_count", "side_t", "pool_count", "buf_flags"):
+        assert np.array_equal(h(d_ro[k]), ro[k]), (step, k)
+    assert np.array_equal(h(d_ro["buf_actions"]), ro["buf_actions"])
+    assert np.array_equal(h(d_ro["pd_target"]), ro["pd_target"])
+    assert np.array_equal(h(d_ro["buf_values"]), ro["buf_values"])
+    np.testing.assert_allclose(h(d_ro["buf_rewards"]), ro["buf_rewards"], rtol=1e-11, atol=1e-13)
+    np.testing.assert_allclose(h(d_ro["buf_rew6"]), ro["buf_rew6"], rtol=2e-6, atol=1e-7)
+    for k in ("state", "buf_states", "side_obs"):
+        a, b = h(d_ro[k]), ro[k]
+        assert np.abs(a - b).max() <= np.spacing(np.float32(1.0)) * max(1.0, np.abs(b).max()), (step, k)
+    c = h(d_ro["ctr"]).reshape(-1, 2)
+    assert (c[:-1, 0] == ro["ctr"][0]).all() and (c[:-1, 1] == ro["ctr"][1]).all() and c[-1, 0] == 0
 
 
 @pytest.mark.parametrize("N,T,max_len,det", [(300, 9, 3, False), (4096, 6, 4, False), (37, 7, 100, True)])
@@ -77,26 +101,7 @@ def test_vec_step_vs_oracle(eng, golden, oracle, N, T, max_len, det):
     blocks, state, ro, rng = _host_rollout(spec, N, 5, T, max_len, 2, seed=N + T, det=det)
     d_blocks, d_state, d_ro = _to_device(eng, blocks, state, ro)
     launch = eng.a3_vec_prepare(d_blocks, d_state, d_ro)
-    h = lambda t_: t_.cpu().numpy()
-
-    def compare(step):
-        for k in ("phase", "t1", "t2", "reached_frames", "target_reached", "mode", "seq_len"):
-            assert np.array_equal(h(d_state[k]), state[k]), (step, k)
-        np.testing.assert_allclose(h(d_state["sequence"]), state["sequence"], rtol=1e-12, atol=1e-13)
-        np.testing.assert_allclose(h(d_state["goal"]), state["goal"], rtol=1e-11, atol=1e-12)
-        for k in ("traj_len", "side_count", "side_t", "pool_count", "buf_flags"):
-            assert np.array_equal(h(d_ro[k]), ro[k]), (step, k)
-        assert np.array_equal(h(d_ro["buf_actions"]), ro["buf_actions"])
-        assert np.array_equal(h(d_ro["pd_target"]), ro["pd_target"])
-        assert np.array_equal(h(d_ro["buf_values"]), ro["buf_values"])
-        np.testing.assert_allclose(h(d_ro["buf_rewards"]), ro["buf_rewards"], rtol=1e-11, atol=1e-13)
-        np.testing.assert_allclose(h(d_ro["buf_rew6"]), ro["buf_rew6"], rtol=2e-6, atol=1e-7)
-        for k in ("state", "buf_states", "side_obs"):
-            a, b = h(d_ro[k]), ro[k]
-            assert np.abs(a - b).max() <= np.spacing(np.float32(1.0)) * max(1.0, np.abs(b).max()), (step, k)
-        c = h(d_ro["ctr"]).reshape(-1, 2)
-        assert (c[:-1, 0] == ro["ctr"][0]).all() and (c[:-1, 1] == ro["ctr"][1]).all() and c[-1, 0] == 0
-
+    compare = lambda step: _compare(d_state, d_ro, state, ro, step)
     launch(_abi.VSTEP_RESET_ALL)
     oracle.a3_vec_step(spec, lut, CONTACT, blocks, state, ro, _abi.VSTEP_RESET_ALL)
     compare("reset")
