@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""The critic side of IQ-Learn (imitation_lib/imitation/iq_sac.py) or SQIL (imitation_lib/imitation/sqil_sac.py) on
+synthetic transitions (olympic_hip.synthetic): a squashed-Gaussian policy with random weights supplies the actions the
+critic's loss needs, the expert's and the policy's transitions are seeded stand-ins, and DeviceIQLearn.fit_Q runs
+update_Q_function and the soft target update on the GPU: three oly_sg_act calls at most (K25) and one oly_iq_q_update
+(K26) per update.  The policy is not trained: update_policy is the follow-up to the critic update.
+
+    python examples/iq_q_fit.py --algo iq|sqil [--updates 200] [--batch 32] [--no-target] [--log] [--json FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "olympics-mujoco_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from olympic_hip import _abi  # noqa: E402
+from olympic_hip.bc import DeviceSquashedGaussianPolicy  # noqa: E402
+from olympic_hip.engine import Engine  # noqa: E402
+from olympic_hip.gail import DeviceStandardizer  # noqa: E402
+from olympic_hip.iq import DeviceIQLearn, DeviceSoftQCritic, DeviceSQIL  # noqa: E402
+from olympic_hip.synthetic import il_synthetic_transitions  # noqa: E402
+
+
+class PrintingWriter:
+    def add_scalar(self, name, value, it):
+        print(f"  [{it}] {name} = {value:.6g}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", choices=("iq", "sqil"), default="iq")
+    ap.add_argument("--updates", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=32, help="policy rows per update; as many expert rows are added")
+    ap.add_argument("--in-dim", type=int, default=32)
+    ap.add_argument("--act-dim", type=int, default=11)
+    ap.add_argument("--no-target", action="store_true", help="use_target=False: the next-state pass carries a gradient")
+    ap.add_argument("--log", action="store_true", help="print the logged scalars under the reference's names")
+    ap.add_argument("--json", default=None, metavar="FILE", help="write the run's figures to FILE")
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    eng = Engine(0)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    D, A = args.in_dim, args.act_dim
+    p_lins = [torch.nn.Linear(D, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 2 * A)]
+    with torch.no_grad():
+        p_lins[2].weight.mul_(0.1)
+    policy = DeviceSquashedGaussianPolicy(eng, p_lins, -np.ones(A), np.ones(A), standardizer=DeviceStandardizer(eng, D))
+    c_lins = [torch.nn.Linear(D + A, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
+    critic = DeviceSoftQCritic(eng, c_lins, standardizer=DeviceStandardizer(eng, D + A), lr=3e-4, tau=0.005)
+    demo = il_synthetic_transitions(20000, D, A, seed=1)
+    kw = dict(gamma=0.99, batch_size=args.batch, use_target=not args.no_target, logging_iter=max(1, args.updates // 4),
+              sw=PrintingWriter() if args.log else None, max_replay_size=50000)
+    agent = (DeviceIQLearn if args.algo == "iq" else DeviceSQIL)(eng, policy, critic, demo, **kw)
+    first = last = None
+    for u in range(args.updates):
+        # what the collection loop would hand over: the transitions of one vec step of 256 environments
+        dataset = {k: torch.as_tensor(v).cuda() for k, v in il_synthetic_transitions(256, D, A, seed=100 + u, drift=0.5).items()}
+        out = agent.fit_Q(dataset, generator=gen)
+        if u == 0:
+            first = out.clone()
+        last = out
+    first, last = first.cpu().numpy(), last.cpu().numpy()
+    name = "IQ-Loss/LossQ" if args.algo == "sqil" else "Loss1 + Loss2 + Chi2"
+    tot = lambda o: float(o[0]) if args.algo == "sqil" else float(o[0] + o[1] + o[2])
+    print(f"{args.algo}: {critic.step} critic updates at batch {2 * args.batch} ({'a target' if not args.no_target else 'no target'}); "
+          f"{name} {tot(first):.5f} -> {tot(last):.5f}; Q for expert {first[4]:.4f} -> {last[4]:.4f}, "
+          f"Q for policy {first[6]:.4f} -> {last[6]:.4f}; gradient norm {last[15]:.4f}")
+    q = critic.predict(torch.as_tensor(demo["states"][:256]).cuda(), torch.as_tensor(demo["actions"][:256]).cuda())
+    print(f"Q on 256 expert rows: mean {float(q.mean()):.4f}; target mean "
+          f"{float(critic.predict_target(torch.as_tensor(demo['states'][:256]).cuda(), torch.as_tensor(demo['actions'][:256]).cuda()).mean()):.4f}")
+    critic.sync_to_torch()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(algo=args.algo, updates=int(critic.step), first={t: float(v) for t, v in zip(_abi.IQ_Q_TAGS, first)},
+                           last={t: float(v) for t, v in zip(_abi.IQ_Q_TAGS, last)}), f)
+
+
+if __name__ == "__main__":
+    main()

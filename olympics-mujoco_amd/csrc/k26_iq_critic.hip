@@ -1,0 +1,722 @@
+// K26: the soft-Q critic update of the SAC-family imitation agents, IQ_SAC.update_Q_function with _lossQ, getV,
+// get_targetV, regularizer_loss, update_Q_parameters and _update_all_targets (imitation_lib/imitation/iq_sac.py:421-429,
+// 467-595, 674-676) and SQIL's loss (imitation_lib/imitation/sqil_sac.py:64-136).  The critic is a
+// FullyConnectedNetwork((obs | act) -> [512, 256] -> 1, relu / relu / identity) whose Standardizer takes the whole
+// concatenated row.  The policy passes (compute_action_and_log_prob_t on next_obs and on obs) are K25's and come in as
+// the blocks a_next / logp_next and a_pi / logp_pi.
+//
+//   oly_iq_q_update   one update in four launches:
+//   P  iq_prologue_kernel  the transposed W2 stream of the backward from param; the column sums of the three critic
+//                          inputs X0 = (obs | act), X1 = (next_obs | a_next), X2 = (obs | a_pi) in NSP fixed slices.
+//   A  iq_rows_kernel      one 16-row tile per workgroup (8 waves) runs every pass of its rows: each pass standardised
+//                          with the statistics its network's Standardizer holds AT that pass (live: S + X0, then
+//                          + X1 without a target, then + X2; target: T + X1), the forward on the f32 matrix cores in
+//                          the forward kernel's chain order (ilmlp_common.h), so Q has oly_ilmlp_forward's bits.  Then
+//                          per row V, y, the loss terms and the coefficients dL/dQ, dL/dQ', dL/dV (fp64 from the f32
+//                          values, narrowed once), and the backward of every pass that carries a gradient through the
+//                          relus from the stored outputs.  Activations and deltas go to the workspace in row quads, one
+//                          slot of BP rows per gradient pass; the tile's loss sums to fixed slots.
+//   B  iq_weights_kernel   K24's launch B: one 16 x 16 weight tile per workgroup, dW summed over the slots' rows in a
+//                          fixed order, weight decay, Adam, the stepped value into param, the moments and the packed
+//                          stream; with update_target the soft target update f32(tau) w + f32(1 - tau) t (two float32
+//                          products, one add) into target_param and its packed stream; the tile's sum of squared
+//                          gradients to a fixed slot.
+//   F  iq_fold_kernel      one workgroup: the 16 scalars from the per-tile partials, the two Standardizers' sums.
+// Every reduction has a fixed order and there are no atomics: two runs give identical bits.
+#include <cstdlib>
+
+#include "fit_common.h"
+#include "ilmlp_common.h"
+#include "mlp_tiles.h"
+#include "oly_common.h"
+
+namespace {
+using namespace oly_ilmlp;
+using oly_fit::adam1;
+using oly_fit::NSP;
+using oly_fit::pt_index;
+using oly_fit::THREADS;
+static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
+
+constexpr int MAX_BATCH = OLY_BC_MAX_BATCH;
+constexpr int MAX_ACT = OLY_BC_MAX_ACT;
+constexpr int NSLOT = 3;     // gradient passes at most: Q(obs|act), Q(next_obs|a') without a target, Q(obs|a_pi)
+constexpr int NTERM = 12;    // per-row loss terms, by subset (policy rows, expert rows)
+static_assert(MAX_BATCH <= 16 * THREADS, "the fold kernel's loops run over at most 256 tiles");
+
+// terms of a row: Q, Q^2, reward = Q - y, y, V, V - y, w reward^2, Q [absorbing], [absorbing],
+//                 SQIL (Q - (R + y))^2, SQIL (V - (R_min + y))^2, unused
+enum { T_Q, T_Q2, T_R, T_Y, T_V, T_VY, T_CHI, T_QABS, T_ABS, T_SQ, T_SV };
+
+// workspace (floats), BP = batch rounded up to 16 rows, RP = NSLOT BP; [RP][W] arrays in row quads, element (row, col) at
+// ((row / 4) W + col) 4 + row % 4, slot s in rows [s BP, (s + 1) BP):
+//   xs [RP][64] | h1 [RP][512] | h2 [RP][256] | dZ1 [RP][512] | dZ2 [RP][256] | dZ3 [RP] | the raw outputs qv [3][BP] of
+//   the three passes | loss partials [BP / 16][2][NTERM] f64 | statistics partials [3][NSP][2][64] f64 | the inputs'
+//   column sums [3][2][64] f64 | gradient-norm partials [weight tiles] f64 | the transposed stream W2T
+struct WsL {
+  size_t xs, h1, h2, dz1, dz2, dz3, qv, lossp, statp, delta, gnp, w2t, total;
+};
+constexpr int MAX_WTILES = 32 * (IN_MAX / 16) + 512 + 16;
+__host__ __device__ inline WsL ws_layout(int batch) {
+  const size_t BP = (size_t)(batch + 15) / 16 * 16, RP = NSLOT * BP;
+  WsL W;
+  W.xs = 0;
+  W.h1 = W.xs + RP * IN_MAX;
+  W.h2 = W.h1 + RP * H1;
+  W.dz1 = W.h2 + RP * H2;
+  W.dz2 = W.dz1 + RP * H1;
+  W.dz3 = W.dz2 + RP * H2;
+  W.qv = W.dz3 + RP;
+  W.lossp = W.qv + 3 * BP;
+  W.statp = W.lossp + BP / 16 * 2 * NTERM * 2;
+  W.delta = W.statp + (size_t)3 * NSP * 2 * IN_MAX * 2;
+  W.gnp = W.delta + (size_t)3 * 2 * IN_MAX * 2;
+  W.w2t = W.gnp + (size_t)MAX_WTILES * 2;
+  W.total = W.w2t + (size_t)H2 * H1;
+  return W;
+}
+
+struct QArgs {
+  int in_dim, act_dim, D, B, n_policy;
+  int algo, loss_mode, reg_mode, treat_abs, use_target, update_target, has_v;
+  int slot[3];                 // the workspace slot of each pass's gradient rows, -1: the pass has no gradient
+  int n_slots;
+  const float *obs, *act, *next_obs, *absorbing, *a_next, *logp_next, *a_pi, *logp_pi;
+  double *colstats, *tcolstats;
+  float *param, *m, *v, *packed, *tparam, *tpacked, *ws;
+  float gamma, alpha, reg_mult, r_min, r_max, tau, omt;
+  oly_fit::AdamK ad;
+  float wd;
+  double* out;
+  ParamLayout P;
+  WsL W;
+};
+
+// column k < D of row `row` of critic input `src`
+__device__ __forceinline__ float input_at(const QArgs& a, int src, size_t row, int k) {
+  const float* s = src == 1 ? a.next_obs : a.obs;
+  const float* u = src == 0 ? a.act : src == 1 ? a.a_next : a.a_pi;
+  return k < a.in_dim ? s[row * a.in_dim + k] : u[row * a.act_dim + (k - a.in_dim)];
+}
+
+// grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. 3 NSP - 1, slice b % NSP of input
+// b / NSP: four row-strided chains per column, met in a fixed order (fit_common.h's fold_chains)
+constexpr int PRO_BLOCKS = 64;
+static_assert(3 * NSP <= PRO_BLOCKS, "one workgroup per statistics slice");
+__global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
+  __shared__ double part[8 * IN_MAX];
+  for (int e = blockIdx.x * THREADS + threadIdx.x; e < H2 * H1; e += PRO_BLOCKS * THREADS)
+    a.ws[a.W.w2t + pt_index(H2, e / H1, e % H1)] = a.param[a.P.w2 + e];
+  const int src = blockIdx.x / NSP, s = blockIdx.x % NSP;
+  if (src >= 3 || (src == 2 && !a.has_v) || (!a.colstats && !a.tcolstats)) return;
+  const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
+  const int per = (a.B + NSP - 1) / NSP, r0 = s * per, r1 = min(a.B, r0 + per);
+  double sum = 0.0, ss = 0.0;
+  if (k < a.D)
+    for (int r = r0 + grp; r < r1; r += 4) {
+      const double v = input_at(a, src, (size_t)r, k);
+      sum += v;
+      ss += v * v;
+    }
+  oly_fit::fold_chains(sum, ss, a.D, part,
+                       reinterpret_cast<double*>(a.ws + a.W.statp) + (size_t)(src * NSP + s) * 2 * IN_MAX);
+}
+
+__device__ __forceinline__ float relu32(float v) { return (v > 0.f || v != v) ? v : 0.f; }   // NaN kept like torch
+
+// ---------------------------------------------------------------------------------------------------------------
+// Launch A.  512 threads = 8 waves, K24's chains: layer 1 wave w -> column tiles 4w .. 4w+3, layer 2 -> 2w, 2w+1, the
+// output column by wave 0 as one chain over k < 256.  Backward: dZ2 = dQ W3 [h2 > 0] (one float32 product per element:
+// the output layer has one unit), dH1 = dZ2 W2 on the matrix cores (wave w -> tiles 4w .. 4w+3, the transposed stream).
+constexpr int RTHREADS = 512;
+constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16;
+constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (3 * 2 * IN_MAX + 16 * NTERM);
+static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
+
+template <int G1>
+__global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xT = lds;                       // [64 x 16]   standardised input (act16 images, mlp_tiles.h)
+  float* hA = xT + IN_MAX * 16;          // [512 x 16]  h1
+  float* hB = hA + H1 * 16;              // [256 x 16]  h2
+  float* gz = hB + H2 * 16;              // [256 x 16]  dZ2
+  double* st = reinterpret_cast<double*>(lds + ROWS_LDS_FLOATS);   // [3 passes][2][IN_MAX] mean, std
+  double* terms = st + 3 * 2 * IN_MAX;   // [16 rows][NTERM]
+  __shared__ float z[3][16];             // the raw outputs of the passes by row
+  __shared__ float coef[3][16];          // dL/d(output) of the passes by row
+  __shared__ int sub[16];                // 0 policy row, 1 expert row, -1 beyond the batch
+  const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, h4 = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int row0 = blockIdx.x * 16, B = a.B, D = a.D;
+  const size_t BP = (size_t)gridDim.x * 16;
+  float* ws = a.ws;
+  float4* ws4 = reinterpret_cast<float4*>(ws);
+
+  if (tid < D) {   // Standardizer.update_mean_std with each pass's rows (networks.py:76-81): the sums pass by pass
+    const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
+    double s[3], ss[3];
+    for (int p = 0; p < 3; ++p) {
+      s[p] = ss[p] = 0.0;
+      if ((a.colstats || a.tcolstats) && (p < 2 || a.has_v))
+        for (int q = 0; q < NSP; ++q) {
+          s[p] += sp[(size_t)(p * NSP + q) * 2 * IN_MAX + tid];
+          ss[p] += sp[(size_t)(p * NSP + q) * 2 * IN_MAX + IN_MAX + tid];
+        }
+    }
+    if (blockIdx.x == 0) {
+      double* d = reinterpret_cast<double*>(ws + a.W.delta);
+      for (int p = 0; p < 3; ++p) {
+        d[p * 2 * IN_MAX + tid] = s[p];
+        d[p * 2 * IN_MAX + IN_MAX + tid] = ss[p];
+      }
+    }
+    double cnt = 0.0, sum = 0.0, sq = 0.0;
+    if (a.colstats) cnt = a.colstats[tid], sum = a.colstats[D + tid], sq = a.colstats[2 * D + tid];
+    for (int p = 0; p < 3; ++p) {
+      double pc, ps, pq;
+      bool have;
+      if (p == 1 && a.use_target) {
+        have = a.tcolstats != nullptr;
+        pc = have ? a.tcolstats[tid] + (double)B : 0.0;
+        ps = have ? a.tcolstats[D + tid] + s[1] : 0.0;
+        pq = have ? a.tcolstats[2 * D + tid] + ss[1] : 0.0;
+      } else {
+        have = a.colstats != nullptr;
+        if (p < 2 || a.has_v) cnt += (double)B, sum += s[p], sq += ss[p];
+        pc = cnt, ps = sum, pq = sq;
+      }
+      double mean = 0.0, sd = 1.0;
+      if (have) {
+        const double n = pc + 1e-2;
+        mean = ps / n;
+        sd = sqrt(fmax((pq + 1e-2) / n - mean * mean, 1e-2));
+      }
+      st[(p * 2) * IN_MAX + tid] = mean;
+      st[(p * 2 + 1) * IN_MAX + tid] = sd;
+    }
+  }
+  if (tid < 16) sub[tid] = row0 + tid < B ? (row0 + tid >= a.n_policy ? 1 : 0) : -1;
+  __syncthreads();
+
+  // ---- the forwards
+  for (int p = 0; p < 3; ++p) {
+    if (p == 2 && !a.has_v) break;
+    const bool tgt = p == 1 && a.use_target;
+    const bool standardise = tgt ? a.tcolstats != nullptr : a.colstats != nullptr;
+    const float* P = tgt ? a.tpacked : a.packed;
+    const float4* P4 = reinterpret_cast<const float4*>(P);
+    const int slot = a.slot[p];
+    const size_t srow0 = (size_t)(slot < 0 ? 0 : slot) * BP + row0;
+    const size_t quad = (srow0 >> 2) + h4;           // this lane's accumulator rows: 4 h4 + i = one row quad
+    const double* mean = st + (p * 2) * IN_MAX;
+    const double* sd = mean + IN_MAX;
+    for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
+      const int m = e / IN_MAX, k = e & (IN_MAX - 1);
+      float v = 0.f;
+      if (sub[m] >= 0 && k < D) {
+        v = input_at(a, p, (size_t)(row0 + m), k);
+        // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
+        if (standardise) v = (float)(((double)v - mean[k]) / sd[k]);
+      }
+      xT[act16_index(k, m)] = v;
+      if (slot >= 0) ws[a.W.xs + (((srow0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
+    }
+    __syncthreads();
+    {  // ---- layer 1: [16, D] x [D, 512]
+      f32x4 acc[1][4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float4* a4[1] = {reinterpret_cast<const float4*>(xT)};
+      tiles<G1, 4, 1>(a4, P4 + P_W1 / 4 + (size_t)(4 * wave) * (IN_MAX / 16) * 64, (IN_MAX / 16) * 64, lane, acc);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int col = 16 * (4 * wave + t) + c;
+        const float bv = P[P_B1 + col];
+        float4 h;
+        h.x = relu32(acc[0][t][0] + bv);
+        h.y = relu32(acc[0][t][1] + bv);
+        h.z = relu32(acc[0][t][2] + bv);
+        h.w = relu32(acc[0][t][3] + bv);
+        hA[act16_index(col, 4 * h4)] = h.x;
+        hA[act16_index(col, 4 * h4 + 1)] = h.y;
+        hA[act16_index(col, 4 * h4 + 2)] = h.z;
+        hA[act16_index(col, 4 * h4 + 3)] = h.w;
+        if (slot >= 0) ws4[(a.W.h1 >> 2) + quad * H1 + col] = h;
+      }
+    }
+    __syncthreads();
+    {  // ---- layer 2: [16, 512] x [512, 256]
+      f32x4 acc[1][2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float4* a4[1] = {reinterpret_cast<const float4*>(hA)};
+      tiles<H1 / 16, 2, 1>(a4, P4 + P_W2 / 4 + (size_t)(2 * wave) * (H1 / 16) * 64, (H1 / 16) * 64, lane, acc);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int col = 16 * (2 * wave + t) + c;
+        const float bv = P[P_B2 + col];
+        float4 h;
+        h.x = relu32(acc[0][t][0] + bv);
+        h.y = relu32(acc[0][t][1] + bv);
+        h.z = relu32(acc[0][t][2] + bv);
+        h.w = relu32(acc[0][t][3] + bv);
+        hB[act16_index(col, 4 * h4)] = h.x;
+        hB[act16_index(col, 4 * h4 + 1)] = h.y;
+        hB[act16_index(col, 4 * h4 + 2)] = h.z;
+        hB[act16_index(col, 4 * h4 + 3)] = h.w;
+        if (slot >= 0) ws4[(a.W.h2 >> 2) + quad * H2 + col] = h;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {  // ---- the output unit: one chain over k < 256, as the forward kernel
+      f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
+      const float4* a4[1] = {reinterpret_cast<const float4*>(hB)};
+      tiles<H2 / 16, 1, 1>(a4, P4 + P_W3 / 4, 0, lane, acc);
+      if (c == 0) {
+        const float bv = P[P_B3];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float q = acc[0][0][i] + bv;
+          z[p][4 * h4 + i] = q;
+          ws[a.W.qv + (size_t)p * BP + row0 + 4 * h4 + i] = q;
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the loss terms and the coefficients of row tid (iq_sac.py:467-563, sqil_sac.py:64-92)
+  if (tid < 16) {
+    const int e = sub[tid];
+    double t[NTERM];
+    for (int j = 0; j < NTERM; ++j) t[j] = 0.0;
+    float cQ = 0.f, cN = 0.f, cV = 0.f;
+    if (e >= 0) {
+      const size_t i = (size_t)row0 + tid;
+      const double n_all = (double)B, n_p = (double)a.n_policy, n_e = (double)(B - a.n_policy);
+      const double n_own = e ? n_e : n_p;
+      const float ab = a.absorbing[i];
+      const float Q = z[0][tid];
+      const float nv = z[1][tid] - a.alpha * a.logp_next[i];          // getV / get_targetV (:571-585)
+      const float cy = (1.f - ab) * a.gamma;
+      const float y = cy * nv;                                        // :482
+      const float V = a.has_v ? z[2][tid] - a.alpha * a.logp_pi[i] : 0.f;
+      const float r = Q - y, vy = V - y;
+      double dr = 0.0, dV = 0.0, dy = 0.0;      // dL/d(reward) (= dL/dQ), dL/dV, dL/dy beside -dL/d(reward)
+      t[T_Q] = Q;
+      t[T_Q2] = (double)Q * (double)Q;
+      t[T_R] = r;
+      t[T_Y] = y;
+      t[T_V] = V;
+      t[T_VY] = vy;
+      t[T_QABS] = ab != 0.f ? (double)Q : 0.0;
+      t[T_ABS] = ab != 0.f ? 1.0 : 0.0;
+      if (a.algo == OLY_IQ_ALGO_IQ) {
+        if (e) dr -= 1.0 / n_e;                                       // loss_term1 = -mean(reward[expert])
+        if (a.loss_mode == OLY_IQ_VALUE) dV = 1.0 / n_all;
+        else if (a.loss_mode == OLY_IQ_VALUE_EXPERT) dV = e ? 1.0 / n_e : 0.0;
+        else if (a.loss_mode == OLY_IQ_VALUE_POLICY) dV = e ? 0.0 : 1.0 / n_p;
+        else if (!e) dr += 1.0 / n_p;                                 // q_old_policy: mean(reward[~expert])
+        dy = -dV;
+        const double ra = a.treat_abs ? (double)ab : 0.0;
+        const double w = (1.0 - ra) * (double)a.reg_mult + ra * (1.0 - (double)a.gamma) * (double)a.reg_mult;
+        const bool in = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY || (a.reg_mode == OLY_IQ_REG_EXP && e) ||
+                        (a.reg_mode == OLY_IQ_REG_PLCY && !e);
+        if (in) {
+          const double n = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY ? n_all : n_own;
+          dr += 2.0 * w * (double)r / n;
+          t[T_CHI] = w * (double)r * (double)r;
+        }
+      } else {
+        const double rm = (double)a.reg_mult;
+        if (e) {
+          const float d = Q - (a.r_max + y);                          // sqil_sac.py:80
+          dr += rm * (double)d / n_e;
+          t[T_SQ] = (double)d * (double)d;
+        } else if (a.loss_mode == OLY_SQIL_PLCY) {
+          const float d = Q - (a.r_min + y);                          // :90
+          dr += rm * (double)d / n_p;
+          t[T_SQ] = (double)d * (double)d;
+        }
+        if (a.loss_mode == OLY_SQIL_VALUE || (a.loss_mode == OLY_SQIL_VALUE_PLCY && !e)) {
+          const float d = V - (a.r_min + y);                          // :85, :88
+          dV = rm * (double)d / (a.loss_mode == OLY_SQIL_VALUE ? n_all : n_p);
+          dy = -dV;
+          t[T_SV] = (double)d * (double)d;
+        }
+      }
+      cQ = (float)dr;
+      cV = (float)dV;
+      cN = a.use_target ? 0.f : (float)((double)cy * (dy - dr));     // y = cy next_v carries a gradient without a target
+    }
+    coef[0][tid] = cQ;
+    coef[1][tid] = cN;
+    coef[2][tid] = cV;
+    for (int j = 0; j < NTERM; ++j) terms[tid * NTERM + j] = t[j];
+  }
+  __syncthreads();
+  if (tid < 2 * NTERM) {      // this tile's partials: subset tid / NTERM, term tid % NTERM, rows in order
+    const int e = tid / NTERM, j = tid % NTERM;
+    double s = 0.0;
+    for (int r = 0; r < 16; ++r)
+      if (sub[r] == e) s += terms[r * NTERM + j];
+    reinterpret_cast<double*>(ws + a.W.lossp)[(size_t)blockIdx.x * 2 * NTERM + tid] = s;
+  }
+
+  // ---- the backwards
+  for (int p = 0; p < 3; ++p) {
+    const int slot = a.slot[p];
+    if (slot < 0) continue;
+    const size_t srow0 = (size_t)slot * BP + row0;
+    const size_t quad = (srow0 >> 2) + h4;
+    if (tid < 16) ws[a.W.dz3 + srow0 + tid] = coef[p][tid];
+    {  // ---- dZ2 = (dQ W3) [h2 > 0]; this thread wrote the h2 and h1 values it reads back
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int col = 16 * (2 * wave + t) + c;
+        const float w3 = a.param[a.P.w3 + col];
+        const float4 h = ws4[(a.W.h2 >> 2) + quad * H2 + col];
+        float4 g;
+        g.x = h.x > 0.f && sub[4 * h4] >= 0 ? coef[p][4 * h4] * w3 : 0.f;
+        g.y = h.y > 0.f && sub[4 * h4 + 1] >= 0 ? coef[p][4 * h4 + 1] * w3 : 0.f;
+        g.z = h.z > 0.f && sub[4 * h4 + 2] >= 0 ? coef[p][4 * h4 + 2] * w3 : 0.f;
+        g.w = h.w > 0.f && sub[4 * h4 + 3] >= 0 ? coef[p][4 * h4 + 3] * w3 : 0.f;
+        gz[act16_index(col, 4 * h4)] = g.x;
+        gz[act16_index(col, 4 * h4 + 1)] = g.y;
+        gz[act16_index(col, 4 * h4 + 2)] = g.z;
+        gz[act16_index(col, 4 * h4 + 3)] = g.w;
+        ws4[(a.W.dz2 >> 2) + quad * H2 + col] = g;
+      }
+    }
+    __syncthreads();
+    {  // ---- dZ1 = (dZ2 W2) [h1 > 0]
+      f32x4 acc[1][4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float4* a4[1] = {reinterpret_cast<const float4*>(gz)};
+      tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
+                           (H2 / 16) * 64, lane, acc);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int col = 16 * (4 * wave + t) + c;
+        const float4 h = ws4[(a.W.h1 >> 2) + quad * H1 + col];
+        float4 g;
+        g.x = h.x > 0.f ? acc[0][t][0] : 0.f;
+        g.y = h.y > 0.f ? acc[0][t][1] : 0.f;
+        g.z = h.z > 0.f ? acc[0][t][2] : 0.f;
+        g.w = h.w > 0.f ? acc[0][t][3] : 0.f;
+        ws4[(a.W.dz1 >> 2) + quad * H1 + col] = g;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Launch B.  Tiles (n-tile x k-tile): W1 32 x ceil(D / 16), W2 16 x 32, W3 1 x 16; the k-tile 0 of each layer also steps
+// the layer's bias.
+__host__ __device__ inline int weight_tiles(int D) { return 32 * ((D + 15) / 16) + 512 + 16; }
+
+// the soft target update of the parameter at i (packed at pk): f32(tau) w + f32(1 - tau) t
+__device__ __forceinline__ void step_target(const QArgs& a, size_t i, size_t pk, float p) {
+  if (!a.update_target) return;
+  const float t = a.tau * p + a.omt * a.tparam[i];
+  a.tparam[i] = t;
+  a.tpacked[pk] = t;
+}
+
+constexpr int STEP_UNROLL = 4;      // 16-row steps whose loads are issued together
+__global__ __launch_bounds__(THREADS) void iq_weights_kernel(QArgs a) {
+  __shared__ float red[4 * 256];
+  __shared__ float bred[4 * 64];
+  __shared__ double dred[THREADS];
+  __shared__ double bsq[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, h4 = lane >> 4;
+  const WsL& W = a.W;
+  const ParamLayout& PL = a.P;
+  const int kt0 = (a.D + 15) / 16;
+  int t = blockIdx.x, layer, nt, kt;
+  if (t < 32 * kt0) {
+    layer = 0, nt = t / kt0, kt = t % kt0;
+  } else if ((t -= 32 * kt0) < 512) {
+    layer = 1, nt = t / 32, kt = t % 32;
+  } else {
+    layer = 2, nt = 0, kt = t - 512;
+  }
+  // delta [R][dw] (N columns used) and activation [R][aw] (K columns used) of the layer, both in row quads
+  const int dw = layer == 0 ? H1 : layer == 1 ? H2 : 1;
+  const int N = dw;
+  const int aw = layer == 0 ? IN_MAX : layer == 1 ? H1 : H2;
+  const int K = layer == 0 ? a.D : aw;
+  const float4* dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.dz1 : layer == 1 ? W.dz2 : W.dz3));
+  const float4* al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.xs : layer == 1 ? W.h1 : W.h2));
+  const int n0 = 16 * nt, k0 = 16 * kt;
+  const bool n_ok = n0 + c < N, k_ok = k0 + c < K;
+  // a step = the 16 rows of one tile of launch A in one slot (which wrote all 16: zeros in the deltas beyond the batch);
+  // lane group h4 takes the step's row quad h4.  Wave w: steps [w Q, min(steps, (w + 1) Q))
+  const int steps = a.n_slots * ((a.B + 15) / 16), Q = (steps + 3) / 4, s0 = wave * Q, s1 = min(steps, s0 + Q);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int s = s0; s < s1; s += STEP_UNROLL) {
+    float4 dv[STEP_UNROLL], av[STEP_UNROLL];
+#pragma unroll
+    for (int u = 0; u < STEP_UNROLL; ++u) {
+      const size_t q = (size_t)4 * (s + u) + h4;
+      const bool in = s + u < s1;
+      dv[u] = (in && n_ok) ? dl[q * dw + n0 + c] : zero4;
+      av[u] = (in && k_ok) ? al[q * aw + k0 + c] : zero4;
+    }
+#pragma unroll
+    for (int u = 0; u < STEP_UNROLL; ++u) {
+      // A[i = lane & 15][r = lane >> 4] = delta[row 4 q + r][n0 + i], B[r][j = lane & 15] = a[row 4 q + r][k0 + j]
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].x, av[u].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].y, av[u].y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].z, av[u].z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].w, av[u].w, acc, 0, 0, 0);
+      bsum += ((dv[u].x + dv[u].y) + dv[u].z) + dv[u].w;
+    }
+  }
+  // D[n = 4 (lane >> 4) + i][k = lane & 15]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[wave * 256 + (4 * h4 + i) * 16 + c] = acc[i];
+  bred[wave * 64 + lane] = bsum;
+  __syncthreads();
+  {
+    const int nn = tid >> 4, kk = tid & 15, ne = n0 + nn, ke = k0 + kk;
+    double g2 = 0.0;
+    if (ne < N && ke < K) {
+      const float g = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
+      g2 = (double)g * (double)g;
+      size_t i, pk;
+      if (layer == 0) i = PL.w1 + (size_t)ne * a.D + ke, pk = pk_index(P_W1, IN_MAX / 16, ne, ke);
+      else if (layer == 1) i = PL.w2 + (size_t)ne * H1 + ke, pk = pk_index(P_W2, H1 / 16, ne, ke);
+      else i = PL.w3 + ke, pk = pk_index(P_W3, H2 / 16, 0, ke);
+      const float p = adam1(a, i, g);
+      a.packed[pk] = p;
+      step_target(a, i, pk, p);
+    }
+    dred[tid] = g2;
+    if (tid < 16) bsq[tid] = 0.0;
+    if (kt == 0 && tid < 16 && n0 + tid < N) {   // the bias: the column sums of delta, lane groups then waves in order
+      const float gb = oly_fit::bias_colsum(bred, tid);
+      bsq[tid] = (double)gb * (double)gb;
+      const size_t pb = (layer == 0 ? PL.b1 : layer == 1 ? PL.b2 : PL.b3) + n0 + tid;
+      const size_t kb = (layer == 0 ? P_B1 : layer == 1 ? P_B2 : P_B3) + n0 + tid;
+      const float p = adam1(a, pb, gb);
+      a.packed[kb] = p;
+      step_target(a, pb, kb, p);
+    }
+  }
+  __syncthreads();
+  for (int h = THREADS / 2; h > 0; h >>= 1) {     // the tile's sum of squared gradients: a halving tree, then the biases
+    if (tid < h) dred[tid] += dred[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double s = dred[0];
+    for (int j = 0; j < 16; ++j) s += bsq[j];
+    reinterpret_cast<double*>(a.ws + W.gnp)[blockIdx.x] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Launch F: one workgroup.  Thread j < 2 NTERM adds term j of the tiles in order; thread t adds the gradient-norm
+// partials t, t + 256, ... and a halving tree joins them; thread 0 writes the 16 scalars; threads < D add the passes'
+// column sums to the Standardizers in the order of the passes.
+__global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, int tiles_b) {
+  __shared__ double S[2 * NTERM];
+  __shared__ double dred[THREADS];
+  const int tid = threadIdx.x, D = a.D;
+  if (tid < 2 * NTERM) {
+    const double* lp = reinterpret_cast<const double*>(a.ws + a.W.lossp);
+    double s = 0.0;
+    for (int t = 0; t < tiles_a; ++t) s += lp[(size_t)t * 2 * NTERM + tid];
+    S[tid] = s;
+  }
+  {
+    const double* gp = reinterpret_cast<const double*>(a.ws + a.W.gnp);
+    double s = 0.0;
+    for (int t = tid; t < tiles_b; t += THREADS) s += gp[t];
+    dred[tid] = s;
+  }
+  __syncthreads();
+  for (int h = THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) dred[tid] += dred[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double* Sp = S;            // policy rows
+    const double* Se = S + NTERM;    // expert rows
+    const double n_all = (double)a.B, n_p = (double)a.n_policy, n_e = n_all - n_p;
+    double o[16];
+    for (int j = 0; j < 16; ++j) o[j] = 0.0;
+    if (a.algo == OLY_IQ_ALGO_IQ) {
+      o[0] = -Se[T_R] / n_e;
+      o[1] = a.loss_mode == OLY_IQ_VALUE ? (Sp[T_VY] + Se[T_VY]) / n_all
+             : a.loss_mode == OLY_IQ_VALUE_EXPERT ? Se[T_VY] / n_e
+             : a.loss_mode == OLY_IQ_VALUE_POLICY ? Sp[T_VY] / n_p
+                                                  : Sp[T_R] / n_p;
+      o[2] = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY ? (Sp[T_CHI] + Se[T_CHI]) / n_all
+             : a.reg_mode == OLY_IQ_REG_EXP ? Se[T_CHI] / n_e
+             : a.reg_mode == OLY_IQ_REG_PLCY ? Sp[T_CHI] / n_p
+                                             : 0.0;
+    } else {
+      const double second = a.loss_mode == OLY_SQIL_VALUE ? 0.5 * (Sp[T_SV] + Se[T_SV]) / n_all
+                            : a.loss_mode == OLY_SQIL_VALUE_PLCY ? 0.5 * Sp[T_SV] / n_p
+                                                                 : 0.5 * Sp[T_SQ] / n_p;
+      o[0] = (double)a.reg_mult * (0.5 * Se[T_SQ] / n_e + second);
+    }
+    o[3] = a.has_v ? (Sp[T_V] + Se[T_V]) / n_all : 0.0;
+    o[4] = Se[T_Q] / n_e;
+    o[5] = Se[T_Q2] / n_e;
+    o[6] = Sp[T_Q] / n_p;
+    o[7] = Sp[T_Q2] / n_p;
+    o[8] = (Sp[T_R] + Se[T_R]) / n_all;
+    o[9] = Se[T_R] / n_e;
+    o[10] = Sp[T_R] / n_p;
+    o[11] = Se[T_Y] / n_e;
+    o[12] = Sp[T_Y] / n_p;
+    o[13] = Se[T_QABS] / Se[T_ABS];      // 0 / 0 = NaN for an empty subset, as torch.mean of nothing
+    o[14] = Sp[T_QABS] / Sp[T_ABS];
+    o[15] = sqrt(dred[0]);
+    for (int j = 0; j < 16; ++j) a.out[j] = o[j];
+  }
+  if (tid < D) {
+    const double* d = reinterpret_cast<const double*>(a.ws + a.W.delta);
+    const double Bd = (double)a.B;
+    if (a.colstats) {
+      double cnt = a.colstats[tid], sum = a.colstats[D + tid], sq = a.colstats[2 * D + tid];
+      for (int p = 0; p < 3; ++p) {
+        if ((p == 1 && a.use_target) || (p == 2 && !a.has_v)) continue;
+        cnt += Bd;
+        sum += d[p * 2 * IN_MAX + tid];
+        sq += d[p * 2 * IN_MAX + IN_MAX + tid];
+      }
+      a.colstats[tid] = cnt;
+      a.colstats[D + tid] = sum;
+      a.colstats[2 * D + tid] = sq;
+    }
+    if (a.tcolstats && a.use_target) {
+      a.tcolstats[tid] += Bd;
+      a.tcolstats[D + tid] += d[2 * IN_MAX + tid];
+      a.tcolstats[2 * D + tid] += d[2 * IN_MAX + IN_MAX + tid];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t oly_iq_q_ws(int batch, int in_dim, int act_dim) {
+  if (batch < 2 || batch > MAX_BATCH || in_dim <= 0 || act_dim <= 0 || act_dim > MAX_ACT || in_dim + act_dim > IN_MAX)
+    return -1;
+  return (int64_t)ws_layout(batch).total;
+}
+
+extern "C" int64_t oly_iq_q_ws_values(int batch, int in_dim, int act_dim) {
+  if (oly_iq_q_ws(batch, in_dim, act_dim) < 0) return -1;
+  return (int64_t)ws_layout(batch).qv;
+}
+
+extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream stream) {
+  const char* name = "oly_iq_q_update";
+  if (!ctx) return OLY_EINVAL;
+  if (!f) OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL argument", name);
+  const int in_dim = f->in_dim, A = f->act_dim, B = f->batch, D = in_dim + A;
+  if (oly_iq_q_ws(B, in_dim, A) < 0 || f->n_policy < 1 || f->n_policy >= B)
+    OLY_FAIL(ctx, OLY_EINVAL,
+             "%s: supported: 2 <= batch <= %d, in_dim >= 1, 1 <= act_dim <= %d, in_dim + act_dim <= %d, 1 <= n_policy < "
+             "batch (got batch %d, in %d, act %d, n_policy %d)",
+             name, MAX_BATCH, MAX_ACT, IN_MAX, B, in_dim, A, f->n_policy);
+  const bool iq = f->algo == OLY_IQ_ALGO_IQ, sqil = f->algo == OLY_IQ_ALGO_SQIL;
+  if (!iq && !sqil) OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown algorithm %d", name, f->algo);
+  if (iq && f->plcy_loss_mode == OLY_IQ_V0)
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: plcy_loss_mode v0 is not built", name);
+  if (iq ? (f->plcy_loss_mode < OLY_IQ_VALUE || f->plcy_loss_mode > OLY_IQ_Q_OLD_POLICY)
+         : (f->plcy_loss_mode < OLY_SQIL_PLCY || f->plcy_loss_mode > OLY_SQIL_VALUE_PLCY))
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown plcy_loss_mode %d", name, f->plcy_loss_mode);
+  if (f->regularizer_mode < OLY_IQ_REG_EXP_AND_PLCY || f->regularizer_mode > OLY_IQ_REG_OFF)
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown regularizer_mode %d", name, f->regularizer_mode);
+  if (f->gradient_penalty_lambda > 0.f || f->gradient_penalty_lambda != f->gradient_penalty_lambda)
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: the gradient penalty is not built (gradient_penalty_lambda must be 0)", name);
+  if (!(f->tau >= 0.0 && f->tau <= 1.0)) OLY_FAIL(ctx, OLY_EINVAL, "%s: tau %g outside [0, 1]", name, f->tau);
+  const bool has_v = iq || f->plcy_loss_mode != OLY_SQIL_PLCY;
+  const bool need_target = f->use_target || f->update_target;
+  if (!f->obs || !f->act || !f->next_obs || !f->absorbing || !f->a_next || !f->logp_next || !f->param || !f->m || !f->v ||
+      !f->packed || !f->ws || !f->out || (has_v && (!f->a_pi || !f->logp_pi)) ||
+      (need_target && (!f->target_param || !f->target_packed)))
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL pointer in the argument block", name);
+  const WsL W = ws_layout(B);
+  int rc = oly_fit::refuse_buffers(ctx, name, f->ws_floats, W.total, f->ws, f->packed, f->step, 1);
+  if (rc != OLY_OK) return rc;
+  if (need_target && (reinterpret_cast<uintptr_t>(f->target_packed) & 15) != 0)
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: target_packed must be 16-byte aligned", name);
+  if (f->packed_floats < (int64_t)P_TOTAL || (need_target && f->target_packed_floats < (int64_t)P_TOTAL))
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: a packed stream holds %ld floats", name, (long)P_TOTAL);
+  if ((reinterpret_cast<uintptr_t>(f->out) & 7) != 0 || (reinterpret_cast<uintptr_t>(f->colstats) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(f->target_colstats) & 7) != 0)
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: out and the colstats must be 8-byte aligned", name);
+
+  QArgs a{};
+  a.in_dim = in_dim;
+  a.act_dim = A;
+  a.D = D;
+  a.B = B;
+  a.n_policy = f->n_policy;
+  a.algo = f->algo;
+  a.loss_mode = f->plcy_loss_mode;
+  a.reg_mode = f->regularizer_mode;
+  a.treat_abs = f->treat_absorbing != 0;
+  a.use_target = f->use_target != 0;
+  a.update_target = f->update_target != 0;
+  a.has_v = has_v;
+  int ns = 0;
+  a.slot[0] = ns++;
+  a.slot[1] = a.use_target ? -1 : ns++;
+  a.slot[2] = has_v ? ns++ : -1;
+  a.n_slots = ns;
+  a.obs = f->obs;
+  a.act = f->act;
+  a.next_obs = f->next_obs;
+  a.absorbing = f->absorbing;
+  a.a_next = f->a_next;
+  a.logp_next = f->logp_next;
+  a.a_pi = f->a_pi;
+  a.logp_pi = f->logp_pi;
+  a.colstats = f->colstats;
+  a.tcolstats = a.use_target ? f->target_colstats : nullptr;
+  a.param = f->param;
+  a.m = f->m;
+  a.v = f->v;
+  a.packed = f->packed;
+  a.tparam = f->target_param;
+  a.tpacked = f->target_packed;
+  a.ws = f->ws;
+  a.gamma = f->gamma;
+  a.alpha = f->alpha;
+  a.reg_mult = f->reg_mult;
+  a.r_min = f->R_min;
+  a.r_max = f->R_max;
+  a.tau = (float)f->tau;
+  a.omt = (float)(1.0 - f->tau);
+  a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->eps, f->lr, (long)f->step + 1);
+  a.wd = f->weight_decay;
+  a.out = f->out;
+  a.P = param_layout(D, 1);
+  a.W = W;
+
+  const unsigned bit = D <= 32 ? 1u : 2u;
+  if (!(ctx->iqq_attr_done & bit)) {
+    OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(D <= 32 ? iq_rows_kernel<2> : iq_rows_kernel<4>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
+    ctx->iqq_attr_done |= bit;
+  }
+  const int tiles_a = (B + 15) / 16, tiles_b = weight_tiles(D);
+  hipLaunchKernelGGL(iq_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
+  if (D <= 32) hipLaunchKernelGGL(iq_rows_kernel<2>, dim3(tiles_a), dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
+  else hipLaunchKernelGGL(iq_rows_kernel<4>, dim3(tiles_a), dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
+  hipLaunchKernelGGL(iq_weights_kernel, dim3(tiles_b), dim3(THREADS), 0, oly_s(stream), a);
+  hipLaunchKernelGGL(iq_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), a, tiles_a, tiles_b);
+  OLY_LAUNCH_CHECK(ctx, "soft-Q critic update kernels");
+  return OLY_OK;
+}

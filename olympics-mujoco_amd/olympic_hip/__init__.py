@@ -4,7 +4,8 @@ Nothing here imports the CPU oracle; the HIP library is loaded lazily by olympic
 its absence is an error, not a fallback."""
 from . import _abi, specs  # noqa: F401
 
-__all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy"]
+__all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy", "DeviceSoftQCritic",
+           "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL"]
 
 
 def __getattr__(name):
@@ -12,4 +13,8 @@ def __getattr__(name):
     if name in ("DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy"):
         from . import bc
         return getattr(bc, name)
+    # the SAC family's critic side (iq.py, K26)
+    if name in ("DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL"):
+        from . import iq
+        return getattr(iq, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -270,6 +270,34 @@ class SGAct(C.Structure):
                 ("out_flags", C.c_int32), ("pad", C.c_int32)]
 
 
+class IQQ(C.Structure):
+    """oly_iq_q (K26): one soft-Q critic update of IQ-Learn / SQIL for oly_iq_q_update."""
+    _fields_ = [("in_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32), ("n_policy", C.c_int32),
+                ("algo", C.c_int32), ("plcy_loss_mode", C.c_int32), ("regularizer_mode", C.c_int32),
+                ("treat_absorbing", C.c_int32), ("use_target", C.c_int32), ("update_target", C.c_int32),
+                ("step", C.c_int32), ("pad", C.c_int32), ("gamma", C.c_float), ("alpha", C.c_float),
+                ("reg_mult", C.c_float), ("R_min", C.c_float), ("R_max", C.c_float),
+                ("gradient_penalty_lambda", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("weight_decay", C.c_float), ("pad2", C.c_float), ("tau", C.c_double), ("obs", vp),
+                ("act", vp), ("next_obs", vp), ("absorbing", vp), ("a_next", vp), ("logp_next", vp), ("a_pi", vp),
+                ("logp_pi", vp), ("colstats", vp), ("target_colstats", vp), ("param", vp), ("m", vp), ("v", vp),
+                ("packed", vp), ("target_param", vp), ("target_packed", vp), ("packed_floats", C.c_int64),
+                ("target_packed_floats", C.c_int64), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp)]
+
+
+IQ_ALGO = {"iq": 0, "sqil": 1}
+IQ_PLCY_LOSS_MODES = {"value": 0, "value_expert": 1, "value_policy": 2, "q_old_policy": 3, "v0": 4}
+SQIL_PLCY_LOSS_MODES = {"plcy": 0, "value": 1, "value_plcy": 2}
+IQ_REGULARIZER_MODES = {"exp_and_plcy": 0, "exp": 1, "plcy": 2, "off": 3}
+# out [16] of oly_iq_q_update: the reference's tags (iq_sac.py:426-428, 494, 535, 624-643); SQIL logs slot 0 as IQ-Loss/LossQ
+IQ_Q_TAGS = ("IQ-Loss/Loss1", "IQ-Loss/Loss2", "IQ-Loss/Chi2 Loss", "V for policy on all states",
+             "Action-Value/Q for expert", "Action-Value/Q^2 for expert", "Action-Value/Q for policy",
+             "Action-Value/Q^2 for policy", "Action-Value/Reward", "Action-Value/Reward_Expert",
+             "Action-Value/Reward_Policy", "Targets/expert data", "Targets/policy data",
+             "Action-Value/Q Absorbing state exp", "Action-Value/Q Absorbing state plcy",
+             "Gradients/Norm2 Gradient LossQ wrt. Q-parameters")
+
+
 SIGNATURES = {
     "oly_strerror": (C.c_char_p, [C.c_int]),
     "oly_last_error": (C.c_char_p, [vp]),
@@ -392,6 +420,9 @@ SIGNATURES = {
     "oly_bc_fit_log_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "oly_bc_fit_steps_log": (C.c_int, [vp, C.POINTER(BCFitLog), C.c_int, vp]),
     "oly_sg_act": (C.c_int, [vp, C.POINTER(SGAct), vp]),
+    "oly_iq_q_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "oly_iq_q_ws_values": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "oly_iq_q_update": (C.c_int, [vp, C.POINTER(IQQ), vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

@@ -1106,6 +1106,89 @@ class Engine:
         self.ctx.call("oly_sg_act", C.byref(f), self._s())
         return o
 
+    # -------------------------------------------------------------- K26 (the soft-Q critic update of IQ-Learn / SQIL)
+    def iq_q_ws(self, batch, in_dim, act_dim):
+        """A workspace for iq_q_update with batches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_iq_q_ws(int(batch), int(in_dim), int(act_dim)))
+        if n < 0:
+            raise OlyError(f"iq_q_update: unsupported batch={batch} in={in_dim} act={act_dim} (2 <= batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, act <= {_abi.OLY_BC_MAX_ACT}, in + act <= 64)")
+        return self._new((n,), torch.float32)
+
+    def iq_q_update(self, obs, act, next_obs, absorbing, a_next, logp_next, a_pi, logp_pi, n_policy, colstats,
+                    target_colstats, param, m, v, packed, target_param, target_packed, ws, step, lr, algo="iq",
+                    plcy_loss_mode="value", regularizer_mode="exp_and_plcy", treat_absorbing=False, use_target=True,
+                    update_target=True, gamma=0.99, alpha=1e-3, reg_mult=0.5, R_min=0.0, R_max=1.0, tau=0.005, beta1=0.9,
+                    beta2=0.999, eps=1e-8, weight_decay=0.0, gradient_penalty_lambda=0.0, out=None):
+        """oly_iq_q_update: one update_Q_function and _update_all_targets of IQ_SAC (algo "iq") or SQIL ("sqil").  obs /
+        next_obs [B,in] f32, act / a_next / a_pi [B,A] f32, absorbing / logp_next / logp_pi [B] f32; rows [0, n_policy)
+        are the policy's, the rest the expert's.  colstats / target_colstats [3,in+A] f64 or None; param / m / v /
+        target_param flat in torch order (W1 [512,in+A] | b1 | W2 | b2 | W3 [1,256] | b3); packed / target_packed their
+        ilmlp_pack streams, kept current by the call; step = Adam steps taken before.  a_pi / logp_pi may be None for
+        SQIL's plcy mode.  Returns out [16] f64 (_abi.IQ_Q_TAGS).  No synchronisation."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or not isinstance(act, torch.Tensor) or act.dim() != 2:
+            raise OlyError("iq_q_update: obs [B,in] and act [B,A] must be tensors")
+        B, in_dim = (int(t) for t in obs.shape)
+        A = int(act.shape[1])
+        nws = int(lib().oly_iq_q_ws(B, in_dim, A))
+        if nws < 0:
+            raise OlyError(f"iq_q_update: unsupported batch={B} in={in_dim} act={A} (2 <= batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, act <= {_abi.OLY_BC_MAX_ACT}, in + act <= 64)")
+        if not 1 <= int(n_policy) < B:
+            raise OlyError(f"iq_q_update: n_policy={n_policy} outside [1, {B})")
+        if algo not in _abi.IQ_ALGO:
+            raise OlyError(f"iq_q_update: unknown algorithm {algo!r}")
+        modes = _abi.IQ_PLCY_LOSS_MODES if algo == "iq" else _abi.SQIL_PLCY_LOSS_MODES
+        if plcy_loss_mode not in modes or (algo == "iq" and plcy_loss_mode == "v0"):
+            raise OlyError(f"iq_q_update: plcy_loss_mode {plcy_loss_mode!r} is not one of "
+                           f"{[k for k in modes if k != 'v0']} (v0 is not built)")
+        if regularizer_mode not in _abi.IQ_REGULARIZER_MODES:
+            raise OlyError(f"iq_q_update: unknown regularizer_mode {regularizer_mode!r}")
+        if float(gradient_penalty_lambda) > 0.0:
+            raise OlyError("iq_q_update: the gradient penalty is not built")
+        if not 0.0 <= float(tau) <= 1.0:
+            raise OlyError(f"iq_q_update: tau={tau} outside [0, 1]")
+        D = in_dim + A
+        need_pi = algo == "iq" or plcy_loss_mode != "plcy"
+        need_target = bool(use_target) or bool(update_target)
+        n_par = 512 * D + 512 + 256 * 512 + 256 + 256 + 1
+        npk = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 1))
+        _req(obs, "obs", (B, in_dim), f32, dv)
+        _req(act, "act", (B, A), f32, dv)
+        _req(next_obs, "next_obs", (B, in_dim), f32, dv)
+        _req(absorbing, "absorbing", (B,), f32, dv)
+        _req(a_next, "a_next", (B, A), f32, dv)
+        _req(logp_next, "logp_next", (B,), f32, dv)
+        _req(a_pi, "a_pi", (B, A), f32, dv, optional=not need_pi)
+        _req(logp_pi, "logp_pi", (B,), f32, dv, optional=not need_pi)
+        _req(colstats, "colstats", (3, D), f64, dv, optional=True)
+        _req(target_colstats, "target_colstats", (3, D), f64, dv, optional=True)
+        for t, name in ((param, "param"), (m, "m"), (v, "v")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (npk,), f32, dv)
+        _req(target_param, "target_param", (n_par,), f32, dv, optional=not need_target)
+        _req(target_packed, "target_packed", (npk,), f32, dv, optional=not need_target)
+        _req(ws, "ws", (nws,), f32, dv)
+        out = _req(out if out is not None else self._new((16,), f64), "out", (16,), f64, dv)
+        f = _abi.IQQ(in_dim=in_dim, act_dim=A, batch=B, n_policy=int(n_policy), algo=_abi.IQ_ALGO[algo],
+                     plcy_loss_mode=modes[plcy_loss_mode], regularizer_mode=_abi.IQ_REGULARIZER_MODES[regularizer_mode],
+                     treat_absorbing=int(bool(treat_absorbing)), use_target=int(bool(use_target)),
+                     update_target=int(bool(update_target)), step=int(step), pad=0, gamma=float(gamma), alpha=float(alpha),
+                     reg_mult=float(reg_mult), R_min=float(R_min), R_max=float(R_max),
+                     gradient_penalty_lambda=float(gradient_penalty_lambda), lr=float(lr), beta1=float(beta1),
+                     beta2=float(beta2), eps=float(eps), weight_decay=float(weight_decay), pad2=0.0, tau=float(tau),
+                     obs=obs.data_ptr(), act=act.data_ptr(), next_obs=next_obs.data_ptr(), absorbing=absorbing.data_ptr(),
+                     a_next=a_next.data_ptr(), logp_next=logp_next.data_ptr(), a_pi=ptr(a_pi), logp_pi=ptr(logp_pi),
+                     colstats=ptr(colstats), target_colstats=ptr(target_colstats), param=param.data_ptr(),
+                     m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(), target_param=ptr(target_param),
+                     target_packed=ptr(target_packed), packed_floats=npk, target_packed_floats=npk if need_target else 0,
+                     ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr())
+        self.ctx.call("oly_iq_q_update", C.byref(f), self._s())
+        return out
+
     # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
     def _gail_packed_floats(self, D):
         from ._ffi import lib

@@ -1,0 +1,463 @@
+"""The critic side of the SAC-family imitation agents on the device: IQ-Learn (imitation_lib/imitation/iq_sac.py) and
+SQIL (imitation_lib/imitation/sqil_sac.py).
+
+  Regressor(FullyConnectedNetwork((obs | act) -> [512, 256] -> 1)) x 2, _init_target, the critic's optimiser
+                                                         -> DeviceSoftQCritic (parameters, target, Adam moments, packed
+                                                            streams and the two Standardizers' sums, all on the device)
+  mushroom-rl's ReplayMemory (iq_sac.py:286)             -> DeviceReplayMemory, RESTATED from its published definition
+                                                            (mushroom-rl is not installed): a ring that add() fills in
+                                                            order and get() samples uniformly with replacement
+  IQ_SAC.update_Q_function, _lossQ, getV, get_targetV, regularizer_loss, update_Q_parameters, logging_loss,
+  _update_all_targets (:421-429, 467-595, 621-647, 674-676)
+                                                         -> DeviceIQLearn.update_Q_function: the policy passes are
+                                                            oly_sg_act calls (K25) in the reference's order, the rest is
+                                                            ONE oly_iq_q_update call (K26)
+  IQ_SAC.fit (:373-406), iq_update's critic part (:408-419)  -> DeviceIQLearn.fit_Q
+  SQIL._lossQ (sqil_sac.py:64-136)                       -> DeviceSQIL
+
+Not built, each refused by the constructors: the policy side (update_policy, which needs dQ/da through the critic and
+the gradient of K25, and _update_alpha: learnable_alpha) - the follow-up to this module; the gradient penalty
+(gradient_penalty_lambda > 0) and plcy_loss_mode "v0".
+
+Stated differences from the reference: the minibatches are drawn from torch's device generator (the replay memory's
+indices with replacement, the demonstrations' as the first entries of a fresh permutation): the same distributions,
+another sequence than numpy's.  Of logging_loss's scalars the per-action-dimension means, variances, mins and maxes
+("All Actions ...") are left out.  SQIL's iq_update logs its loss as "IQ-Loss/LossQ".
+"""
+import numpy as np
+import torch
+
+from . import _abi
+from ._ffi import OlyError
+from .bc import DeviceSquashedGaussianPolicy
+from .gail import DeviceStandardizer, _same
+
+_H1, _H2 = 512, 256
+FOLLOW_UP = "the policy side of the SAC family (update_policy, _update_alpha) is the follow-up to the critic update"
+DEMO_KEYS = ("states", "actions", "next_states", "absorbing")
+
+
+class DeviceSoftQCritic:
+    """The soft-Q critic and its target.  net: the reference's FullyConnectedNetwork (its `_linears`) or a list of its
+    three nn.Linear layers, (in + A) <= 64 -> 512 -> 256 -> 1.  standardizer: a DeviceStandardizer over all in + A columns
+    or None; with one the target gets its own (the reference deep-copies critic_params, iq_sac.py:291), starting from
+    the same sums.  The target's weights start as a copy of the live ones (_init_target).  The optimiser is
+    torch.optim.Adam(lr, betas, eps, weight_decay) (amsgrad off); tau is the soft target update's rate."""
+
+    def __init__(self, engine, net, standardizer=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, tau=0.005):
+        lins = list(getattr(net, "_linears", net))
+        if len(lins) != 3:
+            raise OlyError(f"DeviceSoftQCritic: expected three Linear layers, got {len(lins)}")
+        self.eng, self.net, self.lins, self.stand = engine, net, lins, standardizer
+        self.D = int(lins[0].in_features)
+        if (int(lins[0].out_features), int(lins[1].in_features), int(lins[1].out_features), int(lins[2].in_features),
+                int(lins[2].out_features)) != (_H1, _H1, _H2, _H2, 1) or not 2 <= self.D <= 64:
+            raise OlyError("DeviceSoftQCritic: supported shape is (in + A) <= 64 -> 512 -> 256 -> 1")
+        if standardizer is not None and int(standardizer.dim) != self.D:
+            raise OlyError(f"DeviceSoftQCritic: the standardizer has {standardizer.dim} columns, the network {self.D} "
+                           "(the critic standardises the whole row, actions included)")
+        if not 0.0 <= float(tau) <= 1.0:
+            raise OlyError(f"DeviceSoftQCritic: tau={tau} outside [0, 1]")
+        self.lr, self.betas = float(lr), (float(betas[0]), float(betas[1]))
+        self.eps, self.weight_decay, self.tau = float(eps), float(weight_decay), float(tau)
+        dev = engine.device
+        with torch.no_grad():
+            self.param = torch.cat([t.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+                                    for lin in lins for t in (lin.weight, lin.bias)]).contiguous()
+        self.target_param = self.param.clone()
+        self.exp_avg = torch.zeros_like(self.param)
+        self.exp_avg_sq = torch.zeros_like(self.param)
+        self.step = 0
+        self.target_stand = None
+        if standardizer is not None:
+            self.target_stand = DeviceStandardizer(engine, self.D)
+            self.target_stand.colstats.copy_(standardizer.colstats)
+            self.target_stand._fresh = standardizer._fresh
+        self.packed = engine.ilmlp_pack(*self._views(self.param))
+        self.target_packed = engine.ilmlp_pack(*self._views(self.target_param))
+
+    def _views(self, flat):
+        shapes = [(_H1, self.D), (_H1,), (_H2, _H1), (_H2,), (1, _H2), (1,)]
+        out, o = [], 0
+        for s in shapes:
+            n = int(np.prod(s))
+            out.append(flat[o:o + n].view(s))
+            o += n
+        return out
+
+    @property
+    def n_par(self):
+        return int(self.param.numel())
+
+    def repack(self):
+        """Re-pack both streams after the parameters were written (load_state_dict does this)."""
+        self.eng.ilmlp_pack(*self._views(self.param), packed=self.packed)
+        self.eng.ilmlp_pack(*self._views(self.target_param), packed=self.target_packed)
+
+    @staticmethod
+    def _colstats(st):
+        if st is None:
+            return None
+        if getattr(st, "_fresh", False):     # the running sums start from zero; an update adds to them in place
+            st.colstats.zero_()
+        return st.colstats
+
+    def _rows(self, obs, act):
+        x = torch.cat([obs.reshape(len(obs), -1), act.reshape(len(act), -1)], dim=1).to(torch.float32).contiguous()
+        if int(x.shape[1]) != self.D:
+            raise OlyError(f"DeviceSoftQCritic: obs | act has {x.shape[1]} columns, the network {self.D}")
+        return x
+
+    @torch.no_grad()
+    def predict(self, obs, act):
+        """Q(obs | act) [n, 1] with the current statistics, without updating them (K16's forward)."""
+        return self.eng.ilmlp_forward(self._rows(obs, act), self.packed, 1, "identity", colstats=self._colstats(self.stand))
+
+    @torch.no_grad()
+    def predict_target(self, obs, act):
+        return self.eng.ilmlp_forward(self._rows(obs, act), self.target_packed, 1, "identity",
+                                      colstats=self._colstats(self.target_stand))
+
+    @torch.no_grad()
+    def sync_to_torch(self):
+        """Write the live parameters back into the wrapped Linear layers (torch-side evaluation)."""
+        v = self._views(self.param)
+        for i, lin in enumerate(self.lins):
+            lin.weight.copy_(v[2 * i].to(lin.weight.device))
+            lin.bias.copy_(v[2 * i + 1].to(lin.bias.device))
+        return self.net
+
+    # ---- checkpoint (il_checkpoint)
+    def state_dict(self):
+        s, t = self.stand, self.target_stand
+        return dict(D=self.D, param=self.param.clone(), target_param=self.target_param.clone(),
+                    exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), step=int(self.step),
+                    standardizer=None if s is None else s.state_dict(),
+                    target_standardizer=None if t is None else t.state_dict())
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place (every device buffer keeps its pointer), then repack()."""
+        who = "DeviceSoftQCritic"
+        _same(who, "D", int(d["D"]), self.D)
+        _same(who, "standardizer", d["standardizer"] is not None, self.stand is not None)
+        self.param.copy_(d["param"])
+        self.target_param.copy_(d["target_param"])
+        self.exp_avg.copy_(d["exp_avg"])
+        self.exp_avg_sq.copy_(d["exp_avg_sq"])
+        self.step = int(d["step"])
+        if self.stand is not None:
+            self.stand.load_state_dict(d["standardizer"])
+            self.target_stand.load_state_dict(d["target_standardizer"])
+        self.repack()
+
+
+class DeviceReplayMemory:
+    """mushroom-rl's ReplayMemory RESTATED from its published definition as a ring of device blocks: add() writes the
+    samples in order at the running index, which wraps at max_size (the memory is then full); `initialized` is
+    size > initial_size; get(n) draws n indices uniformly from [0, size) with replacement.  The indices come from torch's
+    generator on the blocks' device and nothing is read back: the counters are host integers."""
+
+    KEYS = ("states", "actions", "rewards", "next_states", "absorbing", "last")
+
+    def __init__(self, engine, initial_size, max_size, in_dim, act_dim):
+        if int(max_size) < 1 or int(initial_size) < 0:
+            raise OlyError("DeviceReplayMemory: max_size >= 1 and initial_size >= 0 are required")
+        self.eng, self.initial_size, self.max_size = engine, int(initial_size), int(max_size)
+        self.in_dim, self.act_dim = int(in_dim), int(act_dim)
+        z = lambda *s: torch.zeros((self.max_size,) + s, dtype=torch.float32, device=engine.device)
+        self.blocks = dict(states=z(self.in_dim), actions=z(self.act_dim), rewards=z(), next_states=z(self.in_dim),
+                           absorbing=z(), last=z())
+        self._idx, self._full = 0, False
+
+    @property
+    def initialized(self):
+        return self.size > self.initial_size
+
+    @property
+    def size(self):
+        return self.max_size if self._full else self._idx
+
+    @torch.no_grad()
+    def add(self, dataset):
+        """dataset: a dict of blocks of n samples in order: states [n,in], actions [n,A], next_states [n,in], absorbing
+        [n]; rewards and last [n] optional (zeros)."""
+        dev = self.eng.device
+        n = int(torch.as_tensor(dataset["states"]).shape[0])
+        if n == 0:
+            return
+        first = max(0, n - self.max_size)              # older samples of a longer dataset would be overwritten anyway
+        pos = (self._idx + torch.arange(first, n, device=dev)) % self.max_size
+        for k, blk in self.blocks.items():
+            if k not in dataset:
+                if k in ("rewards", "last"):
+                    blk[pos] = 0.0
+                    continue
+                raise OlyError(f"DeviceReplayMemory.add: the dataset has no {k!r}")
+            t = torch.as_tensor(dataset[k]).to(device=dev, dtype=torch.float32).reshape((n,) + tuple(blk.shape[1:]))
+            blk[pos] = t[first:]
+        if self._idx + n >= self.max_size:
+            self._full = True
+        self._idx = (self._idx + n) % self.max_size
+
+    @torch.no_grad()
+    def get(self, n_samples, generator=None):
+        """(states, actions, rewards, next_states, absorbing, last) of n_samples uniformly drawn samples."""
+        if self.size < 1:
+            raise OlyError("DeviceReplayMemory.get: the memory is empty")
+        idx = torch.randint(self.size, (int(n_samples),), device=self.eng.device, generator=generator)
+        return tuple(self.blocks[k][idx] for k in self.KEYS)
+
+    def reset(self):
+        self._idx, self._full = 0, False
+
+    def state_dict(self):
+        return dict(idx=int(self._idx), full=bool(self._full), max_size=self.max_size,
+                    blocks={k: v.clone() for k, v in self.blocks.items()})
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        _same("DeviceReplayMemory", "max_size", int(d["max_size"]), self.max_size)
+        for k, v in self.blocks.items():
+            v.copy_(d["blocks"][k])
+        self._idx, self._full = int(d["idx"]), bool(d["full"])
+
+
+class DeviceIQLearn:
+    """IQ_SAC's critic side (iq_sac.py:256-420, 467-595, 621-647, 674-676) with its hot path on the device.
+
+    policy: a DeviceSquashedGaussianPolicy (it is not trained here); critic: a DeviceSoftQCritic over in + A columns;
+    demonstrations: a dict with `states` [n, >= in], `actions` [n,A], `next_states`, `absorbing` [n] (state_mask picks the
+    states' columns).  sw: an object with add_scalar(name, value, iteration), or None.  _iter starts at 1 as in the
+    reference; an update logs when _iter % logging_iter == 0."""
+
+    ALGO = "iq"
+    MODES = tuple(k for k in _abi.IQ_PLCY_LOSS_MODES if k != "v0")
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=1e-3,
+                 reg_mult=0.5, plcy_loss_mode="value", regularizer_mode="exp_and_plcy", treat_absorbing_states=False,
+                 delay_Q=1, logging_iter=1, state_mask=None, sw=None, n_fits=1, initial_replay_size=0,
+                 max_replay_size=100000, learnable_alpha=False, gradient_penalty_lambda=0.0):
+        who = type(self).__name__
+        if not isinstance(policy, DeviceSquashedGaussianPolicy):
+            raise OlyError(f"{who}: policy must be a DeviceSquashedGaussianPolicy")
+        if not isinstance(critic, DeviceSoftQCritic):
+            raise OlyError(f"{who}: critic must be a DeviceSoftQCritic")
+        if learnable_alpha:
+            raise OlyError(f"{who}: learnable_alpha=True is not built: {FOLLOW_UP}")
+        if float(gradient_penalty_lambda) > 0.0:
+            raise OlyError(f"{who}: gradient_penalty_lambda > 0 is not built (a second-order pass through the critic): "
+                           f"{FOLLOW_UP}")
+        if plcy_loss_mode == "v0":
+            raise OlyError(f"{who}: plcy_loss_mode 'v0' is not built (a fourth critic pass on the expert rows): {FOLLOW_UP}")
+        if plcy_loss_mode not in self.MODES:
+            raise OlyError(f"{who}: plcy_loss_mode {plcy_loss_mode!r} is not one of {list(self.MODES)}")
+        if regularizer_mode not in _abi.IQ_REGULARIZER_MODES:
+            raise OlyError(f"{who}: regularizer_mode {regularizer_mode!r} is not one of {list(_abi.IQ_REGULARIZER_MODES)}")
+        self.in_dim, self.act_dim = int(policy.in_dim), int(policy.act_dim)
+        if self.in_dim + self.act_dim > 64:
+            raise OlyError(f"{who}: in_dim + act_dim = {self.in_dim + self.act_dim} > 64 columns of the critic's input")
+        if int(critic.D) != self.in_dim + self.act_dim:
+            raise OlyError(f"{who}: the critic takes {critic.D} columns, the policy's observation and action give "
+                           f"{self.in_dim} + {self.act_dim}")
+        for k in DEMO_KEYS:
+            if k not in demonstrations:
+                raise OlyError(f"{who}: demonstrations have no {k!r}")
+        if int(batch_size) < 1 or 2 * int(batch_size) > _abi.OLY_BC_MAX_BATCH or int(logging_iter) < 1 or int(delay_Q) < 1:
+            raise OlyError(f"{who}: 1 <= batch_size <= {_abi.OLY_BC_MAX_BATCH // 2}, logging_iter >= 1 and delay_Q >= 1 "
+                           "are required")
+        self.eng, self.policy, self.critic, self.sw = engine, policy, critic, sw
+        dev = engine.device
+        mask = None if state_mask is None else torch.as_tensor(np.asarray(state_mask, np.int64), device=dev)
+
+        def up(a, width, name, masked=False):
+            t = torch.as_tensor(a).to(device=dev, dtype=torch.float32)
+            if masked and mask is not None and t.dim() == 2:
+                t = t[:, mask]
+            if width is None:
+                t = t.reshape(-1)
+            elif t.dim() != 2 or int(t.shape[1]) != width:
+                raise OlyError(f"{who}: demonstrations[{name!r}] has shape {tuple(t.shape)}, expected [n, {width}]")
+            return t.contiguous()
+        self.demo = dict(states=up(demonstrations["states"], self.in_dim, "states", True),
+                         actions=up(demonstrations["actions"], self.act_dim, "actions"),
+                         next_states=up(demonstrations["next_states"], self.in_dim, "next_states", True),
+                         absorbing=up(demonstrations["absorbing"], None, "absorbing"))
+        self.n_demo = int(self.demo["states"].shape[0])
+        if self.n_demo < 1 or any(int(v.shape[0]) != self.n_demo for v in self.demo.values()):
+            raise OlyError(f"{who}: the demonstrations' blocks have {[int(v.shape[0]) for v in self.demo.values()]} rows")
+        self.gamma, self.batch_size, self.use_target = float(gamma), int(batch_size), bool(use_target)
+        # torch.tensor(np.log(init_alpha), dtype=float32).exp(): alpha in float32 (iq_sac.py:328, 686-687)
+        self.log_alpha = float(np.float32(np.log(init_alpha)))
+        self.reg_mult = float(reg_mult)
+        self.plcy_loss_mode, self.regularizer_mode = plcy_loss_mode, regularizer_mode
+        self.treat_absorbing_states = bool(treat_absorbing_states)
+        self.delay_Q, self.logging_iter, self.n_fits = int(delay_Q), int(logging_iter), int(n_fits)
+        self.R_min, self.R_max = 0.0, 1.0
+        self.replay = DeviceReplayMemory(engine, initial_replay_size, max_replay_size, self.in_dim, self.act_dim)
+        self._iter = 1
+        self._ws = {}
+
+    @property
+    def alpha(self):
+        return float(torch.tensor(self.log_alpha, dtype=torch.float32).exp())
+
+    def _has_v(self):
+        return True
+
+    def _workspace(self, B):
+        if B not in self._ws:
+            self._ws[B] = self.eng.iq_q_ws(B, self.in_dim, self.act_dim)
+        return self._ws[B]
+
+    def _policy_pass(self, x, eps, generator, want_log_prob=True):
+        p = self.policy
+        x = p._rows(x)
+        o = p._fused(x, p._noise(int(x.shape[0]), eps, generator), ("log_prob",) if want_log_prob else ())
+        return o["action"], o["log_prob"]
+
+    @torch.no_grad()
+    def update_Q_function(self, obs, act, next_obs, absorbing, n_policy, eps=None, generator=None):
+        """update_Q_function and _update_all_targets on a batch whose rows [0, n_policy) are the policy's and the rest the
+        expert's.  The policy passes are issued in the reference's order: next_obs; on a logging iteration draw_action
+        on the expert rows (logging_loss, :646: it feeds the policy's Standardizer and draws noise); obs.  eps: None
+        (the noise is drawn from `generator` pass by pass) or a dict with `next` [B,A], `pi` [B,A] and, on a logging
+        iteration, `expert` [B - n_policy, A].  Returns the [16] f64 device block of _abi.IQ_Q_TAGS; on a logging
+        iteration the scalars also go to sw (which reads them back)."""
+        f32 = torch.float32
+        obs, next_obs = obs.to(f32).contiguous(), next_obs.to(f32).contiguous()
+        act, absorbing = act.to(f32).contiguous(), absorbing.to(f32).reshape(-1).contiguous()
+        B, n_policy = int(obs.shape[0]), int(n_policy)
+        eps = eps or {}
+        logging = self._iter % self.logging_iter == 0
+        c, p = self.critic, self.policy
+        a_next, lp_next = self._policy_pass(next_obs, eps.get("next"), generator)
+        a_pi = lp_pi = a_exp = None
+
+        def expert_pass():
+            return self._policy_pass(obs[n_policy:], eps.get("expert"), generator, want_log_prob=False)[0]
+        if logging and self.ALGO == "iq":
+            a_exp = expert_pass()
+        if self._has_v():
+            a_pi, lp_pi = self._policy_pass(obs, eps.get("pi"), generator)
+        if logging and self.ALGO != "iq":          # SQIL logs after its loss is formed (sqil_sac.py:94-113)
+            a_exp = expert_pass()
+        w_norm = torch.linalg.vector_norm(c.param.double()) if logging and self.sw is not None else None
+        cs, tcs = c._colstats(c.stand), c._colstats(c.target_stand)
+        out = self.eng.iq_q_update(obs, act, next_obs, absorbing, a_next, lp_next, a_pi, lp_pi, n_policy, cs, tcs, c.param,
+                                   c.exp_avg, c.exp_avg_sq, c.packed, c.target_param, c.target_packed, self._workspace(B),
+                                   c.step, c.lr, algo=self.ALGO, plcy_loss_mode=self.plcy_loss_mode,
+                                   regularizer_mode=self.regularizer_mode, treat_absorbing=self.treat_absorbing_states,
+                                   use_target=self.use_target, update_target=True, gamma=self.gamma, alpha=self.alpha,
+                                   reg_mult=self.reg_mult, R_min=self.R_min, R_max=self.R_max, tau=c.tau,
+                                   beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, weight_decay=c.weight_decay)
+        c.step += 1
+        if c.stand is not None:
+            c.stand._fresh = False
+            if self.use_target:
+                c.target_stand._fresh = False
+        if logging and self.sw is not None:
+            self._log(out, act, a_exp, n_policy, w_norm)
+        return out
+
+    def _log(self, out, act, a_exp, n_policy, w_norm):
+        host, it, sw = out.cpu().numpy(), self._iter, self.sw
+        tags = _abi.IQ_Q_TAGS
+        if self.ALGO == "iq":
+            for k in (0, 1, 2):
+                sw.add_scalar(tags[k], float(host[k]), it)
+            sw.add_scalar("IQ-Loss/Alpha", self.alpha, it)
+            skip = ()
+        else:
+            sw.add_scalar("IQ-Loss/LossQ", float(host[0]), it)
+            sw.add_scalar("Action-Value/R_min", self.R_min, it)
+            skip = (3, 13, 14)                      # SQIL logs neither V nor the absorbing states' Q
+        for k in range(3, 16):
+            if k not in skip:
+                sw.add_scalar(tags[k], float(host[k]), it)
+        sw.add_scalar("Action-Value/Norm of Q net: ", float(w_norm), it)
+        msq = lambda t: float(torch.square(t).mean())
+        sw.add_scalar("Actions/mean squared action expert (from data)", msq(act[n_policy:]), it)
+        sw.add_scalar("Actions/mean squared action expert (from policy)", msq(a_exp), it)
+        sw.add_scalar("Actions/mean squared action policy", msq(act[:n_policy]), it)
+        sw.add_scalar("Actions/mean squared action both", msq(act), it)
+
+    def draw_demo_idx(self, n, generator=None):
+        """The first n entries of a fresh permutation of the demonstrations (minibatch_generator's first batch)."""
+        n = min(int(n), self.n_demo)
+        keys = torch.rand((self.n_demo,), device=self.eng.device, generator=generator)
+        return torch.topk(keys, n, largest=False, sorted=True).indices
+
+    @torch.no_grad()
+    def fit_Q(self, dataset, generator=None):
+        """IQ_SAC.fit (:373-406) with iq_update's critic part: the dataset goes into the replay memory; once that is
+        initialised, n_fits times a policy minibatch from it and as many demonstration rows make one batch for
+        update_Q_function (every delay_Q iterations).  Then _iter and policy.iter advance.  Returns the last update's
+        scalars, or None."""
+        self.replay.add(dataset)
+        out = None
+        if self.replay.initialized:
+            for _ in range(self.n_fits):
+                s, a, _r, ns, ab, _l = self.replay.get(self.batch_size, generator)
+                idx = self.draw_demo_idx(int(s.shape[0]), generator)
+                d = self.demo
+                if self._iter % self.delay_Q == 0:
+                    out = self.update_Q_function(torch.cat([s, d["states"][idx]]), torch.cat([a, d["actions"][idx]]),
+                                                 torch.cat([ns, d["next_states"][idx]]),
+                                                 torch.cat([ab, d["absorbing"][idx]]), int(s.shape[0]), generator=generator)
+        self._iter += 1
+        self.policy.iter = getattr(self.policy, "iter", 0) + 1
+        return out
+
+    # ---- checkpoint (il_checkpoint.save / load take this object as the agent)
+    KIND = "iq_learn_critic"
+
+    def state_dict(self):
+        st = self.policy.stand
+        return dict(kind=self.KIND, policy=self.policy.state_dict(), policy_iter=int(getattr(self.policy, "iter", 0)),
+                    policy_standardizer=None if st is None else st.state_dict(), critic=self.critic.state_dict(),
+                    replay=self.replay.state_dict(), iter=int(self._iter), log_alpha=float(self.log_alpha))
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place (every device buffer keeps its pointer)."""
+        who = type(self).__name__
+        _same(who, "kind", d.get("kind"), self.KIND)
+        st = self.policy.stand
+        _same(who, "policy standardizer", d["policy_standardizer"] is not None, st is not None)
+        self.policy.load_state_dict(d["policy"])
+        self.policy.iter = int(d["policy_iter"])
+        if st is not None:
+            st.load_state_dict(d["policy_standardizer"])
+        self.critic.load_state_dict(d["critic"])
+        self.replay.load_state_dict(d["replay"])
+        self._iter, self.log_alpha = int(d["iter"]), float(d["log_alpha"])
+
+    def save(self, path, **meta):
+        from . import il_checkpoint
+        return il_checkpoint.save(path, self, None, **meta)
+
+    def load(self, path):
+        from . import il_checkpoint
+        return il_checkpoint.load(path, self, None)
+
+
+class DeviceSQIL(DeviceIQLearn):
+    """SQIL (sqil_sac.py): DeviceIQLearn with SQIL's loss, its modes plcy / value / value_plcy and the rewards R_min (policy
+    rows) and R_max (expert rows).  plcy, the true SQIL objective, runs no pass on (obs | a_pi)."""
+
+    ALGO = "sqil"
+    MODES = tuple(_abi.SQIL_PLCY_LOSS_MODES)
+    KIND = "sqil_critic"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, R_min=0.0, R_max=1.0,
+                 plcy_loss_mode="plcy", **kw):
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target,
+                         plcy_loss_mode=plcy_loss_mode, **kw)
+        self.R_min, self.R_max = float(R_min), float(R_max)
+
+    def _has_v(self):
+        return self.plcy_loss_mode != "plcy"
+
+
+__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL"]

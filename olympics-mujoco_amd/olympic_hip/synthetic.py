@@ -73,3 +73,19 @@ def a3_synthetic_blocks(N, K, seed=1, C=16, p_bad=1.0 / 300, p_low=0.0):
     kk, nn = np.nonzero(hit)
     b["geom2"][kk, nn, slot[kk, nn]] = 9
     return {k: np.ascontiguousarray(v) for k, v in b.items()}
+
+
+def il_synthetic_transitions(n, in_dim, act_dim, seed=0, absorbing_frac=0.05, drift=0.0):
+    """Seeded stand-in for a replay memory's or a demonstration file's content: n transitions as float32 blocks
+    states [n,in], actions [n,A] in (-1, 1), next_states [n,in], absorbing / last [n] (0 or 1), rewards [n] (zeros: the
+    imitation agents ignore them).  The columns have a scale and a shift each; `drift` moves the whole state
+    distribution, so that two calls can play the expert's and the policy's data."""
+    rng = np.random.default_rng(seed)
+    scale, shift = rng.uniform(0.3, 3.0, in_dim), rng.standard_normal(in_dim) * 2.0 + drift
+    states = rng.standard_normal((n, in_dim)) * scale + shift
+    actions = np.tanh(rng.standard_normal((n, act_dim)) + 0.3 * (states[:, :1] - shift[0]) / scale[0])
+    next_states = states + 0.1 * rng.standard_normal((n, in_dim)) * scale + 0.05 * actions[:, :1]
+    absorbing = rng.uniform(size=n) < absorbing_frac
+    f = np.float32
+    return dict(states=states.astype(f), actions=actions.astype(f), next_states=next_states.astype(f),
+                absorbing=absorbing.astype(f), last=absorbing.astype(f), rewards=np.zeros(n, f))
