@@ -1,6 +1,8 @@
 // Pieces that the minibatch fits share: K15 (csrc/k15_disc_fit.hip, the VAIL discriminator), K16 (csrc/k16_il_critic.hip,
-// the imitation critic) and K18 (csrc/k18_gail_disc.hip, GAIL's discriminator); oly_ppo_adam_step (K14) takes its bias
-// corrections from adam_scalars.  The order of every addition here is what makes a fit deterministic and what the tests
+// the imitation critic), K18 (csrc/k18_gail_disc.hip, GAIL's discriminator), K24 (csrc/k24_bc_fit.hip, behavioural
+// cloning) and K26 (csrc/k26_iq_critic.hip, the soft-Q critic); oly_ppo_adam_step (K14) takes its bias corrections from
+// adam_scalars.  What only K18, K24 and K26 share (one network, one two-launch design) is one level up, in ilmlp_fit.h.
+// The order of every addition here is what makes a fit deterministic and what the tests
 // pin: a change to it is a change to all of its users.  The functions that take an argument block `a` are templates
 // over the kernels' own FitArgs (the networks differ; the members named here do not).  The device functions are written
 // so that their users compile to the code they had with their own copies; how an index is spelt can matter to that.
@@ -102,7 +104,7 @@ __device__ void stats_slice(const A& a, long off, int R, int s, double* part) {
   fold_chains(sum, ss, a.in_dim, part, reinterpret_cast<double*>(a.ws + a.W.statp) + (size_t)s * 2 * MAX_IN);
 }
 
-// ---- the tail of a weights kernel (launch B of K15 and K18)
+// ---- the tail of a weights kernel (launch B of K15, K18, K24 and K26)
 // the bias gradient of the tile's column tid < 16: the column sums of delta in bred [4 waves][64 lanes], lane groups
 // then waves in order
 __device__ __forceinline__ float bias_colsum(const float* bred, int tid) {

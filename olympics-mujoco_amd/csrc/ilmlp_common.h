@@ -1,6 +1,9 @@
-// Pieces of the imitation-learning MLP  in -> 512 -> 256 -> out  that K16 (csrc/k16_il_critic.hip: relu hidden layers, the
-// critic and the policy mean) and K18 (csrc/k18_gail_disc.hip: tanh hidden layers, GAIL's discriminator) share: the
-// packed operand stream's layout, the flat parameter order and the forward kernel on the f32 matrix cores.
+// Pieces of the imitation-learning MLP  in -> 512 -> 256 -> out  that its kernels share: the packed operand stream's
+// layout, the flat parameter order and the forward kernel on the f32 matrix cores.  The forward kernel is K16's
+// (csrc/k16_il_critic.hip: relu hidden layers, the critic and the policy mean) and K18's (csrc/k18_gail_disc.hip: tanh
+// hidden layers, GAIL's discriminator); the layout and the chain `tiles` are also those of K21 and K25 and, through
+// ilmlp_fit.h, of the fits K18, K24 (csrc/k24_bc_fit.hip) and K26 (csrc/k26_iq_critic.hip), whose rows kernels keep the
+// forward kernel's chain order.
 #pragma once
 #include "disc_common.h"
 #include "mlp_tiles.h"

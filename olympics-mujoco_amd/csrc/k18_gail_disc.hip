@@ -30,24 +30,20 @@
 //                           partials and writes the per-minibatch outputs and colstats += minibatch b; workgroups
 //                           1 .. 16 sum minibatch b+1's rows into the statistics partials launch A of b+1 reads.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits.  What the fit shares with
-// K15 and K16 (Adam, the statistics fold, the weights kernel's tail, the epoch driver's host side) is in fit_common.h.
+// K15 and K16 (Adam, the statistics fold, the weights kernel's tail, the epoch driver's host side) is in fit_common.h;
+// what the two launches share with K24 and K26 (the Standardizer's head, the activation and its gradient, the row-quad
+// stores, dZ1, the W2T build, the tile count, the rows kernel's dispatch) is in ilmlp_fit.h, taken here with Tanh.
 #include <cstdlib>
 
 #include "disc_common.h"
-#include "fit_common.h"
-#include "ilmlp_common.h"
-#include "mlp_tiles.h"
+#include "ilmlp_fit.h"
 #include "oly_common.h"
 
 namespace {
-using namespace oly_ilmlp;
-using oly_disc::tanh32;
+using namespace oly_ilfit;
 using oly_fit::adam1;
-using oly_fit::NSP;
-using oly_fit::pt_index;
 using oly_fit::row_at;
 using oly_fit::stats_slice;
-using oly_fit::THREADS;
 static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
 
 constexpr int MAX_BATCH = 4096;
@@ -97,21 +93,18 @@ struct FitArgs {
 };
 
 // grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. NSP-1, minibatch 0's partials
-constexpr int PRO_BLOCKS = 64;
 __global__ __launch_bounds__(THREADS) void gfit_prologue_kernel(FitArgs a) {
   __shared__ double part[8 * IN_MAX];
-  for (int e = blockIdx.x * THREADS + threadIdx.x; e < H2 * H1; e += PRO_BLOCKS * THREADS)
-    a.ws[a.W.w2t + pt_index(H2, e / H1, e % H1)] = a.param[a.P.w2 + e];
+  build_w2t(a);
   if (blockIdx.x < NSP) stats_slice(a, a.off, a.R, blockIdx.x, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Launch A.  512 threads = 8 waves, two per SIMD: at 2048 rows the 128 workgroups leave every CU at most one, so a
+// Launch A.  RTHREADS = 512 threads = 8 waves, two per SIMD: at 2048 rows the 128 workgroups leave every CU at most one, so a
 // second wave per SIMD is what covers the other's weight loads and tanh32.  The forward kernel's chains: layer 1 wave w ->
 // column tiles 4w .. 4w+3, layer 2 -> 2w, 2w+1, the logit by wave 0 as one chain over k < 256 (column 0 of W3's first
 // tile).  Backward: dZ2 (wave w -> tiles 2w, 2w+1) and dH1 (wave w -> tiles 4w .. 4w+3, the chain over the 256 layer-2
 // units).
-constexpr int RTHREADS = 512;
 constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16 + H2 + 16;
 constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (2 * IN_MAX + 2 * 16);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
@@ -145,28 +138,19 @@ __global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(7, 8))
   if (tid < in_dim) {   // Standardizer.update_mean_std with the minibatch's rows (networks.py:76-81), as K15
     const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
     const int ds = a.ds;
-    double s = 0.0, ss = 0.0;
-    for (int p = 0; p < NSP; ++p) {
-      s += sp[p * 2 * IN_MAX + tid];
-      ss += sp[p * 2 * IN_MAX + IN_MAX + tid];
-    }
+    double s, ss;
+    slice_sums(sp, tid, s, ss);
     double mean = 0.0, sd = 1.0;        // an action column passes through: f32((f64(a) - 0) / 1) is a
     if (tid < ds) {
-      const double cnt = a.colstats[tid] + (double)R + 1e-2;
-      mean = (a.colstats[ds + tid] + s) / cnt;
-      sd = sqrt(fmax((a.colstats[2 * ds + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+      col_moments(a.colstats[tid] + (double)R, a.colstats[ds + tid] + s, a.colstats[2 * ds + tid] + ss, mean, sd);
     } else if (a.std2) {
       // a next-state column: the Standardizer has taken the minibatch's states in, then its next states
       // (preprocess_inputs, networks.py:224-227), so column j's statistics hold both sets of sums
       const int j = tid - ds;
-      double s1 = 0.0, ss1 = 0.0;
-      for (int p = 0; p < NSP; ++p) {
-        s1 += sp[p * 2 * IN_MAX + j];
-        ss1 += sp[p * 2 * IN_MAX + IN_MAX + j];
-      }
-      const double cnt = a.colstats[j] + (double)R + (double)R + 1e-2;
-      mean = ((a.colstats[ds + j] + s1) + s) / cnt;
-      sd = sqrt(fmax(((a.colstats[2 * ds + j] + ss1) + ss + 1e-2) / cnt - mean * mean, 1e-2));
+      double s1, ss1;
+      slice_sums(sp, j, s1, ss1);
+      col_moments(a.colstats[j] + (double)R + (double)R, (a.colstats[ds + j] + s1) + s, (a.colstats[2 * ds + j] + ss1) + ss,
+                  mean, sd);
     }
     st[tid] = mean;
     st[IN_MAX + tid] = sd;
@@ -202,10 +186,10 @@ __global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(7, 8))
       const int col = 16 * (4 * wave + t) + c;
       const float bv = P[P_B1 + col];
       float4 h;
-      h.x = tanh32(acc[0][t][0] + bv);
-      h.y = tanh32(acc[0][t][1] + bv);
-      h.z = tanh32(acc[0][t][2] + bv);
-      h.w = tanh32(acc[0][t][3] + bv);
+      h.x = Tanh::f(acc[0][t][0] + bv);
+      h.y = Tanh::f(acc[0][t][1] + bv);
+      h.z = Tanh::f(acc[0][t][2] + bv);
+      h.w = Tanh::f(acc[0][t][3] + bv);
       hA[act16_index(col, 4 * h4)] = h.x;
       hA[act16_index(col, 4 * h4 + 1)] = h.y;
       hA[act16_index(col, 4 * h4 + 2)] = h.z;
@@ -226,10 +210,10 @@ __global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(7, 8))
       const int col = 16 * (2 * wave + t) + c;
       const float bv = P[P_B2 + col];
       float4 h;
-      h.x = tanh32(acc[0][t][0] + bv);
-      h.y = tanh32(acc[0][t][1] + bv);
-      h.z = tanh32(acc[0][t][2] + bv);
-      h.w = tanh32(acc[0][t][3] + bv);
+      h.x = Tanh::f(acc[0][t][0] + bv);
+      h.y = Tanh::f(acc[0][t][1] + bv);
+      h.z = Tanh::f(acc[0][t][2] + bv);
+      h.w = Tanh::f(acc[0][t][3] + bv);
       hB[act16_index(col, 4 * h4)] = h.x;
       hB[act16_index(col, 4 * h4 + 1)] = h.y;
       hB[act16_index(col, 4 * h4 + 2)] = h.z;
@@ -283,46 +267,23 @@ __global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(7, 8))
       const int col = 16 * (2 * wave + t) + c;
       const float wc = w3[col];
       float4 g;
-      g.x = (dds[4 * h4] * wc) * (1.0f - h2r[t].x * h2r[t].x);
-      g.y = (dds[4 * h4 + 1] * wc) * (1.0f - h2r[t].y * h2r[t].y);
-      g.z = (dds[4 * h4 + 2] * wc) * (1.0f - h2r[t].z * h2r[t].z);
-      g.w = (dds[4 * h4 + 3] * wc) * (1.0f - h2r[t].w * h2r[t].w);
-      gz[act16_index(col, 4 * h4)] = g.x;
-      gz[act16_index(col, 4 * h4 + 1)] = g.y;
-      gz[act16_index(col, 4 * h4 + 2)] = g.z;
-      gz[act16_index(col, 4 * h4 + 3)] = g.w;
+      g.x = Tanh::back(dds[4 * h4] * wc, h2r[t].x);
+      g.y = Tanh::back(dds[4 * h4 + 1] * wc, h2r[t].y);
+      g.z = Tanh::back(dds[4 * h4 + 2] * wc, h2r[t].z);
+      g.w = Tanh::back(dds[4 * h4 + 3] * wc, h2r[t].w);
+      put_quad(gz, col, h4, g);
       ws4[(a.W.dz2 >> 2) + quad * H2 + col] = g;
     }
   }
   __syncthreads();
-  {  // ---- dZ1 = (dZ2 W2) (1 - h1^2)
-    f32x4 acc[1][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float4* a4[1] = {reinterpret_cast<const float4*>(gz)};
-    tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
-                         (H2 / 16) * 64, lane, acc);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int col = 16 * (4 * wave + t) + c;
-      float4 g;
-      const float h0 = hA[act16_index(col, 4 * h4)], h1v = hA[act16_index(col, 4 * h4 + 1)];
-      const float h2v = hA[act16_index(col, 4 * h4 + 2)], h3 = hA[act16_index(col, 4 * h4 + 3)];
-      g.x = acc[0][t][0] * (1.0f - h0 * h0);
-      g.y = acc[0][t][1] * (1.0f - h1v * h1v);
-      g.z = acc[0][t][2] * (1.0f - h2v * h2v);
-      g.w = acc[0][t][3] * (1.0f - h3 * h3);
-      ws4[(a.W.dz1 >> 2) + quad * H1 + col] = g;
-    }
-  }
+  // ---- dZ1 = (dZ2 W2) (1 - h1^2)
+  dz1_tiles<Tanh>(gz, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2),
+                  [&](int col) { return get_quad(hA, col, h4); }, ws4, a.W.dz1, quad);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Launch B.  Tiles (n-tile x k-tile): W1 32 x ceil(in / 16), W2 16 x 32, W3 1 x 16; the k-tile 0 of each layer also steps
-// the layer's bias.
-__host__ __device__ inline int weight_tiles(int in_dim) { return 32 * ((in_dim + 15) / 16) + 512 + 16; }
-
-constexpr int STEP_UNROLL = 4;      // 16-row steps whose loads are issued together
+// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is 1 x 16).  The dW chain and the waves' meeting are spelt out here,
+// not taken from ilmlp_fit.h as in K24 and K26: with the shared functions this kernel ran 1 to 3 % longer at 2048 rows.
 __global__ __launch_bounds__(THREADS) void gfit_weights_kernel(FitArgs a) {
   __shared__ float red[4 * 256];
   __shared__ float bred[4 * 64];
@@ -651,12 +612,6 @@ extern "C" int oly_gail_disc_fit_epoch_pair(oly_ctx* ctx, const oly_gail_disc_fi
   rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 1, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
                                 stream);
   if (rc != OLY_OK) return rc;
-  const unsigned bit = in_dim <= 32 ? 1u << 16 : 1u << 17;
-  if (!(ctx->gail_attr_done & bit)) {
-    OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(in_dim <= 32 ? gfit_rows_kernel<2> : gfit_rows_kernel<4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
-    ctx->gail_attr_done |= bit;
-  }
   oly_fit::set_minibatch(a, 0, nb, n_rows, batch);
   hipLaunchKernelGGL(gfit_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   for (int b = 0; b < nb; ++b) {
@@ -666,9 +621,10 @@ extern "C" int oly_gail_disc_fit_epoch_pair(oly_ctx* ctx, const oly_gail_disc_fi
     a.bce_out = f->bce_out ? f->bce_out + b : nullptr;
     a.ent_out = f->ent_out ? f->ent_out + b : nullptr;
     const dim3 grid_a((unsigned)((a.R + 15) / 16));
-    if (in_dim <= 32) hipLaunchKernelGGL(gfit_rows_kernel<2>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
-    else hipLaunchKernelGGL(gfit_rows_kernel<4>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
-    hipLaunchKernelGGL(gfit_weights_kernel, dim3(weight_tiles(in_dim)), dim3(THREADS), 0, oly_s(stream), a);
+    rc = launch_rows(ctx, ctx->gail_attr_done, 1u << 16, gfit_rows_kernel<2>, gfit_rows_kernel<4>, in_dim, grid_a, ROWS_LDS,
+                     stream, a);
+    if (rc != OLY_OK) return rc;
+    hipLaunchKernelGGL(gfit_weights_kernel, dim3(weight_tiles(in_dim, 1)), dim3(THREADS), 0, oly_s(stream), a);
   }
   OLY_LAUNCH_CHECK(ctx, "gail discriminator fit kernels");
   return OLY_OK;

@@ -22,27 +22,24 @@
 //                         workgroups 1 .. 16 sum step s+1's rows into the statistics partials launch A of s+1 reads.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits, and a call of n steps
 // leaves the bits of n calls of one step (the prologue rebuilds from param exactly what launch B keeps current).
-// Adam, the statistics fold and the weights kernel's tail are fit_common.h's, shared with K15, K16 and K18.
+// Adam, the statistics fold and the weights kernel's tail are fit_common.h's, shared with K15, K16 and K18; the two
+// launches' common phases (the Standardizer's head, the activation and its gradient, the row-quad stores, dZ1, the W2T
+// build, the dW chain, the waves' meeting, the rows kernel's dispatch) are ilmlp_fit.h's, shared with K18 and K26.
 //
 //   oly_bc_fit_steps_log  the same with the whole of logging() (:82-94): on a logging step, after launch B,
 //   L  K25's kernel (k25_sg_act.hip) on the rows idx[s] with the stepped stream and the statistics that hold them twice
 //   F  bc_log_fold_kernel  -mean(log_prob) into the step's fourth scalar; colstats += minibatch s a second time.
 #include <cstdlib>
 
-#include "fit_common.h"
-#include "ilmlp_common.h"
-#include "mlp_tiles.h"
+#include "ilmlp_fit.h"
 #include "oly_common.h"
 #include "sg_act.h"
 
 namespace {
-using namespace oly_ilmlp;
+using namespace oly_ilfit;
 using oly_fit::adam1;
-using oly_fit::NSP;
-using oly_fit::pt_index;
 using oly_fit::row_at;
 using oly_fit::stats_slice;
-using oly_fit::THREADS;
 static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
 
 constexpr int MAX_BATCH = OLY_BC_MAX_BATCH;   // loss_tree folds at most THREADS = 256 tiles of 16 rows
@@ -97,24 +94,19 @@ struct FitArgs {
 };
 
 // grid PRO_BLOCKS: the transposed streams from param (grid-stride) and, workgroups 0 .. NSP-1, step 0's partials
-constexpr int PRO_BLOCKS = 64;
 __global__ __launch_bounds__(THREADS) void bc_prologue_kernel(FitArgs a) {
   __shared__ double part[8 * IN_MAX];
-  for (int e = blockIdx.x * THREADS + threadIdx.x; e < H2 * H1; e += PRO_BLOCKS * THREADS)
-    a.ws[a.W.w2t + pt_index(H2, e / H1, e % H1)] = a.param[a.P.w2 + e];
+  build_w2t(a);
   for (int e = blockIdx.x * THREADS + threadIdx.x; e < OUTP * H2; e += PRO_BLOCKS * THREADS)
     a.ws[a.W.w3t + pt_index(OUTP, e / H2, e % H2)] = e / H2 < a.out_dim ? a.param[a.P.w3 + e] : 0.f;
   if (a.colstats && blockIdx.x < NSP) stats_slice(a, a.off, a.R, blockIdx.x, part);
 }
 
-__device__ __forceinline__ float relu32(float v) { return (v > 0.f || v != v) ? v : 0.f; }   // NaN kept like torch
-
 // ---------------------------------------------------------------------------------------------------------------
-// Launch A.  512 threads = 8 waves, two per SIMD (as K18: at the batches of this fit a CU holds one workgroup, so the
+// Launch A.  RTHREADS = 512 threads = 8 waves, two per SIMD (as K18: at the batches of this fit a CU holds one workgroup, so the
 // second wave per SIMD is what covers the other's weight loads).  Chains: layer 1 wave w -> column tiles 4w .. 4w+3,
 // layer 2 -> 2w, 2w+1, the output layer's tile t by wave t.  Backward: dH2 (wave w -> tiles 2w, 2w+1, the chain over the
 // 32 padded outputs) and dH1 (wave w -> tiles 4w .. 4w+3, the chain over the 256 layer-2 units).
-constexpr int RTHREADS = 512;
 constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16 + 2 * OUTP * 16;
 constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (2 * IN_MAX + 3 * 256 + 48);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
@@ -144,15 +136,12 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
 
   if (standardise && tid < in_dim) {   // Standardizer.update_mean_std with the minibatch's rows (networks.py:76-81), as K18
     const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
-    double s = 0.0, ss = 0.0;
-    for (int p = 0; p < NSP; ++p) {
-      s += sp[p * 2 * IN_MAX + tid];
-      ss += sp[p * 2 * IN_MAX + IN_MAX + tid];
-    }
-    const double cnt = a.colstats[tid] + (double)R + 1e-2;
-    const double mean = (a.colstats[in_dim + tid] + s) / cnt;
+    double s, ss;
+    slice_sums(sp, tid, s, ss);
+    double mean, sd;
+    col_moments(a.colstats[tid] + (double)R, a.colstats[in_dim + tid] + s, a.colstats[2 * in_dim + tid] + ss, mean, sd);
     st[tid] = mean;
-    st[IN_MAX + tid] = sqrt(fmax((a.colstats[2 * in_dim + tid] + ss + 1e-2) / cnt - mean * mean, 1e-2));
+    st[IN_MAX + tid] = sd;
     if (blockIdx.x == 0) {
       double* d = reinterpret_cast<double*>(ws + a.W.delta);
       d[tid] = s;
@@ -184,10 +173,10 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
       const int col = 16 * (4 * wave + t) + c;
       const float bv = P[P_B1 + col];
       float4 h;
-      h.x = relu32(acc[0][t][0] + bv);
-      h.y = relu32(acc[0][t][1] + bv);
-      h.z = relu32(acc[0][t][2] + bv);
-      h.w = relu32(acc[0][t][3] + bv);
+      h.x = Relu::f(acc[0][t][0] + bv);
+      h.y = Relu::f(acc[0][t][1] + bv);
+      h.z = Relu::f(acc[0][t][2] + bv);
+      h.w = Relu::f(acc[0][t][3] + bv);
       hA[act16_index(col, 4 * h4)] = h.x;
       hA[act16_index(col, 4 * h4 + 1)] = h.y;
       hA[act16_index(col, 4 * h4 + 2)] = h.z;
@@ -208,10 +197,10 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
       const int col = 16 * (2 * wave + t) + c;
       const float bv = P[P_B2 + col];
       float4 h;
-      h.x = relu32(acc[0][t][0] + bv);
-      h.y = relu32(acc[0][t][1] + bv);
-      h.z = relu32(acc[0][t][2] + bv);
-      h.w = relu32(acc[0][t][3] + bv);
+      h.x = Relu::f(acc[0][t][0] + bv);
+      h.y = Relu::f(acc[0][t][1] + bv);
+      h.z = Relu::f(acc[0][t][2] + bv);
+      h.w = Relu::f(acc[0][t][3] + bv);
       hB[act16_index(col, 4 * h4)] = h.x;
       hB[act16_index(col, 4 * h4 + 1)] = h.y;
       hB[act16_index(col, 4 * h4 + 2)] = h.z;
@@ -281,14 +270,11 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
     for (int t = 0; t < 2; ++t) {
       const int col = 16 * (2 * wave + t) + c;
       float4 g;
-      g.x = h2r[t].x > 0.f ? acc[0][t][0] : 0.f;
-      g.y = h2r[t].y > 0.f ? acc[0][t][1] : 0.f;
-      g.z = h2r[t].z > 0.f ? acc[0][t][2] : 0.f;
-      g.w = h2r[t].w > 0.f ? acc[0][t][3] : 0.f;
-      gz[act16_index(col, 4 * h4)] = g.x;
-      gz[act16_index(col, 4 * h4 + 1)] = g.y;
-      gz[act16_index(col, 4 * h4 + 2)] = g.z;
-      gz[act16_index(col, 4 * h4 + 3)] = g.w;
+      g.x = Relu::back(acc[0][t][0], h2r[t].x);
+      g.y = Relu::back(acc[0][t][1], h2r[t].y);
+      g.z = Relu::back(acc[0][t][2], h2r[t].z);
+      g.w = Relu::back(acc[0][t][3], h2r[t].w);
+      put_quad(gz, col, h4, g);
       ws4[(a.W.dz2 >> 2) + quad * H2 + col] = g;
     }
   }
@@ -305,40 +291,19 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
       lp[2 * tiles_n + 2 * blockIdx.x + 1] = 0.0;
     }
   }
-  {  // ---- dZ1 = (dZ2 W2) [h1 > 0]
-    f32x4 acc[1][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float4* a4[1] = {reinterpret_cast<const float4*>(gz)};
-    tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
-                         (H2 / 16) * 64, lane, acc);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int col = 16 * (4 * wave + t) + c;
-      float4 g;
-      g.x = hA[act16_index(col, 4 * h4)] > 0.f ? acc[0][t][0] : 0.f;
-      g.y = hA[act16_index(col, 4 * h4 + 1)] > 0.f ? acc[0][t][1] : 0.f;
-      g.z = hA[act16_index(col, 4 * h4 + 2)] > 0.f ? acc[0][t][2] : 0.f;
-      g.w = hA[act16_index(col, 4 * h4 + 3)] > 0.f ? acc[0][t][3] : 0.f;
-      ws4[(a.W.dz1 >> 2) + quad * H1 + col] = g;
-    }
-  }
+  // ---- dZ1 = (dZ2 W2) [h1 > 0]
+  dz1_tiles<Relu>(gz, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2),
+                  [&](int col) { return get_quad(hA, col, h4); }, ws4, a.W.dz1, quad);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Launch B.  Tiles (n-tile x k-tile): W1 32 x ceil(in / 16), W2 16 x 32, W3 (1 or 2) x 16; the k-tile 0 of each layer also
-// steps the layer's bias.
-__host__ __device__ inline int weight_tiles(int in_dim, int out_dim) {
-  return 32 * ((in_dim + 15) / 16) + 512 + 16 * ((out_dim + 15) / 16);
-}
-
-constexpr int STEP_UNROLL = 4;      // 16-row steps whose loads are issued together
+// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is (1 or 2) x 16).
 constexpr double HALF_LOG_2PI_P1 = 0.5 + 0.5 * 1.8378770664093454835606594728112;   // 0.5 + 0.5 log(2 pi)
 __global__ __launch_bounds__(THREADS) void bc_weights_kernel(FitArgs a) {
   __shared__ float red[4 * 256];
   __shared__ float bred[4 * 64];
   __shared__ double dred[2 * THREADS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, h4 = lane >> 4;
+  const int tid = threadIdx.x;
   const WsL& W = a.W;
   const ParamLayout& PL = a.P;
   const int kt0 = (a.in_dim + 15) / 16;
@@ -357,38 +322,11 @@ __global__ __launch_bounds__(THREADS) void bc_weights_kernel(FitArgs a) {
   const int K = layer == 0 ? a.in_dim : aw;
   const float4* dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.dz1 : layer == 1 ? W.dz2 : W.dz3));
   const float4* al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.xs : layer == 1 ? W.h1 : W.h2));
-  const int n0 = 16 * nt, k0 = 16 * kt, R = a.R;
-  const bool n_ok = n0 + c < N, k_ok = k0 + c < K;
-  // a step = the 16 rows of one tile of launch A (which wrote all 16: zeros in the deltas beyond the minibatch); lane
-  // group h4 takes the step's row quad h4.  Wave w: steps [w Q, min(steps, (w + 1) Q))
-  const int steps = (R + 15) / 16, Q = (steps + 3) / 4, s0 = wave * Q, s1 = min(steps, s0 + Q);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float bsum = 0.f;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int s = s0; s < s1; s += STEP_UNROLL) {
-    float4 dv[STEP_UNROLL], av[STEP_UNROLL];
-#pragma unroll
-    for (int u = 0; u < STEP_UNROLL; ++u) {
-      const size_t q = (size_t)4 * (s + u) + h4;
-      const bool in = s + u < s1;
-      dv[u] = (in && n_ok) ? dl[q * dw + n0 + c] : zero4;
-      av[u] = (in && k_ok) ? al[q * aw + k0 + c] : zero4;
-    }
-#pragma unroll
-    for (int u = 0; u < STEP_UNROLL; ++u) {
-      // A[i = lane & 15][r = lane >> 4] = delta[row 4 q + r][n0 + i], B[r][j = lane & 15] = a[row 4 q + r][k0 + j]
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].x, av[u].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].y, av[u].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].z, av[u].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].w, av[u].w, acc, 0, 0, 0);
-      bsum += ((dv[u].x + dv[u].y) + dv[u].z) + dv[u].w;
-    }
-  }
-  // D[n = 4 (lane >> 4) + i][k = lane & 15]
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[wave * 256 + (4 * h4 + i) * 16 + c] = acc[i];
-  bred[wave * 64 + lane] = bsum;
-  __syncthreads();
+  const int n0 = 16 * nt, k0 = 16 * kt, R = a.R, steps = (R + 15) / 16;
+  f32x4 acc;
+  float bsum;
+  dw_accumulate(dl, al, dw, aw, n0, N, k0, K, steps, acc, bsum);
+  meet_waves(red, bred, acc, bsum);
   {
     const int nn = tid >> 4, kk = tid & 15, ne = n0 + nn, ke = k0 + kk;
     if (ne < N && ke < K) {
@@ -540,12 +478,6 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
   rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 2 * A, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
                       stream);
   if (rc != OLY_OK) return rc;
-  const unsigned bit = in_dim <= 32 ? 1u : 2u;
-  if (!(ctx->bcfit_attr_done & bit)) {
-    OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(in_dim <= 32 ? bc_rows_kernel<2> : bc_rows_kernel<4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
-    ctx->bcfit_attr_done |= bit;
-  }
   a.off = 0;
   hipLaunchKernelGGL(bc_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   const dim3 grid_a((unsigned)((batch + 15) / 16)), grid_b((unsigned)weight_tiles(in_dim, 2 * A));
@@ -557,8 +489,8 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
     a.Rn = s + 1 < n_steps ? batch : 0;
     a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->eps, f->lr, (long)f->step + s + 1);
     a.out = f->out + out_w * (size_t)s;
-    if (in_dim <= 32) hipLaunchKernelGGL(bc_rows_kernel<2>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
-    else hipLaunchKernelGGL(bc_rows_kernel<4>, grid_a, dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
+    rc = launch_rows(ctx, ctx->bcfit_attr_done, 1u, bc_rows_kernel<2>, bc_rows_kernel<4>, in_dim, grid_a, ROWS_LDS, stream, a);
+    if (rc != OLY_OK) return rc;
     hipLaunchKernelGGL(bc_weights_kernel, grid_b, dim3(THREADS), 0, oly_s(stream), a);
     if (lg && ((long)lg->iter0 + s) % lg->logging_iter == 0) {
       // logging() (behavioral_cloning.py:82-94): compute_action_and_log_prob on the minibatch.  colstats holds idx[s] once

@@ -16,26 +16,22 @@
 //                          values, narrowed once), and the backward of every pass that carries a gradient through the
 //                          relus from the stored outputs.  Activations and deltas go to the workspace in row quads, one
 //                          slot of BP rows per gradient pass; the tile's loss sums to fixed slots.
-//   B  iq_weights_kernel   K24's launch B: one 16 x 16 weight tile per workgroup, dW summed over the slots' rows in a
+//   B  iq_weights_kernel   the launch B of ilmlp_fit.h, as K24: one 16 x 16 weight tile per workgroup, dW summed over the slots' rows in a
 //                          fixed order, weight decay, Adam, the stepped value into param, the moments and the packed
 //                          stream; with update_target the soft target update f32(tau) w + f32(1 - tau) t (two float32
 //                          products, one add) into target_param and its packed stream; the tile's sum of squared
 //                          gradients to a fixed slot.
 //   F  iq_fold_kernel      one workgroup: the 16 scalars from the per-tile partials, the two Standardizers' sums.
-// Every reduction has a fixed order and there are no atomics: two runs give identical bits.
+// Every reduction has a fixed order and there are no atomics: two runs give identical bits.  The Standardizer's head, the
+// hidden layers, dZ1, the dW chain and the waves' meeting are ilmlp_fit.h's, shared with K18 and K24.
 #include <cstdlib>
 
-#include "fit_common.h"
-#include "ilmlp_common.h"
-#include "mlp_tiles.h"
+#include "ilmlp_fit.h"
 #include "oly_common.h"
 
 namespace {
-using namespace oly_ilmlp;
+using namespace oly_ilfit;
 using oly_fit::adam1;
-using oly_fit::NSP;
-using oly_fit::pt_index;
-using oly_fit::THREADS;
 static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
 
 constexpr int MAX_BATCH = OLY_BC_MAX_BATCH;
@@ -101,12 +97,10 @@ __device__ __forceinline__ float input_at(const QArgs& a, int src, size_t row, i
 
 // grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. 3 NSP - 1, slice b % NSP of input
 // b / NSP: four row-strided chains per column, met in a fixed order (fit_common.h's fold_chains)
-constexpr int PRO_BLOCKS = 64;
 static_assert(3 * NSP <= PRO_BLOCKS, "one workgroup per statistics slice");
 __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
   __shared__ double part[8 * IN_MAX];
-  for (int e = blockIdx.x * THREADS + threadIdx.x; e < H2 * H1; e += PRO_BLOCKS * THREADS)
-    a.ws[a.W.w2t + pt_index(H2, e / H1, e % H1)] = a.param[a.P.w2 + e];
+  build_w2t(a);
   const int src = blockIdx.x / NSP, s = blockIdx.x % NSP;
   if (src >= 3 || (src == 2 && !a.has_v) || (!a.colstats && !a.tcolstats)) return;
   const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
@@ -122,13 +116,10 @@ __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
                        reinterpret_cast<double*>(a.ws + a.W.statp) + (size_t)(src * NSP + s) * 2 * IN_MAX);
 }
 
-__device__ __forceinline__ float relu32(float v) { return (v > 0.f || v != v) ? v : 0.f; }   // NaN kept like torch
-
 // ---------------------------------------------------------------------------------------------------------------
-// Launch A.  512 threads = 8 waves, K24's chains: layer 1 wave w -> column tiles 4w .. 4w+3, layer 2 -> 2w, 2w+1, the
+// Launch A.  RTHREADS = 512 threads = 8 waves, the chains of ilmlp_fit.h: layer 1 wave w -> column tiles 4w .. 4w+3, layer 2 -> 2w, 2w+1, the
 // output column by wave 0 as one chain over k < 256.  Backward: dZ2 = dQ W3 [h2 > 0] (one float32 product per element:
 // the output layer has one unit), dH1 = dZ2 W2 on the matrix cores (wave w -> tiles 4w .. 4w+3, the transposed stream).
-constexpr int RTHREADS = 512;
 constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16;
 constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (3 * 2 * IN_MAX + 16 * NTERM);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
@@ -157,11 +148,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
     double s[3], ss[3];
     for (int p = 0; p < 3; ++p) {
       s[p] = ss[p] = 0.0;
-      if ((a.colstats || a.tcolstats) && (p < 2 || a.has_v))
-        for (int q = 0; q < NSP; ++q) {
-          s[p] += sp[(size_t)(p * NSP + q) * 2 * IN_MAX + tid];
-          ss[p] += sp[(size_t)(p * NSP + q) * 2 * IN_MAX + IN_MAX + tid];
-        }
+      if ((a.colstats || a.tcolstats) && (p < 2 || a.has_v)) slice_sums(sp + (size_t)p * NSP * 2 * IN_MAX, tid, s[p], ss[p]);
     }
     if (blockIdx.x == 0) {
       double* d = reinterpret_cast<double*>(ws + a.W.delta);
@@ -186,11 +173,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
         pc = cnt, ps = sum, pq = sq;
       }
       double mean = 0.0, sd = 1.0;
-      if (have) {
-        const double n = pc + 1e-2;
-        mean = ps / n;
-        sd = sqrt(fmax((pq + 1e-2) / n - mean * mean, 1e-2));
-      }
+      if (have) col_moments(pc, ps, pq, mean, sd);
       st[(p * 2) * IN_MAX + tid] = mean;
       st[(p * 2 + 1) * IN_MAX + tid] = sd;
     }
@@ -222,51 +205,10 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
       if (slot >= 0) ws[a.W.xs + (((srow0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
     }
     __syncthreads();
-    {  // ---- layer 1: [16, D] x [D, 512]
-      f32x4 acc[1][4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float4* a4[1] = {reinterpret_cast<const float4*>(xT)};
-      tiles<G1, 4, 1>(a4, P4 + P_W1 / 4 + (size_t)(4 * wave) * (IN_MAX / 16) * 64, (IN_MAX / 16) * 64, lane, acc);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int col = 16 * (4 * wave + t) + c;
-        const float bv = P[P_B1 + col];
-        float4 h;
-        h.x = relu32(acc[0][t][0] + bv);
-        h.y = relu32(acc[0][t][1] + bv);
-        h.z = relu32(acc[0][t][2] + bv);
-        h.w = relu32(acc[0][t][3] + bv);
-        hA[act16_index(col, 4 * h4)] = h.x;
-        hA[act16_index(col, 4 * h4 + 1)] = h.y;
-        hA[act16_index(col, 4 * h4 + 2)] = h.z;
-        hA[act16_index(col, 4 * h4 + 3)] = h.w;
-        if (slot >= 0) ws4[(a.W.h1 >> 2) + quad * H1 + col] = h;
-      }
-    }
+    // ---- layer 1: [16, D] x [D, 512], layer 2: [16, 512] x [512, 256]; a pass without a gradient keeps no activations
+    hidden_layer<Relu, G1, IN_MAX / 16, 4, P_W1, P_B1>(xT, P, hA, slot >= 0, ws4, a.W.h1, quad);
     __syncthreads();
-    {  // ---- layer 2: [16, 512] x [512, 256]
-      f32x4 acc[1][2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float4* a4[1] = {reinterpret_cast<const float4*>(hA)};
-      tiles<H1 / 16, 2, 1>(a4, P4 + P_W2 / 4 + (size_t)(2 * wave) * (H1 / 16) * 64, (H1 / 16) * 64, lane, acc);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int col = 16 * (2 * wave + t) + c;
-        const float bv = P[P_B2 + col];
-        float4 h;
-        h.x = relu32(acc[0][t][0] + bv);
-        h.y = relu32(acc[0][t][1] + bv);
-        h.z = relu32(acc[0][t][2] + bv);
-        h.w = relu32(acc[0][t][3] + bv);
-        hB[act16_index(col, 4 * h4)] = h.x;
-        hB[act16_index(col, 4 * h4 + 1)] = h.y;
-        hB[act16_index(col, 4 * h4 + 2)] = h.z;
-        hB[act16_index(col, 4 * h4 + 3)] = h.w;
-        if (slot >= 0) ws4[(a.W.h2 >> 2) + quad * H2 + col] = h;
-      }
-    }
+    hidden_layer<Relu, H1 / 16, H1 / 16, 2, P_W2, P_B2>(hA, P, hB, slot >= 0, ws4, a.W.h2, quad);
     __syncthreads();
     if (wave == 0) {  // ---- the output unit: one chain over k < 256, as the forward kernel
       f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
@@ -381,42 +323,20 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
         g.y = h.y > 0.f && sub[4 * h4 + 1] >= 0 ? coef[p][4 * h4 + 1] * w3 : 0.f;
         g.z = h.z > 0.f && sub[4 * h4 + 2] >= 0 ? coef[p][4 * h4 + 2] * w3 : 0.f;
         g.w = h.w > 0.f && sub[4 * h4 + 3] >= 0 ? coef[p][4 * h4 + 3] * w3 : 0.f;
-        gz[act16_index(col, 4 * h4)] = g.x;
-        gz[act16_index(col, 4 * h4 + 1)] = g.y;
-        gz[act16_index(col, 4 * h4 + 2)] = g.z;
-        gz[act16_index(col, 4 * h4 + 3)] = g.w;
+        put_quad(gz, col, h4, g);
         ws4[(a.W.dz2 >> 2) + quad * H2 + col] = g;
       }
     }
     __syncthreads();
-    {  // ---- dZ1 = (dZ2 W2) [h1 > 0]
-      f32x4 acc[1][4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float4* a4[1] = {reinterpret_cast<const float4*>(gz)};
-      tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
-                           (H2 / 16) * 64, lane, acc);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int col = 16 * (4 * wave + t) + c;
-        const float4 h = ws4[(a.W.h1 >> 2) + quad * H1 + col];
-        float4 g;
-        g.x = h.x > 0.f ? acc[0][t][0] : 0.f;
-        g.y = h.y > 0.f ? acc[0][t][1] : 0.f;
-        g.z = h.z > 0.f ? acc[0][t][2] : 0.f;
-        g.w = h.w > 0.f ? acc[0][t][3] : 0.f;
-        ws4[(a.W.dz1 >> 2) + quad * H1 + col] = g;
-      }
-    }
+    // ---- dZ1 = (dZ2 W2) [h1 > 0]; hA holds a later pass by now: the stored h1 comes from the workspace
+    dz1_tiles<Relu>(gz, reinterpret_cast<const float4*>(ws) + (a.W.w2t >> 2),
+                    [&](int col) { return ws4[(a.W.h1 >> 2) + quad * H1 + col]; }, ws4, a.W.dz1, quad);
     __syncthreads();
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Launch B.  Tiles (n-tile x k-tile): W1 32 x ceil(D / 16), W2 16 x 32, W3 1 x 16; the k-tile 0 of each layer also steps
-// the layer's bias.
-__host__ __device__ inline int weight_tiles(int D) { return 32 * ((D + 15) / 16) + 512 + 16; }
-
+// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is 1 x 16).
 // the soft target update of the parameter at i (packed at pk): f32(tau) w + f32(1 - tau) t
 __device__ __forceinline__ void step_target(const QArgs& a, size_t i, size_t pk, float p) {
   if (!a.update_target) return;
@@ -425,13 +345,12 @@ __device__ __forceinline__ void step_target(const QArgs& a, size_t i, size_t pk,
   a.tpacked[pk] = t;
 }
 
-constexpr int STEP_UNROLL = 4;      // 16-row steps whose loads are issued together
 __global__ __launch_bounds__(THREADS) void iq_weights_kernel(QArgs a) {
   __shared__ float red[4 * 256];
   __shared__ float bred[4 * 64];
   __shared__ double dred[THREADS];
   __shared__ double bsq[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, h4 = lane >> 4;
+  const int tid = threadIdx.x;
   const WsL& W = a.W;
   const ParamLayout& PL = a.P;
   const int kt0 = (a.D + 15) / 16;
@@ -451,37 +370,11 @@ __global__ __launch_bounds__(THREADS) void iq_weights_kernel(QArgs a) {
   const float4* dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.dz1 : layer == 1 ? W.dz2 : W.dz3));
   const float4* al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.xs : layer == 1 ? W.h1 : W.h2));
   const int n0 = 16 * nt, k0 = 16 * kt;
-  const bool n_ok = n0 + c < N, k_ok = k0 + c < K;
-  // a step = the 16 rows of one tile of launch A in one slot (which wrote all 16: zeros in the deltas beyond the batch);
-  // lane group h4 takes the step's row quad h4.  Wave w: steps [w Q, min(steps, (w + 1) Q))
-  const int steps = a.n_slots * ((a.B + 15) / 16), Q = (steps + 3) / 4, s0 = wave * Q, s1 = min(steps, s0 + Q);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float bsum = 0.f;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int s = s0; s < s1; s += STEP_UNROLL) {
-    float4 dv[STEP_UNROLL], av[STEP_UNROLL];
-#pragma unroll
-    for (int u = 0; u < STEP_UNROLL; ++u) {
-      const size_t q = (size_t)4 * (s + u) + h4;
-      const bool in = s + u < s1;
-      dv[u] = (in && n_ok) ? dl[q * dw + n0 + c] : zero4;
-      av[u] = (in && k_ok) ? al[q * aw + k0 + c] : zero4;
-    }
-#pragma unroll
-    for (int u = 0; u < STEP_UNROLL; ++u) {
-      // A[i = lane & 15][r = lane >> 4] = delta[row 4 q + r][n0 + i], B[r][j = lane & 15] = a[row 4 q + r][k0 + j]
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].x, av[u].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].y, av[u].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].z, av[u].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[u].w, av[u].w, acc, 0, 0, 0);
-      bsum += ((dv[u].x + dv[u].y) + dv[u].z) + dv[u].w;
-    }
-  }
-  // D[n = 4 (lane >> 4) + i][k = lane & 15]
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[wave * 256 + (4 * h4 + i) * 16 + c] = acc[i];
-  bred[wave * 64 + lane] = bsum;
-  __syncthreads();
+  // the steps run over the rows of every slot
+  f32x4 acc;
+  float bsum;
+  dw_accumulate(dl, al, dw, aw, n0, N, k0, K, a.n_slots * ((a.B + 15) / 16), acc, bsum);
+  meet_waves(red, bred, acc, bsum);
   {
     const int nn = tid >> 4, kk = tid & 15, ne = n0 + nn, ke = k0 + kk;
     double g2 = 0.0;
@@ -705,16 +598,10 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
   a.P = param_layout(D, 1);
   a.W = W;
 
-  const unsigned bit = D <= 32 ? 1u : 2u;
-  if (!(ctx->iqq_attr_done & bit)) {
-    OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(D <= 32 ? iq_rows_kernel<2> : iq_rows_kernel<4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS));
-    ctx->iqq_attr_done |= bit;
-  }
-  const int tiles_a = (B + 15) / 16, tiles_b = weight_tiles(D);
+  const int tiles_a = (B + 15) / 16, tiles_b = weight_tiles(D, 1);
   hipLaunchKernelGGL(iq_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
-  if (D <= 32) hipLaunchKernelGGL(iq_rows_kernel<2>, dim3(tiles_a), dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
-  else hipLaunchKernelGGL(iq_rows_kernel<4>, dim3(tiles_a), dim3(RTHREADS), ROWS_LDS, oly_s(stream), a);
+  rc = launch_rows(ctx, ctx->iqq_attr_done, 1u, iq_rows_kernel<2>, iq_rows_kernel<4>, D, dim3(tiles_a), ROWS_LDS, stream, a);
+  if (rc != OLY_OK) return rc;
   hipLaunchKernelGGL(iq_weights_kernel, dim3(tiles_b), dim3(THREADS), 0, oly_s(stream), a);
   hipLaunchKernelGGL(iq_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), a, tiles_a, tiles_b);
   OLY_LAUNCH_CHECK(ctx, "soft-Q critic update kernels");
