@@ -5,12 +5,13 @@ only the allocator/stream provider here; every computation is a HIP kernel of
 libolympic_hip.so running on torch's current stream.
 """
 import ctypes as C
+import types
 
 import numpy as np
 import torch
 
 from . import _abi
-from ._ffi import Context, OlyError, ptr
+from ._ffi import Context, OlyError, lib, ptr
 
 
 def _req(t, name, shape, dtype, device, optional=False):
@@ -29,6 +30,28 @@ def _req(t, name, shape, dtype, device, optional=False):
     if not t.is_contiguous():
         raise OlyError(f"{name}: tensor must be contiguous")
     return t
+
+
+# What the host layer knows of the two discriminator networks (VAIL: K12 / K15, GAIL: K18), for the bodies the two
+# share below: the pack method the `weights` of a reward step follow and their shapes (the flat parameter vector of a
+# fit is their concatenation, n_par values), the packed-size method, the outputs of a forward, whether a forward takes
+# noise, and what the fit adds to the common arguments: the entry points' stem, the struct, its own scalars and its own
+# tensors as (name, shape key of _disc_fit_epoch, dtype, optional).
+_VAIL = types.SimpleNamespace(
+    pack="disc_pack", packed_floats="_disc_packed_floats", noise=True,
+    weights=lambda D: ((256, D), (256,), (128, 256), (128,), (128, 128), (128,), (128, 128), (128,), (1, 128), (1,)),
+    outputs=lambda B: dict(reward=(B,), logits=(B,), mu=(B, 128), logvar=(B, 128)),
+    n_par=lambda D: 256 * D + 256 + 128 * 256 + 128 + 2 * (128 * 128 + 128) + 128 + 1,
+    fit="disc_fit", struct=_abi.DiscFit, fit_scalars=("info_constraint", "lr_beta"),
+    fit_tensors=(("eps", "noise", torch.float32, False), ("beta", "one", torch.float32, False),
+                 ("kl_out", "batches", torch.float64, True), ("beta_out", "batches", torch.float32, True)))
+_GAIL = types.SimpleNamespace(
+    pack="ilmlp_pack", packed_floats="_gail_packed_floats", noise=False,
+    weights=lambda D: ((512, D), (512,), (256, 512), (256,), (1, 256), (1,)),
+    outputs=lambda B: dict(reward=(B,), logits=(B,)),
+    n_par=lambda D: 512 * D + 512 + 256 * 512 + 256 + 256 + 1,
+    fit="gail_disc_fit", struct=_abi.GailDiscFit, fit_scalars=("entcoeff",),
+    fit_tensors=(("ent_out", "batches", torch.float64, True),))
 
 
 class Engine:
@@ -714,14 +737,170 @@ class Engine:
         self.ctx.call("oly_il_critic_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
         return loss_out
 
-    # -------------------------------------------------------------- K15 (VAIL discriminator fit)
+    # -------------------------------------------------------------- what the two discriminators' methods share
+    # `net` is _VAIL or _GAIL, `name` the public method, which is also its entry point without the oly_ prefix, and
+    # `second` None for states only or (x2, mask2, standardise) for a paired input: (s, s') with use_next_states, (s, a)
+    # with actions (networks.py:216-234, 258-278).  Every path calls its own entry point.
+    def _disc_head(self, name, x, mask, second):
+        """x [B,Dx] f32, its mask [Ds] int32 or None (Ds = Dx) and the oly_disc_pair block of `second` -> (B, Dx, Ds,
+        block or None, D2 or 0)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise OlyError("x: expected a [B,Dx] tensor")
+        B, Dx = (int(v) for v in x.shape)
+        _req(x, "x", (B, Dx), torch.float32, self.device)
+        Ds = Dx if mask is None else int(mask.shape[0])
+        _req(mask, "mask", (Ds,), torch.int32, self.device, optional=True)
+        pair, d2 = (None, 0) if second is None else self._disc_pair(name, second[0], second[1], second[2], B, Ds)
+        return B, Dx, Ds, pair, d2
+
+    def _disc_pair(self, name, x2, mask2, standardise, rows, Ds):
+        """The oly_disc_pair block of x2 [rows, W2] f32 (mask2 [d2] int32 or None) -> (block, d2).  Refused: an empty
+        second part, Ds + d2 > 64, next states of another width than the states."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(x2, torch.Tensor) or x2.dim() != 2:
+            raise OlyError(f"{name}: x2: expected a [rows,W2] tensor")
+        W2 = int(x2.shape[1])
+        _req(x2, "x2", (rows, W2), f32, dv)
+        d2 = W2 if mask2 is None else int(mask2.shape[0])
+        _req(mask2, "mask2", (d2,), torch.int32, dv, optional=True)
+        if d2 <= 0:
+            raise OlyError(f"{name}: the second part has no column (D2 == 0)")
+        if Ds + d2 > 64:
+            raise OlyError(f"{name}: the paired input is {Ds} + {d2} columns wide, the kernels take at most 64")
+        if standardise and d2 != Ds:
+            raise OlyError(f"{name}: next states have {d2} masked columns, the states {Ds}")
+        return _abi.DiscPair(x2=x2.data_ptr(), mask2=ptr(mask2), stride2=W2, d2=d2, standardise=int(bool(standardise))), d2
+
+    def _disc_weights(self, name, net, weights, D):
+        """The pointer array of `weights` (the tensors of net.pack in its order, re-packed inside the call) or None."""
+        if weights is None:
+            return None
+        shapes = net.weights(D)
+        if len(weights) != len(shapes):
+            raise OlyError(f"{name}: weights = the {len(shapes)} tensors of {net.pack}")
+        for i, (t, sh) in enumerate(zip(weights, shapes)):
+            _req(t, f"weights[{i}]", sh, torch.float32, self.device)
+        return (C.c_void_p * len(shapes))(*[t.data_ptr() for t in weights])
+
+    def _disc_outputs(self, name, shapes, want, out):
+        """The outputs `want` among `shapes` (the caller's out[k], validated, or fresh) -> (dict, the pointer or None of
+        every output in shapes' order)."""
+        f32, dv = torch.float32, self.device
+        out = dict(out or {})
+        if not want:
+            raise OlyError(f"{name}: no output requested")
+        for k in want:
+            if k not in shapes:
+                raise OlyError(f"{name}: unknown output {k!r}")
+            out[k] = _req(out.get(k) if out.get(k) is not None else self._new(shapes[k], f32), k, shapes[k], f32, dv)
+        return out, tuple(ptr(out[k]) if k in want else None for k in shapes)
+
+    def _disc_forward_on(self, net, name, x, packed, mask, stats, second, eps, want, out):
+        """A forward on given statistics: stats = (mean, std, colstats) for states only, (stats_a, stats_b) for a pair."""
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        B, Dx, Ds, pair, d2 = self._disc_head(name, x, mask, second)
+        if pair is None:
+            mean, std, colstats = stats
+            if (mean is None) != (std is None) or (mean is not None and colstats is not None):
+                raise OlyError(f"{name}: give mean and std together, or colstats, or neither")
+            _req(colstats, "colstats", (3, Ds), f64, dv, optional=True)
+            _req(mean, "mean", (Ds,), f64, dv, optional=True)
+            _req(std, "std", (Ds,), f64, dv, optional=True)
+            stats = (ptr(mean), ptr(std), ptr(colstats))
+        else:
+            stats_a, stats_b = stats
+            _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=True)
+            _req(stats_b, "stats_b", (3, Ds), f64, dv, optional=True)
+            if second[2] and (stats_a is None) != (stats_b is None):
+                raise OlyError(f"{name}: give stats_a and stats_b together")
+            stats = (C.byref(pair), ptr(stats_a), ptr(stats_b))
+        _req(packed, "packed", (getattr(self, net.packed_floats)(Ds + d2),), f32, dv)   # the raw pointer carries no length
+        noise = ()
+        if net.noise:
+            noise = (ptr(_req(eps, "eps", (B, 128), f32, dv, optional=True)),)
+        out, outs = self._disc_outputs(name, net.outputs(B), want, out)
+        self.ctx.call("oly_" + name, C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), *stats, ptr(packed), *noise, *outs, self._s())
+        return out
+
+    def _disc_reward_step_args(self, net, name, x, packed, colstats, stats_a, mask, second, eps, want, out, weights):
+        """A reward step's arguments, validated -> (out, the arguments before `accumulate`, those after it)."""
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        B, Dx, Ds, pair, d2 = self._disc_head(name, x, mask, second)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        head = (C.c_int64(B), Dx, Ds, ptr(x), ptr(mask))
+        if pair is None:
+            head += (ptr(colstats),)
+        else:
+            _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=not second[2])
+            head += (C.byref(pair), ptr(colstats), ptr(stats_a))
+        _req(packed, "packed", (getattr(self, net.packed_floats)(Ds + d2),), f32, dv)
+        noise = ()
+        if net.noise:
+            noise = (ptr(_req(eps, "eps", (B, 128), f32, dv, optional=True)),)
+        wp = self._disc_weights(name, net, weights, Ds + d2)
+        out, outs = self._disc_outputs(name, net.outputs(B), want, out)
+        return out, head, (wp, ptr(packed), *noise, *outs)
+
+    def _disc_fit_ws_floats(self, net, name, batch, ds, d2=None, standardise=False):
+        """The floats of a fit workspace for minibatches of `batch` rows of ds (d2 None) or ds + d2 columns."""
+        if d2 is None:
+            n = int(getattr(lib(), f"oly_{net.fit}_ws_floats")(int(batch), int(ds)))
+            if n < 0:
+                raise OlyError(f"{name}: unsupported batch={batch} in={ds} (0 < batch <= 4096, in <= 64)")
+            return n
+        n = int(getattr(lib(), f"oly_{net.fit}_pair_ws_floats")(int(batch), int(ds), int(d2), int(bool(standardise))))
+        if n < 0:
+            raise OlyError(f"{name}: unsupported batch={batch}, {ds} + {d2} columns (0 < batch <= 4096, 0 < D2, "
+                           "Ds + D2 <= 64, next states as wide as the states)")
+        return n
+
+    def _disc_fit_epoch(self, net, name, x, second, n_plcy, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed, ws,
+                        step, lr, beta1, beta2, adam_eps, weight_decay, targets, loss_out, bce_out, **own):
+        """One epoch of either discriminator's minibatch loop; `own` holds net.fit_scalars and net.fit_tensors."""
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        n, _, Ds, pair, d2 = self._disc_head(name, x, None, second)
+        batch, in_dim = int(batch), Ds + d2
+        nws = self._disc_fit_ws_floats(net, name, batch, Ds, *(() if pair is None else (d2, second[2])))
+        if not 0 <= int(n_plcy) <= n:
+            raise OlyError(f"{name}: n_plcy={n_plcy} outside [0, {n}]")
+        nb = (n + batch - 1) // batch
+        n_par = net.n_par(in_dim)
+        _req(perm, "perm", (n,), torch.int32, dv)
+        _req(targets, "targets", (n,), f32, dv, optional=True)
+        _req(colstats, "colstats", (3, Ds), f64, dv)
+        for t, key in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(t, key, (n_par,), f32, dv)
+        _req(packed, "packed", (getattr(self, net.packed_floats)(in_dim),), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
+        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
+        shapes = dict(noise=(n, 128), one=(1,), batches=(nb,))
+        for key, shape, dtype, optional in net.fit_tensors:
+            _req(own[key], key, shapes[shape], dtype, dv, optional=optional)
+        f = net.struct(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
+                       beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay), x=x.data_ptr(),
+                       targets=ptr(targets), colstats=colstats.data_ptr(), param=param.data_ptr(),
+                       exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), packed=packed.data_ptr(),
+                       ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(), bce_out=ptr(bce_out),
+                       **{key: float(own[key]) for key in net.fit_scalars},
+                       **{key: ptr(own[key]) for key, _, _, _ in net.fit_tensors})
+        self.ctx.call("oly_" + name, C.byref(f), *(() if pair is None else (C.byref(pair),)), ptr(perm), n, batch, self._s())
+        return loss_out
+
+    # -------------------------------------------------------------- K15 (VAIL discriminator fit), K12 / K15 on a pair
+    def _disc_packed_floats(self, D):
+        cache = self.__dict__.setdefault("_disc_sizes", {})
+        if D not in cache:
+            cache[D] = int(lib().oly_disc_packed_floats(D, 256, 128, 128))
+        return cache[D]
+
     def disc_fit_ws(self, batch, in_dim):
         """A workspace for disc_fit_epoch with minibatches of `batch` rows."""
-        from ._ffi import lib
-        n = int(lib().oly_disc_fit_ws_floats(int(batch), int(in_dim)))
-        if n < 0:
-            raise OlyError(f"disc_fit: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
-        return self._new((n,), torch.float32)
+        return self._new((self._disc_fit_ws_floats(_VAIL, "disc_fit", batch, in_dim),), torch.float32)
+
+    def disc_fit_pair_ws(self, batch, ds, d2, standardise):
+        """A workspace for disc_fit_epoch_pair with minibatches of `batch` rows."""
+        return self._new((self._disc_fit_ws_floats(_VAIL, "disc_fit_pair", batch, ds, d2, standardise),), torch.float32)
 
     def disc_fit_epoch(self, x, n_plcy, eps, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed, beta, ws, step,
                        lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0, info_constraint=0.1, lr_beta=1e-5,
@@ -732,121 +911,41 @@ class Engine:
         then kept current), beta [1] f32 VDBLoss's beta (read and written), targets [n] f32 or None (0 / 1); step =
         Adam steps taken before.  Returns loss_out [n_batches] f64 (bce_out, kl_out f64 and beta_out f32 likewise
         when given)."""
-        from ._ffi import lib
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [n,in] tensor")
-        n, in_dim = (int(v) for v in x.shape)
-        batch = int(batch)
-        nws = int(lib().oly_disc_fit_ws_floats(batch, in_dim))
-        if nws < 0:
-            raise OlyError(f"disc_fit_epoch: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
-        if not 0 <= int(n_plcy) <= n:
-            raise OlyError(f"disc_fit_epoch: n_plcy={n_plcy} outside [0, {n}]")
-        nb = (n + batch - 1) // batch
-        n_par = 256 * in_dim + 256 + 128 * 256 + 128 + 2 * (128 * 128 + 128) + 128 + 1
-        _req(x, "x", (n, in_dim), f32, dv)
-        _req(eps, "eps", (n, 128), f32, dv)
-        _req(perm, "perm", (n,), torch.int32, dv)
-        _req(targets, "targets", (n,), f32, dv, optional=True)
-        _req(colstats, "colstats", (3, in_dim), f64, dv)
-        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-            _req(t, name, (n_par,), f32, dv)
-        _req(packed, "packed", (int(lib().oly_disc_packed_floats(in_dim, 256, 128, 128)),), f32, dv)
-        _req(beta, "beta", (1,), f32, dv)
-        _req(ws, "ws", (nws,), f32, dv)
-        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
-        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
-        _req(kl_out, "kl_out", (nb,), f64, dv, optional=True)
-        _req(beta_out, "beta_out", (nb,), f32, dv, optional=True)
-        f = _abi.DiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
-                         beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
-                         info_constraint=float(info_constraint), lr_beta=float(lr_beta), x=x.data_ptr(),
-                         targets=ptr(targets), eps=eps.data_ptr(), colstats=colstats.data_ptr(), param=param.data_ptr(),
-                         exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), packed=packed.data_ptr(),
-                         beta=beta.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
-                         bce_out=ptr(bce_out), kl_out=ptr(kl_out), beta_out=ptr(beta_out))
-        self.ctx.call("oly_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
-        return loss_out
+        return self._disc_fit_epoch(_VAIL, "disc_fit_epoch", x, None, n_plcy, perm, batch, colstats, param, exp_avg,
+                                    exp_avg_sq, packed, ws, step, lr, beta1, beta2, adam_eps, weight_decay, targets,
+                                    loss_out, bce_out, eps=eps, beta=beta, info_constraint=info_constraint,
+                                    lr_beta=lr_beta, kl_out=kl_out, beta_out=beta_out)
 
-    # ---- K12 / K15 on a paired input: (s, s') with use_next_states, (s, a) with actions (networks.py:258-278)
-    def _disc_packed_floats(self, D):
-        from ._ffi import lib
-        cache = self.__dict__.setdefault("_disc_sizes", {})
-        if D not in cache:
-            cache[D] = int(lib().oly_disc_packed_floats(D, 256, 128, 128))
-        return cache[D]
-
-    def _disc_outputs(self, name, B, want, out):
-        f32, dv = torch.float32, self.device
-        shapes = dict(reward=(B,), logits=(B,), mu=(B, 128), logvar=(B, 128))
-        out = dict(out or {})
-        if not want:
-            raise OlyError(f"{name}: no output requested")
-        for k in want:
-            if k not in shapes:
-                raise OlyError(f"{name}: unknown output {k!r}")
-            out[k] = _req(out.get(k) if out.get(k) is not None else self._new(shapes[k], f32), k, shapes[k], f32, dv)
-        return out, (lambda k: ptr(out[k]) if k in want else None)
+    def disc_fit_epoch_pair(self, x, x2, standardise, n_plcy, eps, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed,
+                            beta, ws, step, lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
+                            info_constraint=0.1, lr_beta=1e-5, targets=None, loss_out=None, bce_out=None, kl_out=None,
+                            beta_out=None):
+        """oly_disc_fit_epoch_pair: disc_fit_epoch on the paired rows x [n,Ds] | x2 [n,D2] (both masked and concatenated,
+        policy rows first); colstats [3,Ds]; param / moments for in = Ds + D2."""
+        return self._disc_fit_epoch(_VAIL, "disc_fit_epoch_pair", x, (x2, None, standardise), n_plcy, perm, batch, colstats,
+                                    param, exp_avg, exp_avg_sq, packed, ws, step, lr, beta1, beta2, adam_eps, weight_decay,
+                                    targets, loss_out, bce_out, eps=eps, beta=beta, info_constraint=info_constraint,
+                                    lr_beta=lr_beta, kl_out=kl_out, beta_out=beta_out)
 
     def disc_forward_pair(self, x, x2, packed, standardise, mask=None, mask2=None, stats_a=None, stats_b=None, eps=None,
                           want=("reward",), out=None):
         """oly_disc_forward_pair: disc_forward on [ standardise(x[:, mask]) | second ], second = standardise(x2[:, mask2])
         with stats_b (standardise: next states) or x2[:, mask2] raw (actions).  stats_a / stats_b [3,Ds] f64 running sums,
         or both None (nothing is standardised)."""
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [B,Dx] tensor")
-        B, Dx = (int(v) for v in x.shape)
-        _req(x, "x", (B, Dx), f32, dv)
-        Ds = Dx if mask is None else int(mask.shape[0])
-        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
-        pair, d2 = self._disc_pair("disc_forward_pair", x2, mask2, standardise, B, Ds)
-        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=True)
-        _req(stats_b, "stats_b", (3, Ds), f64, dv, optional=True)
-        if standardise and (stats_a is None) != (stats_b is None):
-            raise OlyError("disc_forward_pair: give stats_a and stats_b together")
-        _req(packed, "packed", (self._disc_packed_floats(Ds + d2),), f32, dv)
-        _req(eps, "eps", (B, 128), f32, dv, optional=True)
-        out, g = self._disc_outputs("disc_forward_pair", B, want, out)
-        self.ctx.call("oly_disc_forward_pair", C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(stats_a),
-                      ptr(stats_b), ptr(packed), ptr(eps), g("reward"), g("logits"), g("mu"), g("logvar"), self._s())
-        return out
+        return self._disc_forward_on(_VAIL, "disc_forward_pair", x, packed, mask, (stats_a, stats_b),
+                                     (x2, mask2, standardise), eps, want, out)
 
     def disc_reward_step_pair(self, x, x2, packed, colstats, stats_a, accumulate, standardise, mask=None, mask2=None,
                               eps=None, want=("reward",), out=None, weights=None):
         """oly_disc_reward_step_pair: the Standardizer's update with x's masked rows (colstats [3,Ds]; that result kept in
         stats_a [3,Ds]), for next states its second update with x2's masked rows, then the paired forward on both, one C
         call without a host synchronisation.  accumulate=None: validate now and return `launch(accumulate)`."""
-        from ._ffi import lib
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [B,Dx] tensor")
-        B, Dx = (int(v) for v in x.shape)
-        _req(x, "x", (B, Dx), f32, dv)
-        Ds = Dx if mask is None else int(mask.shape[0])
-        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
-        pair, d2 = self._disc_pair("disc_reward_step_pair", x2, mask2, standardise, B, Ds)
-        _req(colstats, "colstats", (3, Ds), f64, dv)
-        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=not standardise)
-        D = Ds + d2
-        _req(packed, "packed", (self._disc_packed_floats(D),), f32, dv)
-        _req(eps, "eps", (B, 128), f32, dv, optional=True)
-        wp = None
-        if weights is not None:
-            shapes_w = ((256, D), (256,), (128, 256), (128,), (128, 128), (128,), (128, 128), (128,), (1, 128), (1,))
-            if len(weights) != 10:
-                raise OlyError("disc_reward_step_pair: weights = the ten tensors of disc_pack")
-            for i, (t, sh) in enumerate(zip(weights, shapes_w)):
-                _req(t, f"weights[{i}]", sh, f32, dv)
-            wp = (C.c_void_p * 10)(*[t.data_ptr() for t in weights])
-        out, g = self._disc_outputs("disc_reward_step_pair", B, want, out)
-        head = (C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(colstats), ptr(stats_a))
-        tail = (wp, ptr(packed), ptr(eps), g("reward"), g("logits"), g("mu"), g("logvar"))
+        out, head, tail = self._disc_reward_step_args(_VAIL, "disc_reward_step_pair", x, packed, colstats, stats_a, mask,
+                                                      (x2, mask2, standardise), eps, want, out, weights)
         if accumulate is None:
             from ._ffi import check
             fn, h = lib().oly_disc_reward_step_pair, self.ctx.handle
-            keep = (x, x2, mask, mask2, colstats, stats_a, packed, eps, weights, pair, out)
+            keep = (x, x2, mask, mask2, colstats, stats_a, packed, eps, weights, out)
 
             def launch(acc):
                 rc = fn(h, *head, 1 if acc else 0, *tail, self._s())
@@ -856,59 +955,6 @@ class Engine:
             return launch
         self.ctx.call("oly_disc_reward_step_pair", *head, int(bool(accumulate)), *tail, self._s())
         return out
-
-    def disc_fit_pair_ws(self, batch, ds, d2, standardise):
-        """A workspace for disc_fit_epoch_pair with minibatches of `batch` rows."""
-        from ._ffi import lib
-        n = int(lib().oly_disc_fit_pair_ws_floats(int(batch), int(ds), int(d2), int(bool(standardise))))
-        if n < 0:
-            raise OlyError(f"disc_fit_pair: unsupported batch={batch}, {ds} + {d2} columns (0 < batch <= 4096, 0 < D2, "
-                           "Ds + D2 <= 64, next states as wide as the states)")
-        return self._new((n,), torch.float32)
-
-    def disc_fit_epoch_pair(self, x, x2, standardise, n_plcy, eps, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed,
-                            beta, ws, step, lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
-                            info_constraint=0.1, lr_beta=1e-5, targets=None, loss_out=None, bce_out=None, kl_out=None,
-                            beta_out=None):
-        """oly_disc_fit_epoch_pair: disc_fit_epoch on the paired rows x [n,Ds] | x2 [n,D2] (both masked and concatenated,
-        policy rows first); colstats [3,Ds]; param / moments for in = Ds + D2."""
-        from ._ffi import lib
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [n,Ds] tensor")
-        n, Ds = (int(v) for v in x.shape)
-        _req(x, "x", (n, Ds), f32, dv)
-        pair, d2 = self._disc_pair("disc_fit_epoch_pair", x2, None, standardise, n, Ds)
-        batch, in_dim = int(batch), Ds + d2
-        nws = int(lib().oly_disc_fit_pair_ws_floats(batch, Ds, d2, int(bool(standardise))))
-        if nws < 0:
-            raise OlyError(f"disc_fit_epoch_pair: unsupported batch={batch} (0 < batch <= 4096)")
-        if not 0 <= int(n_plcy) <= n:
-            raise OlyError(f"disc_fit_epoch_pair: n_plcy={n_plcy} outside [0, {n}]")
-        nb = (n + batch - 1) // batch
-        n_par = 256 * in_dim + 256 + 128 * 256 + 128 + 2 * (128 * 128 + 128) + 128 + 1
-        _req(eps, "eps", (n, 128), f32, dv)
-        _req(perm, "perm", (n,), torch.int32, dv)
-        _req(targets, "targets", (n,), f32, dv, optional=True)
-        _req(colstats, "colstats", (3, Ds), f64, dv)
-        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-            _req(t, name, (n_par,), f32, dv)
-        _req(packed, "packed", (self._disc_packed_floats(in_dim),), f32, dv)
-        _req(beta, "beta", (1,), f32, dv)
-        _req(ws, "ws", (nws,), f32, dv)
-        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
-        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
-        _req(kl_out, "kl_out", (nb,), f64, dv, optional=True)
-        _req(beta_out, "beta_out", (nb,), f32, dv, optional=True)
-        f = _abi.DiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
-                         beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
-                         info_constraint=float(info_constraint), lr_beta=float(lr_beta), x=x.data_ptr(),
-                         targets=ptr(targets), eps=eps.data_ptr(), colstats=colstats.data_ptr(), param=param.data_ptr(),
-                         exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), packed=packed.data_ptr(),
-                         beta=beta.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
-                         bce_out=ptr(bce_out), kl_out=ptr(kl_out), beta_out=ptr(beta_out))
-        self.ctx.call("oly_disc_fit_epoch_pair", C.byref(f), C.byref(pair), ptr(perm), n, batch, self._s())
-        return loss_out
 
     # -------------------------------------------------------------- K24 (behavioural cloning: targets, fit)
     def bc_targets(self, actions, central, delta, out=None):
@@ -1191,7 +1237,6 @@ class Engine:
 
     # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
     def _gail_packed_floats(self, D):
-        from ._ffi import lib
         cache = self.__dict__.setdefault("_gail_sizes", {})
         if D not in cache:
             cache[D] = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 1))
@@ -1199,73 +1244,51 @@ class Engine:
             raise OlyError(f"gail discriminator: unsupported input width {D} (0 < in <= 64)")
         return cache[D]
 
-    def _gail_outputs(self, name, B, want, out):
-        f32, dv = torch.float32, self.device
-        if not want:
-            raise OlyError(f"{name}: no output requested")
-        out = dict(out or {})
-        for k in want:
-            if k not in ("reward", "logits"):
-                raise OlyError(f"{name}: unknown output {k!r}")
-            out[k] = _req(out.get(k) if out.get(k) is not None else self._new((B,), f32), k, (B,), f32, dv)
-        return out, (lambda k: ptr(out[k]) if k in want else None)
-
     def gail_disc_forward(self, x, packed, mask=None, mean=None, std=None, colstats=None, want=("reward",), out=None):
         """GAIL's make_discrim_reward for x [B,Dx] f32 in one launch (in -> 512 -> 256 -> 1, tanh, tanh, identity).
         mask [D] int32: the state columns, gathered inside the kernel (the block is never copied to its masked
         width).  want: any of reward / logits.  Standardisation from mean / std [D] f64, or from the running colstats
         [3,D] of col_stats, or none.  packed: the ilmlp_pack stream of the network (out_dim 1)."""
-        f32, dv = torch.float32, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [B,Dx] tensor")
-        B, Dx = (int(v) for v in x.shape)
-        _req(x, "x", (B, Dx), f32, dv)
-        D = Dx if mask is None else int(mask.shape[0])
-        _req(mask, "mask", (D,), torch.int32, dv, optional=True)
-        if (mean is None) != (std is None) or (mean is not None and colstats is not None):
-            raise OlyError("gail_disc_forward: give mean and std together, or colstats, or neither")
-        _req(colstats, "colstats", (3, D), torch.float64, dv, optional=True)
-        _req(mean, "mean", (D,), torch.float64, dv, optional=True)
-        _req(std, "std", (D,), torch.float64, dv, optional=True)
-        _req(packed, "packed", (self._gail_packed_floats(D),), f32, dv)        # the raw pointer carries no length
-        out, g = self._gail_outputs("gail_disc_forward", B, want, out)
-        self.ctx.call("oly_gail_disc_forward", C.c_int64(B), Dx, D, ptr(x), ptr(mask), ptr(mean), ptr(std),
-                      ptr(colstats), ptr(packed), g("reward"), g("logits"), self._s())
+        return self._disc_forward_on(_GAIL, "gail_disc_forward", x, packed, mask, (mean, std, colstats), None, None, want,
+                                     out)
+
+    def gail_disc_forward_pair(self, x, x2, packed, standardise, mask=None, mask2=None, stats_a=None, stats_b=None,
+                               want=("reward",), out=None):
+        """oly_gail_disc_forward_pair: gail_disc_forward on [ standardise(x[:, mask]) | second ], second =
+        standardise(x2[:, mask2]) with stats_b (standardise: next states) or x2[:, mask2] raw (actions).  stats_a /
+        stats_b [3,Ds] f64 running sums, or both None (nothing is standardised)."""
+        return self._disc_forward_on(_GAIL, "gail_disc_forward_pair", x, packed, mask, (stats_a, stats_b),
+                                     (x2, mask2, standardise), None, want, out)
+
+    def _gail_reward_step(self, name, x, packed, colstats, stats_a, accumulate, mask, second, want, out, weights):
+        out, head, tail = self._disc_reward_step_args(_GAIL, name, x, packed, colstats, stats_a, mask, second, None, want,
+                                                      out, weights)
+        self.ctx.call("oly_" + name, *head, int(bool(accumulate)), *tail, self._s())
         return out
 
     def gail_reward_step(self, x, packed, colstats, accumulate, mask=None, want=("reward",), out=None, weights=None):
         """oly_gail_reward_step: (re-pack of `weights`, the six parameter tensors in ilmlp_pack's order, when given,) the
         Standardizer's running update with x's masked rows (into colstats [3,D] f64, accumulate: added to the running
         sums) and the forward on the updated statistics, one C call.  x [B,Dx] f32; mask [D] int32 or None."""
-        f32, dv = torch.float32, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [B,Dx] tensor")
-        B, Dx = (int(v) for v in x.shape)
-        _req(x, "x", (B, Dx), f32, dv)
-        D = Dx if mask is None else int(mask.shape[0])
-        _req(mask, "mask", (D,), torch.int32, dv, optional=True)
-        _req(colstats, "colstats", (3, D), torch.float64, dv)
-        _req(packed, "packed", (self._gail_packed_floats(D),), f32, dv)
-        wp = None
-        if weights is not None:
-            shapes_w = ((512, D), (512,), (256, 512), (256,), (1, 256), (1,))
-            if len(weights) != 6:
-                raise OlyError("gail_reward_step: weights = the six tensors of ilmlp_pack")
-            for i, (t, sh) in enumerate(zip(weights, shapes_w)):
-                _req(t, f"weights[{i}]", sh, f32, dv)
-            wp = (C.c_void_p * 6)(*[t.data_ptr() for t in weights])
-        out, g = self._gail_outputs("gail_reward_step", B, want, out)
-        self.ctx.call("oly_gail_reward_step", C.c_int64(B), Dx, D, ptr(x), ptr(mask), ptr(colstats),
-                      int(bool(accumulate)), wp, ptr(packed), g("reward"), g("logits"), self._s())
-        return out
+        return self._gail_reward_step("gail_reward_step", x, packed, colstats, None, accumulate, mask, None, want, out,
+                                      weights)
+
+    def gail_reward_step_pair(self, x, x2, packed, colstats, stats_a, accumulate, standardise, mask=None, mask2=None,
+                              want=("reward",), out=None, weights=None):
+        """oly_gail_reward_step_pair: the Standardizer's update with x's masked rows (colstats [3,Ds]; that result kept in
+        stats_a [3,Ds]), for next states its second update with x2's masked rows, then the paired forward on both, one C
+        call without a host synchronisation."""
+        return self._gail_reward_step("gail_reward_step_pair", x, packed, colstats, stats_a, accumulate, mask,
+                                      (x2, mask2, standardise), want, out, weights)
 
     def gail_disc_fit_ws(self, batch, in_dim):
         """A workspace for gail_disc_fit_epoch with minibatches of `batch` rows."""
-        from ._ffi import lib
-        n = int(lib().oly_gail_disc_fit_ws_floats(int(batch), int(in_dim)))
-        if n < 0:
-            raise OlyError(f"gail_disc_fit: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
-        return self._new((n,), torch.float32)
+        return self._new((self._disc_fit_ws_floats(_GAIL, "gail_disc_fit", batch, in_dim),), torch.float32)
+
+    def gail_disc_fit_pair_ws(self, batch, ds, d2, standardise):
+        """A workspace for gail_disc_fit_epoch_pair with minibatches of `batch` rows."""
+        return self._new((self._disc_fit_ws_floats(_GAIL, "gail_disc_fit_pair", batch, ds, d2, standardise),),
+                         torch.float32)
 
     def gail_disc_fit_epoch(self, x, n_plcy, perm, batch, colstats, param, exp_avg, exp_avg_sq, packed, ws, step, lr,
                             beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0, entcoeff=1e-3, targets=None,
@@ -1275,158 +1298,18 @@ class Engine:
         order (W1 | b1 | W2 | b2 | W3 | b3), packed the ilmlp_pack stream (re-packed from param, then kept current),
         targets [n] f32 or None (0 / 1); step = Adam steps taken before.  Returns loss_out [n_batches] f64 (bce_out,
         ent_out likewise when given)."""
-        from ._ffi import lib
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [n,in] tensor")
-        n, in_dim = (int(v) for v in x.shape)
-        batch = int(batch)
-        nws = int(lib().oly_gail_disc_fit_ws_floats(batch, in_dim))
-        if nws < 0:
-            raise OlyError(f"gail_disc_fit_epoch: unsupported batch={batch} in={in_dim} (0 < batch <= 4096, in <= 64)")
-        if not 0 <= int(n_plcy) <= n:
-            raise OlyError(f"gail_disc_fit_epoch: n_plcy={n_plcy} outside [0, {n}]")
-        nb = (n + batch - 1) // batch
-        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 256 + 1
-        _req(x, "x", (n, in_dim), f32, dv)
-        _req(perm, "perm", (n,), torch.int32, dv)
-        _req(targets, "targets", (n,), f32, dv, optional=True)
-        _req(colstats, "colstats", (3, in_dim), f64, dv)
-        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-            _req(t, name, (n_par,), f32, dv)
-        _req(packed, "packed", (self._gail_packed_floats(in_dim),), f32, dv)
-        _req(ws, "ws", (nws,), f32, dv)
-        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
-        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
-        _req(ent_out, "ent_out", (nb,), f64, dv, optional=True)
-        f = _abi.GailDiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
-                             beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
-                             entcoeff=float(entcoeff), x=x.data_ptr(), targets=ptr(targets), colstats=colstats.data_ptr(),
-                             param=param.data_ptr(), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(),
-                             packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
-                             bce_out=ptr(bce_out), ent_out=ptr(ent_out))
-        self.ctx.call("oly_gail_disc_fit_epoch", C.byref(f), ptr(perm), n, batch, self._s())
-        return loss_out
-
-    # ---- K18 on a paired input: (s, s') with use_next_states, (s, a) with actions (networks.py:216-234)
-    def _disc_pair(self, name, x2, mask2, standardise, rows, Ds):
-        """The oly_disc_pair block of x2 [rows, W2] f32 (mask2 [d2] int32 or None) -> (block, d2).  Refused: an empty
-        second part, Ds + d2 > 64, next states of another width than the states."""
-        f32, dv = torch.float32, self.device
-        if not isinstance(x2, torch.Tensor) or x2.dim() != 2:
-            raise OlyError(f"{name}: x2: expected a [rows,W2] tensor")
-        W2 = int(x2.shape[1])
-        _req(x2, "x2", (rows, W2), f32, dv)
-        d2 = W2 if mask2 is None else int(mask2.shape[0])
-        _req(mask2, "mask2", (d2,), torch.int32, dv, optional=True)
-        if d2 <= 0:
-            raise OlyError(f"{name}: the second part has no column (D2 == 0)")
-        if Ds + d2 > 64:
-            raise OlyError(f"{name}: the paired input is {Ds} + {d2} columns wide, the kernels take at most 64")
-        if standardise and d2 != Ds:
-            raise OlyError(f"{name}: next states have {d2} masked columns, the states {Ds}")
-        return _abi.DiscPair(x2=x2.data_ptr(), mask2=ptr(mask2), stride2=W2, d2=d2, standardise=int(bool(standardise))), d2
-
-    def gail_disc_forward_pair(self, x, x2, packed, standardise, mask=None, mask2=None, stats_a=None, stats_b=None,
-                               want=("reward",), out=None):
-        """oly_gail_disc_forward_pair: gail_disc_forward on [ standardise(x[:, mask]) | second ], second =
-        standardise(x2[:, mask2]) with stats_b (standardise: next states) or x2[:, mask2] raw (actions).  stats_a /
-        stats_b [3,Ds] f64 running sums, or both None (nothing is standardised)."""
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [B,Dx] tensor")
-        B, Dx = (int(v) for v in x.shape)
-        _req(x, "x", (B, Dx), f32, dv)
-        Ds = Dx if mask is None else int(mask.shape[0])
-        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
-        pair, d2 = self._disc_pair("gail_disc_forward_pair", x2, mask2, standardise, B, Ds)
-        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=True)
-        _req(stats_b, "stats_b", (3, Ds), f64, dv, optional=True)
-        if standardise and (stats_a is None) != (stats_b is None):
-            raise OlyError("gail_disc_forward_pair: give stats_a and stats_b together")
-        _req(packed, "packed", (self._gail_packed_floats(Ds + d2),), f32, dv)
-        out, g = self._gail_outputs("gail_disc_forward_pair", B, want, out)
-        self.ctx.call("oly_gail_disc_forward_pair", C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(stats_a),
-                      ptr(stats_b), ptr(packed), g("reward"), g("logits"), self._s())
-        return out
-
-    def gail_reward_step_pair(self, x, x2, packed, colstats, stats_a, accumulate, standardise, mask=None, mask2=None,
-                              want=("reward",), out=None, weights=None):
-        """oly_gail_reward_step_pair: the Standardizer's update with x's masked rows (colstats [3,Ds]; that result kept in
-        stats_a [3,Ds]), for next states its second update with x2's masked rows, then the paired forward on both, one C
-        call without a host synchronisation."""
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [B,Dx] tensor")
-        B, Dx = (int(v) for v in x.shape)
-        _req(x, "x", (B, Dx), f32, dv)
-        Ds = Dx if mask is None else int(mask.shape[0])
-        _req(mask, "mask", (Ds,), torch.int32, dv, optional=True)
-        pair, d2 = self._disc_pair("gail_reward_step_pair", x2, mask2, standardise, B, Ds)
-        _req(colstats, "colstats", (3, Ds), f64, dv)
-        _req(stats_a, "stats_a", (3, Ds), f64, dv, optional=not standardise)
-        D = Ds + d2
-        _req(packed, "packed", (self._gail_packed_floats(D),), f32, dv)
-        wp = None
-        if weights is not None:
-            shapes_w = ((512, D), (512,), (256, 512), (256,), (1, 256), (1,))
-            if len(weights) != 6:
-                raise OlyError("gail_reward_step_pair: weights = the six tensors of ilmlp_pack")
-            for i, (t, sh) in enumerate(zip(weights, shapes_w)):
-                _req(t, f"weights[{i}]", sh, f32, dv)
-            wp = (C.c_void_p * 6)(*[t.data_ptr() for t in weights])
-        out, g = self._gail_outputs("gail_reward_step_pair", B, want, out)
-        self.ctx.call("oly_gail_reward_step_pair", C.c_int64(B), Dx, Ds, ptr(x), ptr(mask), C.byref(pair), ptr(colstats),
-                      ptr(stats_a), int(bool(accumulate)), wp, ptr(packed), g("reward"), g("logits"), self._s())
-        return out
-
-    def gail_disc_fit_pair_ws(self, batch, ds, d2, standardise):
-        """A workspace for gail_disc_fit_epoch_pair with minibatches of `batch` rows."""
-        from ._ffi import lib
-        n = int(lib().oly_gail_disc_fit_pair_ws_floats(int(batch), int(ds), int(d2), int(bool(standardise))))
-        if n < 0:
-            raise OlyError(f"gail_disc_fit_pair: unsupported batch={batch}, {ds} + {d2} columns (0 < batch <= 4096, "
-                           "0 < D2, Ds + D2 <= 64, next states as wide as the states)")
-        return self._new((n,), torch.float32)
+        return self._disc_fit_epoch(_GAIL, "gail_disc_fit_epoch", x, None, n_plcy, perm, batch, colstats, param, exp_avg,
+                                    exp_avg_sq, packed, ws, step, lr, beta1, beta2, adam_eps, weight_decay, targets,
+                                    loss_out, bce_out, entcoeff=entcoeff, ent_out=ent_out)
 
     def gail_disc_fit_epoch_pair(self, x, x2, standardise, n_plcy, perm, batch, colstats, param, exp_avg, exp_avg_sq,
                                  packed, ws, step, lr, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
                                  entcoeff=1e-3, targets=None, loss_out=None, bce_out=None, ent_out=None):
         """oly_gail_disc_fit_epoch_pair: gail_disc_fit_epoch on the paired rows x [n,Ds] | x2 [n,D2] (both masked and
         concatenated, policy rows first); colstats [3,Ds]; param / moments for in = Ds + D2."""
-        from ._ffi import lib
-        f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise OlyError("x: expected a [n,Ds] tensor")
-        n, Ds = (int(v) for v in x.shape)
-        _req(x, "x", (n, Ds), f32, dv)
-        pair, d2 = self._disc_pair("gail_disc_fit_epoch_pair", x2, None, standardise, n, Ds)
-        batch, in_dim = int(batch), Ds + d2
-        nws = int(lib().oly_gail_disc_fit_pair_ws_floats(batch, Ds, d2, int(bool(standardise))))
-        if nws < 0:
-            raise OlyError(f"gail_disc_fit_epoch_pair: unsupported batch={batch} (0 < batch <= 4096)")
-        if not 0 <= int(n_plcy) <= n:
-            raise OlyError(f"gail_disc_fit_epoch_pair: n_plcy={n_plcy} outside [0, {n}]")
-        nb = (n + batch - 1) // batch
-        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 256 + 1
-        _req(perm, "perm", (n,), torch.int32, dv)
-        _req(targets, "targets", (n,), f32, dv, optional=True)
-        _req(colstats, "colstats", (3, Ds), f64, dv)
-        for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-            _req(t, name, (n_par,), f32, dv)
-        _req(packed, "packed", (self._gail_packed_floats(in_dim),), f32, dv)
-        _req(ws, "ws", (nws,), f32, dv)
-        loss_out = _req(loss_out if loss_out is not None else self._new((nb,), f64), "loss_out", (nb,), f64, dv)
-        _req(bce_out, "bce_out", (nb,), f64, dv, optional=True)
-        _req(ent_out, "ent_out", (nb,), f64, dv, optional=True)
-        f = _abi.GailDiscFit(in_dim=in_dim, n_plcy=int(n_plcy), step=int(step), lr=float(lr), beta1=float(beta1),
-                             beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay),
-                             entcoeff=float(entcoeff), x=x.data_ptr(), targets=ptr(targets), colstats=colstats.data_ptr(),
-                             param=param.data_ptr(), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(),
-                             packed=packed.data_ptr(), ws=ws.data_ptr(), ws_floats=nws, loss_out=loss_out.data_ptr(),
-                             bce_out=ptr(bce_out), ent_out=ptr(ent_out))
-        self.ctx.call("oly_gail_disc_fit_epoch_pair", C.byref(f), C.byref(pair), ptr(perm), n, batch, self._s())
-        return loss_out
+        return self._disc_fit_epoch(_GAIL, "gail_disc_fit_epoch_pair", x, (x2, None, standardise), n_plcy, perm, batch,
+                                    colstats, param, exp_avg, exp_avg_sq, packed, ws, step, lr, beta1, beta2, adam_eps,
+                                    weight_decay, targets, loss_out, bce_out, entcoeff=entcoeff, ent_out=ent_out)
 
     # -------------------------------------------------------------- K19 (the discriminator's diagnostics)
     def gail_disc_log_ws(self, n_rows):

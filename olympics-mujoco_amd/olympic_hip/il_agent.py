@@ -150,18 +150,6 @@ class DeviceILCritic:
         self.eng.ilmlp_pack(*self._views(), packed=self.packed)
 
 
-def _moments_state(tr):
-    return dict(n_par=int(tr.exp_avg.numel()), exp_avg=tr.exp_avg.clone(), exp_avg_sq=tr.exp_avg_sq.clone(),
-                step=int(tr.step))
-
-
-def _load_moments(tr, d):
-    _same(type(tr).__name__, "n_par", int(d["n_par"]), int(tr.exp_avg.numel()))
-    tr.exp_avg.copy_(d["exp_avg"])
-    tr.exp_avg_sq.copy_(d["exp_avg_sq"])
-    tr.step = int(d["step"])
-
-
 class VAILAgent:
     """GAIL_TRPO.fit (gail_TRPO.py:105-165) for VAIL_TRPO with the critic on K16:
 
@@ -231,7 +219,7 @@ class VAILAgent:
         self.critic_fit_params = dict(n_epochs=3, batch_size=256) if critic_fit_params is None else dict(critic_fit_params)
         self.post = GAERollout(engine, gamma=gamma, lam=lam)
         self.iter = int(start_iter)
-        if getattr(disc_reward, "pair", None) is not None and not isinstance(disc_trainer, PairedDemonstrations):
+        if getattr(disc_reward, "pair", None) is not None and not isinstance(disc_trainer, DeviceDiscriminatorFit):
             raise OlyError(f"{type(self).__name__}: the reward was built with pair={disc_reward.pair!r}, which only the "
                            "device trainers fit (DeviceDiscriminatorTrainer, DeviceGAILDiscriminatorTrainer), not "
                            f"{type(disc_trainer).__name__}")
@@ -411,9 +399,37 @@ class VAILAgent:
         return log
 
 
-class PairedDemonstrations:
-    """What the two device trainers share when their reward was built with a `pair`: the demonstrations' second array
-    and the draw that selects both parts together."""
+class DeviceDiscriminatorFit:
+    """What the two device trainers share, _fit_discriminator's (gail_TRPO.py:167-220) loop around one epoch call: the
+    workspace, the demonstrations (for a reward built with a `pair`, their second array and the draw that selects both
+    parts together), the flat parameters and Adam's moments, the epochs and the write-back.  A subclass names its
+    Engine methods (FIT, LOG), its log_names, and supplies _check_policy, _begin, _epoch_args, _log_args and _end."""
+
+    def __init__(self, reward, demo, lr, betas, eps, weight_decay, batch_size, n_epochs, use_noisy_targets):
+        from .gail import ExpertDataset
+        self.r, self.eng = reward, reward.eng
+        self.in_dim = int(reward._params()[0].shape[1])
+        self.batch = int(batch_size)
+        self.pair = getattr(reward, "pair", None)
+        self.lr, self.betas, self.eps, self.wd = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
+        dev = self.eng.device
+        self.demo, self.demo2, self.expert = None, None, None
+        if self.pair is not None:
+            self._ws = getattr(self.eng, self.FIT + "_pair_ws")(self.batch, reward.ds, reward.d2, self.pair == "next_state")
+            self._init_pair_demo(demo)
+        else:
+            self._ws = getattr(self.eng, self.FIT + "_ws")(self.batch, self.in_dim)
+            if isinstance(demo, ExpertDataset):
+                self.expert = demo
+            else:
+                self.demo = torch.as_tensor(np.asarray(demo), dtype=torch.float32, device=dev)
+        n_par = sum(int(p.numel()) for p in reward._params())
+        self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros_like(self.param)
+        self.exp_avg_sq = torch.zeros_like(self.param)
+        self.step = 0
+        self._log_ws = None
 
     def _init_pair_demo(self, demo):
         """The demonstrations of a paired fit: an ExpertDataset (next states: its minibatch(idx, want_next=True)) or a
@@ -444,13 +460,20 @@ class PairedDemonstrations:
             raise OlyError(f"{type(self).__name__}: `states` and `{key}` are [rows, columns] with the same rows")
         r._check_pair(self.demo[:1], self.demo2[:1])
 
-    def _pair_demo_rows(self, idx):
-        """(states, second) of the drawn rows, masked: one draw selects both (gail_TRPO.py:178-180, 187-189)."""
+    def _demo_rows(self, n, generator):
+        """The first min(n, rows) rows of a shuffle of the demonstrations, masked; for a pair (states, second): one
+        draw selects both (gail_TRPO.py:178-180, 187-189)."""
+        r = self.r
+        rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
+        idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
         if self.expert is not None:
-            return self.expert.minibatch(idx, want_next=True)
-        d, d2 = self.demo[idx], self.demo2[idx]
-        return (d if self.r.mask is None else d[:, self.r.mask.long()],
-                d2 if self.r.mask2 is None else d2[:, self.r.mask2.long()])
+            return self.expert.minibatch(idx, want_next=True) if self.pair is not None else self.expert.minibatch(idx)
+        d = self.demo[idx]
+        d = d if r.mask is None else d[:, r.mask.long()]
+        if self.pair is None:
+            return d
+        d2 = self.demo2[idx]
+        return d, (d2 if r.mask2 is None else d2[:, r.mask2.long()])
 
     def _pair_policy_rows(self, plcy, x2):
         """The policy's second tensor, checked and masked."""
@@ -463,8 +486,92 @@ class PairedDemonstrations:
             plcy2 = plcy2[:, r.mask2.long()]
         return plcy2.contiguous()
 
+    @torch.no_grad()
+    def _fit(self, plcy_obs, generator, x2, log, eps=None, log_eps=None):
+        """The fit both subclasses document; eps and log_eps reach _epoch_args and _log_args."""
+        r, eng, dev = self.r, self.eng, self.eng.device
+        plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
+        n = int(plcy.shape[0])
+        if n == 0:
+            raise OlyError(f"{type(self).__name__}.fit: no policy rows")
+        self._check_policy(plcy)
+        plcy2 = self._pair_policy_rows(plcy, x2) if self.pair is not None else None
+        if r.mask is not None:
+            plcy = plcy[:, r.mask.long()]
+        plcy = plcy.contiguous()
+        ps = r._params()
+        torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=self.param)
+        self._begin()
+        if r._packed is None:
+            r.packed()
+        st = r.stand
+        if getattr(st, "_fresh", False):     # the running sums start from zero; the fit adds to them in place
+            st.colstats.zero_()
+            st._fresh = False
+        second = {}
+        fit_epoch = getattr(eng, self.FIT + ("_epoch" if self.pair is None else "_epoch_pair"))
+        losses = None
+        logs = torch.zeros((self.n_epochs, _abi.OLY_DISC_LOG_SCALARS), dtype=torch.float64, device=dev) if log else None
+        for e in range(self.n_epochs):
+            demo = self._demo_rows(n, generator)
+            xb = None
+            if self.pair is not None:
+                demo, demo2 = demo
+                xb = torch.cat([plcy2, demo2]).contiguous()
+                second = dict(x2=xb, standardise=self.pair == "next_state")
+            x = torch.cat([plcy, demo]).contiguous()
+            rows = int(x.shape[0])
+            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206: states only
+            targets = None
+            if self.noisy:                                          # :209-211: demo targets drawn first
+                demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
+                plcy_t = torch.empty(n, device=dev).uniform_(0.01, 0.10, generator=generator)
+                targets = torch.cat([plcy_t, demo_t[:rows - n]]).contiguous()
+            perm = torch.randperm(rows, generator=generator, device=dev).to(torch.int32)
+            own = self._epoch_args(e, rows, generator, eps)
+            nb = (rows + self.batch - 1) // self.batch
+            if losses is None:
+                losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
+            fit_epoch(x=x, n_plcy=n, perm=perm, batch=self.batch, colstats=st.colstats, param=self.param,
+                      exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, packed=r._packed, ws=self._ws, step=self.step,
+                      lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps, weight_decay=self.wd,
+                      targets=targets, loss_out=losses[e], **second, **own)
+            self.step += nb
+            if log:                                                 # _discriminator_logging, :220
+                own = self._log_args(e, rows, generator, log_eps)
+                if self._log_ws is None or self._log_ws[0] < rows:
+                    self._log_ws = (rows, getattr(eng, self.LOG + "_ws")(rows))
+                getattr(eng, self.LOG)(x=x, n_plcy=n, colstats=st.colstats, packed=r._packed, ws=self._log_ws[1], x2=xb,
+                                       standardise=self.pair == "next_state", targets=targets, out=logs[e], **own)
+        o = 0
+        for p in ps:                                                # in place: captured pointers stay valid
+            k = int(p.numel())
+            p.data.copy_(self.param[o:o + k].view_as(p))
+            o += k
+        r.invalidate()
+        self._end()
+        return (losses, logs) if log else losses
 
-class DeviceDiscriminatorTrainer(PairedDemonstrations):
+    def _begin(self):
+        """Before the first epoch of a fit."""
+
+    def _end(self):
+        """After the write-back of a fit."""
+
+    # ---- checkpoint (il_checkpoint): `param` is scratch, refilled at the start of every fit
+    def state_dict(self):
+        return dict(n_par=int(self.exp_avg.numel()), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(),
+                    step=int(self.step))
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        _same(type(self).__name__, "n_par", int(d["n_par"]), int(self.exp_avg.numel()))
+        self.exp_avg.copy_(d["exp_avg"])
+        self.exp_avg_sq.copy_(d["exp_avg_sq"])
+        self.step = int(d["step"])
+
+
+class DeviceDiscriminatorTrainer(DeviceDiscriminatorFit):
     """_fit_discriminator (gail_TRPO.py:167-220) for VAIL on K15: states only, or the paired input of a reward built
     with pair="next_state" / "action" (then fit takes the policy's second tensor, the demonstrations carry the second
     array, one draw selects both, and the explicit update of :206 still takes the states only).  Per epoch:
@@ -491,9 +598,11 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
     captured stay valid); the reward's packed stream is left current.  The optimiser's moments and step count
     persist across fits."""
 
+    FIT, LOG, log_names = "disc_fit", "disc_log", DISC_LOG_NAMES["vail"]
+
     def __init__(self, reward, demo, loss, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, batch_size=2048,
                  n_epochs=1, use_noisy_targets=False):
-        from .gail import ExpertDataset, VariationalDiscriminator, VDBLoss
+        from .gail import VariationalDiscriminator, VDBLoss
         if not isinstance(loss, VDBLoss):
             raise OlyError("DeviceDiscriminatorTrainer: loss must be a VDBLoss (the VAIL discriminator)")
         if loss._use_bernoulli_ent:
@@ -502,44 +611,41 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
         if not isinstance(reward.net, VariationalDiscriminator) or not reward.fused:
             raise OlyError("DeviceDiscriminatorTrainer: supported network is VariationalDiscriminator "
                            "in <= 64 -> 256 -> 128 -> (mu, logvar) 128 -> 1")
-        self.r, self.loss, self.eng = reward, loss, reward.eng
-        self.in_dim = int(reward.net.encoder[0].in_features)
-        self.batch = int(batch_size)
-        self.pair = getattr(reward, "pair", None)
-        self.lr, self.betas, self.eps, self.wd = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-        self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
-        dev = self.eng.device
-        if self.pair is not None:
-            self._mask_max = reward._mask_max
-            self._ws = self.eng.disc_fit_pair_ws(self.batch, reward.ds, reward.d2, self.pair == "next_state")
-            self.demo, self.demo2, self.expert = None, None, None
-            self._init_pair_demo(demo)
+        self.loss = loss
+        super().__init__(reward, demo, lr, betas, eps, weight_decay, batch_size, n_epochs, use_noisy_targets)
+        self._mask_max = None if reward.mask is None else int(reward.mask.max())
+        self.beta = torch.empty(1, dtype=torch.float32, device=self.eng.device)
+
+    def _check_policy(self, plcy):
+        r, cols = self.r, int(plcy.shape[1])
+        if self._mask_max is not None and cols <= self._mask_max:
+            raise OlyError(f"DeviceDiscriminatorTrainer.fit: {cols} columns, the state mask reads column {self._mask_max}")
+        masked = cols if r.mask is None else int(r.mask.numel())
+        if masked != (self.in_dim if self.pair is None else r.ds):
+            raise OlyError(f"DeviceDiscriminatorTrainer.fit: {masked} masked columns, the network takes {self.in_dim}")
+
+    def _begin(self):
+        self.beta.fill_(float(self.loss._beta))
+
+    def _epoch_args(self, e, rows, generator, eps):
+        if eps is None:
+            noise = torch.randn((rows, 128), device=self.eng.device, generator=generator)
         else:
-            self._mask_max = None if reward.mask is None else int(reward.mask.max())
-            self._ws = self.eng.disc_fit_ws(self.batch, self.in_dim)
-            self.expert = demo if isinstance(demo, ExpertDataset) else None
-            self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
-                                                                             device=dev)
-        n_par = sum(int(p.numel()) for p in reward._params())
-        self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros_like(self.param)
-        self.exp_avg_sq = torch.zeros_like(self.param)
-        self.beta = torch.empty(1, dtype=torch.float32, device=dev)
-        self.step = 0
-        self._log_ws = None
-        self.log_names = DISC_LOG_NAMES["vail"]
+            noise = eps[e] if eps.dim() == 3 else eps
+        return dict(eps=noise.to(torch.float32).contiguous(), beta=self.beta, info_constraint=self.loss._info_constr,
+                    lr_beta=self.loss._lr_beta)
 
-    def _demo_rows(self, n, generator):
-        rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
-        idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
-        if self.pair is not None:
-            return self._pair_demo_rows(idx)
-        if self.expert is not None:
-            return self.expert.minibatch(idx)
-        d = self.demo[idx]
-        return d if self.r.mask is None else d[:, self.r.mask.long()]
+    def _log_args(self, e, rows, generator, log_eps):
+        if log_eps is None:
+            leps = torch.randn((4 * rows, 128), device=self.eng.device, generator=generator)
+        else:
+            leps = (log_eps[e] if log_eps.dim() == 3 else log_eps).to(torch.float32).contiguous()
+        return dict(eps=leps, beta=self.beta, info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta,
+                    entcoeff=float(getattr(self.loss, "entcoeff", 1e-3)))
 
-    @torch.no_grad()
+    def _end(self):
+        self.loss._beta = float(self.beta)                           # the one host read-back of the call
+
     def fit(self, plcy_obs, generator=None, eps=None, x2=None, log=False, log_eps=None):
         """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations) and, for a paired reward, the
         policy's second tensor x2 [n, obs or act] (next states or actions, full width).  eps: the reparameterisation
@@ -556,97 +662,18 @@ class DeviceDiscriminatorTrainer(PairedDemonstrations):
         matches its inputs).  The copy of the loss the reference logs through takes beta's dual update between its
         three loss evaluations and is then dropped; that is reproduced, and the trainer's beta is not changed.  With
         log=False nothing differs from a trainer without diagnostics: same return value, statistics and bits."""
-        r, eng, dev = self.r, self.eng, self.eng.device
-        plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
-        if self._mask_max is not None and int(plcy.shape[1]) <= self._mask_max:
-            raise OlyError(f"DeviceDiscriminatorTrainer.fit: {plcy.shape[1]} columns, the state mask reads column "
-                           f"{self._mask_max}")
-        plcy2 = self._pair_policy_rows(plcy, x2) if self.pair is not None else None
-        if r.mask is not None:
-            plcy = plcy[:, r.mask.long()]
-        plcy = plcy.contiguous()
-        n = int(plcy.shape[0])
-        if n == 0:
-            raise OlyError("DeviceDiscriminatorTrainer.fit: no policy rows")
-        if int(plcy.shape[1]) != (self.in_dim if self.pair is None else r.ds):
-            raise OlyError(f"DeviceDiscriminatorTrainer.fit: {plcy.shape[1]} masked columns, the network takes {self.in_dim}")
-        ps = r._params()
-        torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=self.param)
-        self.beta.fill_(float(self.loss._beta))
-        if r._packed is None:
-            r.packed()
-        st = r.stand
-        if getattr(st, "_fresh", False):     # the running sums start from zero; the fit adds to them in place
-            st.colstats.zero_()
-            st._fresh = False
-        losses = None
-        logs = torch.zeros((self.n_epochs, _abi.OLY_DISC_LOG_SCALARS), dtype=torch.float64, device=dev) if log else None
-        for e in range(self.n_epochs):
-            demo = self._demo_rows(n, generator)
-            xb = None
-            if self.pair is not None:
-                demo, demo2 = demo
-                xb = torch.cat([plcy2, demo2]).contiguous()
-            x = torch.cat([plcy, demo]).contiguous()
-            rows = int(x.shape[0])
-            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206: states only
-            targets = None
-            if self.noisy:                                          # :209-211: demo targets drawn first
-                demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
-                plcy_t = torch.empty(n, device=dev).uniform_(0.01, 0.10, generator=generator)
-                targets = torch.cat([plcy_t, demo_t[:rows - n]]).contiguous()
-            perm = torch.randperm(rows, generator=generator, device=dev).to(torch.int32)
-            if eps is None:
-                noise = torch.randn((rows, 128), device=dev, generator=generator)
-            else:
-                noise = eps[e] if eps.dim() == 3 else eps
-            nb = (rows + self.batch - 1) // self.batch
-            if losses is None:
-                losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
-            if self.pair is not None:
-                eng.disc_fit_epoch_pair(x, xb, self.pair == "next_state", n, noise.to(torch.float32).contiguous(), perm,
-                                        self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq, r._packed,
-                                        self.beta, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
-                                        adam_eps=self.eps, weight_decay=self.wd, info_constraint=self.loss._info_constr,
-                                        lr_beta=self.loss._lr_beta, targets=targets, loss_out=losses[e])
-            else:
-                eng.disc_fit_epoch(x, n, noise.to(torch.float32).contiguous(), perm, self.batch, st.colstats, self.param,
-                                   self.exp_avg, self.exp_avg_sq, r._packed, self.beta, self._ws, self.step, self.lr,
-                                   beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps, weight_decay=self.wd,
-                                   info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta, targets=targets,
-                                   loss_out=losses[e])
-            self.step += nb
-            if log:                                                 # _discriminator_logging, :220
-                if log_eps is None:
-                    leps = torch.randn((4 * rows, 128), device=dev, generator=generator)
-                else:
-                    leps = (log_eps[e] if log_eps.dim() == 3 else log_eps).to(torch.float32).contiguous()
-                if self._log_ws is None or self._log_ws[0] < rows:
-                    self._log_ws = (rows, eng.disc_log_ws(rows))
-                eng.disc_log(x, n, st.colstats, r._packed, self.beta, self._log_ws[1],
-                             info_constraint=self.loss._info_constr, lr_beta=self.loss._lr_beta,
-                             entcoeff=float(getattr(self.loss, "entcoeff", 1e-3)), eps=leps, x2=xb,
-                             standardise=self.pair == "next_state", targets=targets, out=logs[e])
-        o = 0
-        for p in ps:                                                # in place: captured pointers stay valid
-            k = int(p.numel())
-            p.data.copy_(self.param[o:o + k].view_as(p))
-            o += k
-        r.invalidate()
-        self.loss._beta = float(self.beta)                           # the one host read-back of the call
-        return (losses, logs) if log else losses
+        return self._fit(plcy_obs, generator, x2, log, eps, log_eps)
 
-    # ---- checkpoint (il_checkpoint): `param` and `beta` are scratch, refilled at the start of every fit
+    # ---- checkpoint (il_checkpoint): `beta` is scratch too, refilled from the loss at the start of every fit
     def state_dict(self):
-        return dict(_moments_state(self), beta=float(self.loss._beta))
+        return dict(super().state_dict(), beta=float(self.loss._beta))
 
-    @torch.no_grad()
     def load_state_dict(self, d):
-        _load_moments(self, d)
+        super().load_state_dict(d)
         self.loss._beta = float(d["beta"])
 
 
-class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
+class DeviceGAILDiscriminatorTrainer(DeviceDiscriminatorFit):
     """_fit_discriminator (gail_TRPO.py:167-220) for GAIL on K18: DeviceDiscriminatorTrainer's semantics with GAIL's
     network and loss, states only or the paired input of a reward built with pair="next_state" / "action".  Per epoch:
 
@@ -667,52 +694,29 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
     ones back in place; the reward's packed stream is left current.  The optimiser's moments and step count persist
     across fits."""
 
+    FIT, LOG, log_names = "gail_disc_fit", "gail_disc_log", DISC_LOG_NAMES["gail"]
+
     def __init__(self, reward, demo, entcoeff=1e-3, lr=5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  batch_size=2048, n_epochs=1, use_noisy_targets=False):
-        from .gail import ExpertDataset, GAILDiscriminatorReward
+        from .gail import GAILDiscriminatorReward
         if not isinstance(reward, GAILDiscriminatorReward):
             raise OlyError("DeviceGAILDiscriminatorTrainer: reward must be a GAILDiscriminatorReward "
                            "(in <= 64 -> 512 -> 256 -> 1, tanh)")
-        self.r, self.eng = reward, reward.eng
-        self.in_dim = reward.in_dim
-        self.batch = int(batch_size)
-        self.pair = getattr(reward, "pair", None)
-        if self.pair is not None:
-            self._ws = self.eng.gail_disc_fit_pair_ws(self.batch, reward.ds, reward.d2, self.pair == "next_state")
-            self.demo, self.demo2, self.expert = None, None, None
-            self._init_pair_demo(demo)
-        else:
-            self._ws = self.eng.gail_disc_fit_ws(self.batch, self.in_dim)
-        self.entcoeff, self.lr, self.betas = float(entcoeff), float(lr), (float(betas[0]), float(betas[1]))
-        self.eps, self.wd = float(eps), float(weight_decay)
-        self.n_epochs, self.noisy = int(n_epochs), bool(use_noisy_targets)
-        dev = self.eng.device
+        self.entcoeff = float(entcoeff)
+        super().__init__(reward, demo, lr, betas, eps, weight_decay, batch_size, n_epochs, use_noisy_targets)
+        if self.pair is None and self.demo is not None and (self.demo.dim() != 2 or int(self.demo.shape[1]) <= (
+                reward._mask_max if reward.mask is not None else self.in_dim - 1)):
+            raise OlyError("DeviceGAILDiscriminatorTrainer: the demonstrations are [rows, obs] full observations")
+
+    def _check_policy(self, plcy):
         if self.pair is None:
-            self.expert = demo if isinstance(demo, ExpertDataset) else None
-            self.demo = None if self.expert is not None else torch.as_tensor(np.asarray(demo), dtype=torch.float32,
-                                                                             device=dev)
-            if self.demo is not None and (self.demo.dim() != 2 or int(self.demo.shape[1]) <=
-                                          (reward._mask_max if reward.mask is not None else self.in_dim - 1)):
-                raise OlyError("DeviceGAILDiscriminatorTrainer: the demonstrations are [rows, obs] full observations")
-        n_par = sum(int(p.numel()) for p in reward._params())
-        self.param = torch.empty(n_par, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros_like(self.param)
-        self.exp_avg_sq = torch.zeros_like(self.param)
-        self.step = 0
-        self._log_ws = None
-        self.log_names = DISC_LOG_NAMES["gail"]
+            self.r._check(plcy)
 
-    def _demo_rows(self, n, generator):
-        rows = self.expert.rows if self.expert is not None else int(self.demo.shape[0])
-        idx = torch.randperm(rows, generator=generator, device=self.eng.device)[:min(n, rows)]
-        if self.pair is not None:
-            return self._pair_demo_rows(idx)
-        if self.expert is not None:
-            return self.expert.minibatch(idx)
-        d = self.demo[idx]
-        return d if self.r.mask is None else d[:, self.r.mask.long()]
+    def _epoch_args(self, e, rows, generator, eps):
+        return dict(entcoeff=self.entcoeff)
 
-    @torch.no_grad()
+    _log_args = _epoch_args
+
     def fit(self, plcy_obs, generator=None, x2=None, log=False):
         """n_epochs epochs on the policy rows plcy_obs [n, obs] (full observations) and, for a paired reward, the
         policy's second tensor x2 [n, obs or act] (next states or actions, full width).  Returns the per-minibatch
@@ -725,78 +729,7 @@ class DeviceGAILDiscriminatorTrainer(PairedDemonstrations):
         len // 2, which is the same whenever the reference runs at all (with fewer demonstrations than policy rows its
         target array no longer matches its inputs).  With log=False nothing differs from a trainer without
         diagnostics: same return value, statistics and bits."""
-        r, eng, dev = self.r, self.eng, self.eng.device
-        plcy = plcy_obs.reshape(-1, plcy_obs.shape[-1]).to(torch.float32)
-        n = int(plcy.shape[0])
-        if n == 0:
-            raise OlyError("DeviceGAILDiscriminatorTrainer.fit: no policy rows")
-        plcy2 = None
-        if self.pair is not None:
-            plcy2 = self._pair_policy_rows(plcy, x2)
-        else:
-            r._check(plcy)
-        if r.mask is not None:
-            plcy = plcy[:, r.mask.long()]
-        plcy = plcy.contiguous()
-        ps = r._params()
-        torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps], out=self.param)
-        if r._packed is None:
-            r.packed()
-        st = r.stand
-        if getattr(st, "_fresh", False):     # the running sums start from zero; the fit adds to them in place
-            st.colstats.zero_()
-            st._fresh = False
-        losses = None
-        logs = torch.zeros((self.n_epochs, _abi.OLY_DISC_LOG_SCALARS), dtype=torch.float64, device=dev) if log else None
-        for e in range(self.n_epochs):
-            demo = self._demo_rows(n, generator)
-            xb = None
-            if self.pair is not None:
-                demo, demo2 = demo
-                xb = torch.cat([plcy2, demo2]).contiguous()
-            x = torch.cat([plcy, demo]).contiguous()
-            rows = int(x.shape[0])
-            st.colstats = eng.col_stats(x, st.colstats)            # D_standardizer.update_mean_std(concat), :206: states only
-            targets = None
-            if self.noisy:                                          # :209-211: demo targets drawn first
-                demo_t = torch.empty(n, device=dev).uniform_(0.80, 0.99, generator=generator)
-                plcy_t = torch.empty(n, device=dev).uniform_(0.01, 0.10, generator=generator)
-                targets = torch.cat([plcy_t, demo_t[:rows - n]]).contiguous()
-            perm = torch.randperm(rows, generator=generator, device=dev).to(torch.int32)
-            nb = (rows + self.batch - 1) // self.batch
-            if losses is None:
-                losses = torch.empty((self.n_epochs, nb), dtype=torch.float64, device=dev)
-            if self.pair is not None:
-                eng.gail_disc_fit_epoch_pair(x, xb, self.pair == "next_state", n, perm, self.batch, st.colstats, self.param,
-                                             self.exp_avg, self.exp_avg_sq, r._packed, self._ws, self.step, self.lr,
-                                             beta1=self.betas[0], beta2=self.betas[1], adam_eps=self.eps,
-                                             weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
-                                             loss_out=losses[e])
-            else:
-                eng.gail_disc_fit_epoch(x, n, perm, self.batch, st.colstats, self.param, self.exp_avg, self.exp_avg_sq,
-                                        r._packed, self._ws, self.step, self.lr, beta1=self.betas[0], beta2=self.betas[1],
-                                        adam_eps=self.eps, weight_decay=self.wd, entcoeff=self.entcoeff, targets=targets,
-                                        loss_out=losses[e])
-            self.step += nb
-            if log:                                                 # _discriminator_logging, :220
-                if self._log_ws is None or self._log_ws[0] < rows:
-                    self._log_ws = (rows, eng.gail_disc_log_ws(rows))
-                eng.gail_disc_log(x, n, st.colstats, r._packed, self._log_ws[1], entcoeff=self.entcoeff, x2=xb,
-                                  standardise=self.pair == "next_state", targets=targets, out=logs[e])
-        o = 0
-        for p in ps:                                                # in place: captured pointers stay valid
-            k = int(p.numel())
-            p.data.copy_(self.param[o:o + k].view_as(p))
-            o += k
-        return (losses, logs) if log else losses
-
-    # ---- checkpoint (il_checkpoint): `param` is scratch, refilled at the start of every fit
-    def state_dict(self):
-        return _moments_state(self)
-
-    @torch.no_grad()
-    def load_state_dict(self, d):
-        _load_moments(self, d)
+        return self._fit(plcy_obs, generator, x2, log)
 
 
 class GAILAgent(VAILAgent):
