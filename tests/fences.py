@@ -1,6 +1,6 @@
 """Fenced and poisoned buffers for the GPU tests: what a kernel does to memory it does not own, and which elements of
 its outputs it forgets.  No tests here: tests/test_fences_cpu.py holds the helper itself to its word without a GPU,
-tests/test_gpu_fences.py runs the kernels on it.
+tests/test_gpu_fences.py and tests/test_gpu_il_fences.py run the kernels on it.
 
 Fenced(shape, dtype) is a tensor `t` that is the interior of a uint8 buffer with MARGIN bytes of 0xFF on either side.
 In 0xFF bytes float32 and float64 are NaN, int32 and int64 are -1 and uint8 is 255, so
@@ -21,9 +21,15 @@ oly_ppo_update_grads, 8 in the K24 entries) holds as it does for a tensor of tor
 
 fence_engine(eng) does the same to every tensor the Engine allocates for its caller while the context is open.
 
-New tests use this helper.  The two older ones stay as they are for the tests that have them: `_Guard` in
-tests/test_gpu_parity.py (margins only, the engine's allocations of K1-K9) and `il_shapes.Guarded` (a float sentinel,
-zeroed interior, the imitation-learning kernels)."""
+Bufs is the {name: Fenced} of one case that the GPU tests fill and close with done().
+
+What runs fenced: K10-K14, K23 and K24 in tests/test_gpu_fences.py, K15-K22 and K25 in tests/test_gpu_il_fences.py, K26
+in tests/test_gpu_iq_q.py; tests/il_fence_ledger.py names the test of every entry point, and
+tests/test_il_fence_ledger_cpu.py holds that table to the header without a GPU.
+
+New tests use this helper.  The two older ones stay as they are, and only in the tests that already have them: `_Guard`
+in tests/test_gpu_parity.py (margins only, the engine's allocations of K1-K9) and `il_shapes.Guarded` (a float sentinel,
+zeroed interior, around some outputs of the imitation-learning kernels' own test files)."""
 import contextlib
 
 import numpy as np
@@ -106,6 +112,35 @@ def assert_untouched(bufs, what=""):
     assert_intact(bufs, what)
     hit = {k: f.n - f.unwritten() for k, f in bufs.items() if f is not None and f.unwritten() != f.n}
     assert not hit, f"{what}: elements stored {hit}"
+
+
+class Bufs(dict):
+    """{name: Fenced} of one case."""
+
+    def inp(self, name, a, **kw):
+        """A fenced copy of the array `a` (None stays None); returns the tensor."""
+        if a is None:
+            return None
+        assert name not in self, name
+        self[name] = fenced(a, **kw)
+        return self[name].t
+
+    def out(self, name, shape, dtype):
+        """A fenced, poisoned tensor."""
+        assert name not in self, name
+        self[name] = Fenced(shape, dtype)
+        return self[name].t
+
+    def host(self, name):
+        return self[name].t.cpu().numpy()
+
+    def done(self, what, written=(), finite=()):
+        torch.cuda.synchronize()
+        assert_intact(self, what)
+        assert_written({k: self[k] for k in written}, what)
+        for k in finite:
+            t = self[k].t
+            assert not t.dtype.is_floating_point or not bool(torch.isnan(t).any()), (what, k, "holds a NaN")
 
 
 class EngineFence:

@@ -21,6 +21,7 @@ import a3_reset_draw_restate as R
 import bc_log_restate as blr
 import bc_restate as br
 import fences as fn
+from fences import Bufs
 from helpers import check_persistent_rollout_against_oracle, ppo_update_case
 from olympic_hip import _abi, specs
 from olympic_hip._ffi import OlyError, lib
@@ -45,35 +46,6 @@ def eng():
     yield e
     torch.cuda.synchronize()
     e.ctx.close()
-
-
-class Bufs(dict):
-    """{name: Fenced} of one case."""
-
-    def inp(self, name, a, **kw):
-        """A fenced copy of the array `a` (None stays None); returns the tensor."""
-        if a is None:
-            return None
-        assert name not in self, name
-        self[name] = fn.fenced(a, **kw)
-        return self[name].t
-
-    def out(self, name, shape, dtype):
-        """A fenced, poisoned tensor."""
-        assert name not in self, name
-        self[name] = fn.Fenced(shape, dtype)
-        return self[name].t
-
-    def host(self, name):
-        return self[name].t.cpu().numpy()
-
-    def done(self, what, written=(), finite=()):
-        torch.cuda.synchronize()
-        fn.assert_intact(self, what)
-        fn.assert_written({k: self[k] for k in written}, what)
-        for k in finite:
-            t = self[k].t
-            assert not t.dtype.is_floating_point or not bool(torch.isnan(t).any()), (what, k, "holds a NaN")
 
 
 def test_the_instrument_on_the_device():
