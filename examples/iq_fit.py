@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""IQ-Learn (imitation_lib/imitation/iq_sac.py) or SQIL (imitation_lib/imitation/sqil_sac.py) whole on synthetic
+transitions (olympic_hip.synthetic, as examples/iq_q_fit.py): DeviceIQSAC.fit runs iq_update on the GPU, the critic update
+(the policy passes of K25 and one oly_iq_q_update, K26) and the policy update (one oly_iq_pi_update, K27; with
+--learnable-alpha one oly_iq_alpha_update after it).  The expert's and the policy's transitions are seeded stand-ins; the
+policy that is trained does not collect them.
+
+    python examples/iq_fit.py --algo iq|sqil [--learnable-alpha] [--log] [--updates 200] [--batch 32] [--json FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "olympics-mujoco_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from olympic_hip import _abi  # noqa: E402
+from olympic_hip.bc import DeviceSquashedGaussianPolicy  # noqa: E402
+from olympic_hip.engine import Engine  # noqa: E402
+from olympic_hip.gail import DeviceStandardizer  # noqa: E402
+from olympic_hip.iq import DeviceIQSAC, DeviceSoftQCritic, DeviceSQILSAC  # noqa: E402
+from olympic_hip.synthetic import il_synthetic_transitions  # noqa: E402
+
+
+class PrintingWriter:
+    def add_scalar(self, name, value, it):
+        print(f"  [{it}] {name} = {value:.6g}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", choices=("iq", "sqil"), default="iq")
+    ap.add_argument("--updates", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=32, help="policy rows per update; as many expert rows are added")
+    ap.add_argument("--in-dim", type=int, default=32)
+    ap.add_argument("--act-dim", type=int, default=11)
+    ap.add_argument("--learnable-alpha", action="store_true", help="train the temperature (one 4-byte read-back per update)")
+    ap.add_argument("--log", action="store_true", help="print the logged scalars under the reference's names")
+    ap.add_argument("--json", default=None, metavar="FILE", help="write the run's figures to FILE")
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    eng = Engine(0)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    D, A = args.in_dim, args.act_dim
+    p_lins = [torch.nn.Linear(D, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 2 * A)]
+    with torch.no_grad():
+        p_lins[2].weight.mul_(0.1)
+    policy = DeviceSquashedGaussianPolicy(eng, p_lins, -np.ones(A), np.ones(A), standardizer=DeviceStandardizer(eng, D))
+    c_lins = [torch.nn.Linear(D + A, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
+    critic = DeviceSoftQCritic(eng, c_lins, standardizer=DeviceStandardizer(eng, D + A), lr=3e-4, tau=0.005)
+    demo = il_synthetic_transitions(20000, D, A, seed=1)
+    kw = dict(gamma=0.99, batch_size=args.batch, use_target=True, logging_iter=max(1, args.updates // 4),
+              sw=PrintingWriter() if args.log else None, max_replay_size=50000, actor_optimizer=dict(lr=3e-4),
+              warmup_transitions=1024, learnable_alpha=args.learnable_alpha, lr_alpha=3e-4, init_alpha=0.1)
+    agent = (DeviceIQSAC if args.algo == "iq" else DeviceSQILSAC)(eng, policy, critic, demo, **kw)
+    w0 = policy.param.clone()
+    first_pi = last_q = last_pi = None
+    for u in range(args.updates):
+        # what the collection loop would hand over: the transitions of one vec step of 256 environments
+        dataset = {k: torch.as_tensor(v).cuda() for k, v in il_synthetic_transitions(256, D, A, seed=100 + u, drift=0.5).items()}
+        out_q, out_pi = agent.fit(dataset, generator=gen)
+        last_q = out_q if out_q is not None else last_q
+        if out_pi is not None:
+            last_pi = out_pi.clone()
+            first_pi = last_pi if first_pi is None else first_pi
+    if last_pi is None:
+        sys.exit("no policy update ran: --updates too small for the warm-up of 1024 transitions")
+    first_pi, last_pi, last_q = first_pi.cpu().numpy(), last_pi.cpu().numpy(), last_q.cpu().numpy()
+    moved = float((policy.param - w0).abs().max())
+    print(f"{args.algo}: {critic.step} critic and {agent.pi_step} policy updates at batch {2 * args.batch}; Actor/Loss "
+          f"{first_pi[0]:.5f} -> {last_pi[0]:.5f}; mean log_prob {first_pi[2]:.4f} -> {last_pi[2]:.4f}; mean Q(s, pi(s)) "
+          f"{first_pi[3]:.4f} -> {last_pi[3]:.4f}; policy gradient norm {last_pi[1]:.4f}; the policy moved by {moved:.4f}; "
+          f"alpha {agent.alpha:.5f} ({agent.alpha_step} temperature steps)")
+    policy.sync_to_torch()
+    critic.sync_to_torch()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(algo=args.algo, critic_updates=int(critic.step), policy_updates=int(agent.pi_step),
+                           alpha=agent.alpha, first={t: float(v) for t, v in zip(_abi.IQ_PI_TAGS, first_pi)},
+                           last={t: float(v) for t, v in zip(_abi.IQ_PI_TAGS, last_pi)},
+                           critic_last={t: float(v) for t, v in zip(_abi.IQ_Q_TAGS, last_q)}), f)
+
+
+if __name__ == "__main__":
+    main()

@@ -3,7 +3,7 @@
 synthetic transitions (olympic_hip.synthetic): a squashed-Gaussian policy with random weights supplies the actions the
 critic's loss needs, the expert's and the policy's transitions are seeded stand-ins, and DeviceIQLearn.fit_Q runs
 update_Q_function and the soft target update on the GPU: three oly_sg_act calls at most (K25) and one oly_iq_q_update
-(K26) per update.  The policy is not trained: update_policy is the follow-up to the critic update.
+(K26) per update.  The policy is not trained here: examples/iq_fit.py runs the whole agent (DeviceIQSAC, K27).
 
     python examples/iq_q_fit.py --algo iq|sqil [--updates 200] [--batch 32] [--no-target] [--log] [--json FILE]
 """

@@ -1,6 +1,7 @@
 // The phases that the two-launch minibatch fits of the  in -> 512 -> 256 -> out  network share: K18
-// (csrc/k18_gail_disc.hip, GAIL's discriminator, tanh hidden layers), K24 (csrc/k24_bc_fit.hip, behavioural cloning, relu)
-// and K26 (csrc/k26_iq_critic.hip, the soft-Q critic, relu).  Launch A ("rows") takes one 16-row tile per 512-thread
+// (csrc/k18_gail_disc.hip, GAIL's discriminator, tanh hidden layers), K24 (csrc/k24_bc_fit.hip, behavioural cloning, relu),
+// K26 (csrc/k26_iq_critic.hip, the soft-Q critic, relu) and K27 (csrc/k27_iq_policy.hip, the SAC family's policy update,
+// whose launch A is cut in two where the critic's statistics need every row's action).  Launch A ("rows") takes one 16-row tile per 512-thread
 // workgroup through the forward and the data gradients on the f32 matrix cores; launch B ("weights") takes one 16 x 16
 // weight tile per 256-thread workgroup through dW, Adam and the re-pack.  The loss, the output layer, the Standardizer's
 // accounting and the Adam stores are each kernel's own.  As in fit_common.h, the order of every addition is what the tests
@@ -66,7 +67,7 @@ __device__ __forceinline__ float4 get_quad(const float* img, int col, int h4) {
 // G k-groups of the image `in` against the packed section at P + PW (GS groups per tile), the bias at P + PB, Act, the
 // result into the image `out`.  With `keep` the lane's row quad of each column also goes to the workspace array at float
 // `off` ([rows][128 NT] in row quads, this lane's quad `quad`).
-// K26 alone calls it.  K18 and K24 keep their own text of the two layers: with this function their rows kernels need
+// K26 and K27 call it.  K18 and K24 keep their own text of the two layers: with this function their rows kernels need
 // eight registers fewer, the compiler then schedules the whole kernel for one more wave per SIMD (which a 512-thread
 // workgroup with this much LDS never has) and stops issuing dZ1's weight loads ahead: launch A ran 2.3 % (K18) and 3.7 %
 // (K24) longer at 2048 rows.  The lane and wave indices are re-derived from threadIdx: as parameters their signs are

@@ -82,6 +82,7 @@ struct oly_ctx {
   unsigned bcfit_attr_done = 0; // same for the behavioural-cloning fit's row kernels (K24)
   unsigned sgact_attr_done = 0; // same for the squashed-Gaussian act's instantiations (K25)
   unsigned iqq_attr_done = 0;   // same for the soft-Q critic update's row kernels (K26)
+  unsigned iqpi_attr_done = 0;  // same for the SAC-family policy update's row kernels (K27)
 };
 
 #define OLY_FAIL(ctx, code, ...)                                \

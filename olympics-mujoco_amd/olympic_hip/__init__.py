@@ -5,7 +5,7 @@ its absence is an error, not a fallback."""
 from . import _abi, specs  # noqa: F401
 
 __all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy", "DeviceSoftQCritic",
-           "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL"]
+           "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceIQSAC", "DeviceSQILSAC"]
 
 
 def __getattr__(name):
@@ -13,8 +13,8 @@ def __getattr__(name):
     if name in ("DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy"):
         from . import bc
         return getattr(bc, name)
-    # the SAC family's critic side (iq.py, K26)
-    if name in ("DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL"):
+    # the SAC family (iq.py: the critic side K26, the whole agents with the policy side K27)
+    if name in ("DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceIQSAC", "DeviceSQILSAC"):
         from . import iq
         return getattr(iq, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

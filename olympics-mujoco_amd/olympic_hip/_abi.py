@@ -285,6 +285,27 @@ class IQQ(C.Structure):
                 ("target_packed_floats", C.c_int64), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp)]
 
 
+class IQPi(C.Structure):
+    """oly_iq_pi (K27): one policy update of IQ-Learn / SQIL for oly_iq_pi_update."""
+    _fields_ = [("in_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32), ("step", C.c_int32),
+                ("alpha", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("weight_decay", C.c_float),
+                ("x", vp), ("eps", vp), ("central", vp), ("delta", vp), ("colstats", vp), ("param", vp), ("m", vp),
+                ("v", vp), ("packed", vp), ("packed_floats", C.c_int64), ("critic_packed", vp),
+                ("critic_packed_floats", C.c_int64), ("critic_param", vp), ("critic_colstats", vp), ("ws", vp),
+                ("ws_floats", C.c_int64), ("action", vp), ("log_prob", vp), ("out", vp)]
+
+
+class IQAlpha(C.Structure):
+    """oly_iq_alpha (K27): one _update_alpha for oly_iq_alpha_update."""
+    _fields_ = [("n", C.c_int32), ("step", C.c_int32), ("target_entropy", C.c_float), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("pad", C.c_float), ("log_prob", vp),
+                ("state", vp)]
+
+
+# out [4] of oly_iq_pi_update (iq_sac.py:441-443); slots 2 and 3 are the means of log_prob and of Q(x | a_new)
+IQ_PI_TAGS = ("Actor/Loss", "Gradients/Norm2 Gradient Q wrt. Pi-parameters", "mean(log_prob)", "mean(Q)")
+
 IQ_ALGO = {"iq": 0, "sqil": 1}
 IQ_PLCY_LOSS_MODES = {"value": 0, "value_expert": 1, "value_policy": 2, "q_old_policy": 3, "v0": 4}
 SQIL_PLCY_LOSS_MODES = {"plcy": 0, "value": 1, "value_plcy": 2}
@@ -423,6 +444,10 @@ SIGNATURES = {
     "oly_iq_q_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "oly_iq_q_ws_values": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "oly_iq_q_update": (C.c_int, [vp, C.POINTER(IQQ), vp]),
+    "oly_iq_pi_ws": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "oly_iq_pi_ws_values": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "oly_iq_pi_update": (C.c_int, [vp, C.POINTER(IQPi), vp]),
+    "oly_iq_alpha_update": (C.c_int, [vp, C.POINTER(IQAlpha), vp]),
     "oly_trpo_grad": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp]),
     "oly_trpo_fvp": (C.c_int, [vp, C.POINTER(TRPOStep), C.c_int, vp, vp, vp, vp, vp]),
     "oly_trpo_step": (C.c_int, [vp, C.POINTER(TRPOStep), vp]),

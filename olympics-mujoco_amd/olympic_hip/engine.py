@@ -1235,6 +1235,87 @@ class Engine:
         self.ctx.call("oly_iq_q_update", C.byref(f), self._s())
         return out
 
+    # -------------------------------------------------------------- K27 (the policy and temperature update of IQ-Learn / SQIL)
+    def iq_pi_ws(self, batch, in_dim, act_dim):
+        """A workspace for iq_pi_update with batches of `batch` rows."""
+        from ._ffi import lib
+        n = int(lib().oly_iq_pi_ws(int(batch), int(in_dim), int(act_dim)))
+        if n < 0:
+            raise OlyError(f"iq_pi_update: unsupported batch={batch} in={in_dim} act={act_dim} (1 <= batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, act <= {_abi.OLY_BC_MAX_ACT}, in + act <= 64)")
+        return self._new((n,), torch.float32)
+
+    def iq_pi_update(self, x, eps, central, delta, colstats, param, m, v, packed, critic_packed, critic_param,
+                     critic_colstats, ws, step, lr, alpha=1e-3, log_std_min=-20.0, log_std_max=2.0, beta1=0.9, beta2=0.999,
+                     adam_eps=1e-8, weight_decay=0.0, out=None):
+        """oly_iq_pi_update: one update_policy of IQ_SAC / SQIL (iq_sac.py:431-439, 587-590) without its logging passes.
+        x [Bp,in] f32 the policy_training_states, eps [Bp,A] f32 the noise, central / delta [A] f32; colstats [3,in] f64
+        the policy's Standardizer or None (it takes the rows first); param / m / v the policy's flat parameters and Adam
+        moments in torch order (W1 [512,in] | b1 | W2 | b2 | W3 [2A,256] | b3), packed their ilmlp_pack stream, kept
+        current by the call; critic_packed / critic_param the live critic's (read only), critic_colstats [3,in+A] f64 or
+        None (it takes the rows (x | a_new)); step = Adam steps taken before.  Returns dict(action [Bp,A] f32, log_prob
+        [Bp] f32, out [4] f64 (_abi.IQ_PI_TAGS)); `out` may supply the buffers.  No synchronisation."""
+        from ._ffi import lib
+        f32, f64, dv = torch.float32, torch.float64, self.device
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(central, torch.Tensor) or central.dim() != 1:
+            raise OlyError("iq_pi_update: x [Bp,in] and central [A] must be tensors")
+        B, in_dim = (int(t) for t in x.shape)
+        A = int(central.shape[0])
+        nws = int(lib().oly_iq_pi_ws(B, in_dim, A))
+        if nws < 0:
+            raise OlyError(f"iq_pi_update: unsupported batch={B} in={in_dim} act={A} (1 <= batch <= "
+                           f"{_abi.OLY_BC_MAX_BATCH}, act <= {_abi.OLY_BC_MAX_ACT}, in + act <= 64)")
+        if not float(log_std_min) <= float(log_std_max):
+            raise OlyError("iq_pi_update: log_std_min <= log_std_max is required")
+        D = in_dim + A
+        n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 2 * A * 256 + 2 * A
+        n_cpar = 512 * D + 512 + 256 * 512 + 256 + 256 + 1
+        npk = int(lib().oly_ilmlp_packed_floats(in_dim, 512, 256, 2 * A))
+        ncpk = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 1))
+        _req(x, "x", (B, in_dim), f32, dv)
+        _req(eps, "eps", (B, A), f32, dv)
+        _req(central, "central", (A,), f32, dv)
+        _req(delta, "delta", (A,), f32, dv)
+        _req(colstats, "colstats", (3, in_dim), f64, dv, optional=True)
+        _req(critic_colstats, "critic_colstats", (3, D), f64, dv, optional=True)
+        for t, name in ((param, "param"), (m, "m"), (v, "v")):
+            _req(t, name, (n_par,), f32, dv)
+        _req(packed, "packed", (npk,), f32, dv)
+        _req(critic_packed, "critic_packed", (ncpk,), f32, dv)
+        _req(critic_param, "critic_param", (n_cpar,), f32, dv)
+        _req(ws, "ws", (nws,), f32, dv)
+        out = out or {}
+        o = dict(action=self._out(out, "action", (B, A), f32), log_prob=self._out(out, "log_prob", (B,), f32),
+                 out=self._out(out, "out", (4,), f64))
+        f = _abi.IQPi(in_dim=in_dim, act_dim=A, batch=B, step=int(step), alpha=float(alpha),
+                      log_std_min=float(log_std_min), log_std_max=float(log_std_max), lr=float(lr), beta1=float(beta1),
+                      beta2=float(beta2), adam_eps=float(adam_eps), weight_decay=float(weight_decay), x=x.data_ptr(),
+                      eps=eps.data_ptr(), central=central.data_ptr(), delta=delta.data_ptr(), colstats=ptr(colstats),
+                      param=param.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(), packed_floats=npk,
+                      critic_packed=critic_packed.data_ptr(), critic_packed_floats=ncpk,
+                      critic_param=critic_param.data_ptr(), critic_colstats=ptr(critic_colstats), ws=ws.data_ptr(),
+                      ws_floats=nws, action=o["action"].data_ptr(), log_prob=o["log_prob"].data_ptr(),
+                      out=o["out"].data_ptr())
+        self.ctx.call("oly_iq_pi_update", C.byref(f), self._s())
+        return o
+
+    def iq_alpha_update(self, log_prob, state, step, lr, target_entropy, beta1=0.9, beta2=0.999, eps=1e-8):
+        """oly_iq_alpha_update: one _update_alpha (iq_sac.py:592-595) in one launch.  log_prob [n] f32; state [3] f32 the
+        device block (log_alpha, exp_avg, exp_avg_sq), stepped in place by Adam with step + 1.  Returns state.  No
+        synchronisation."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(log_prob, torch.Tensor) or log_prob.dim() != 1 or int(log_prob.shape[0]) < 1:
+            raise OlyError("iq_alpha_update: log_prob [n] with n >= 1 must be a tensor")
+        n = int(log_prob.shape[0])
+        _req(log_prob, "log_prob", (n,), f32, dv)
+        _req(state, "state", (3,), f32, dv)
+        if int(step) < 0:
+            raise OlyError(f"iq_alpha_update: step={step} < 0")
+        f = _abi.IQAlpha(n=n, step=int(step), target_entropy=float(target_entropy), lr=float(lr), beta1=float(beta1),
+                         beta2=float(beta2), eps=float(eps), pad=0.0, log_prob=log_prob.data_ptr(), state=state.data_ptr())
+        self.ctx.call("oly_iq_alpha_update", C.byref(f), self._s())
+        return state
+
     # -------------------------------------------------------------- K18 (GAIL's discriminator: reward, fit)
     def _gail_packed_floats(self, D):
         cache = self.__dict__.setdefault("_gail_sizes", {})

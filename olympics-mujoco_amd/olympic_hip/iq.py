@@ -15,9 +15,18 @@ SQIL (imitation_lib/imitation/sqil_sac.py).
   IQ_SAC.fit (:373-406), iq_update's critic part (:408-419)  -> DeviceIQLearn.fit_Q
   SQIL._lossQ (sqil_sac.py:64-136)                       -> DeviceSQIL
 
-Not built, each refused by the constructors: the policy side (update_policy, which needs dQ/da through the critic and
-the gradient of K25, and _update_alpha: learnable_alpha) - the follow-up to this module; the gradient penalty
-(gradient_penalty_lambda > 0) and plcy_loss_mode "v0".
+  IQ_SAC.update_policy, _actor_loss, _update_alpha (:431-465, 587-595), iq_update (:408-419) and fit (:373-406) whole;
+  SQIL.iq_update (sqil_sac.py:16-62)                     -> DeviceIQSAC / DeviceSQILSAC: update_policy is ONE
+                                                            oly_iq_pi_update call (K27), its logging passes are K25's
+                                                            and K16's calls in the reference's order, _update_alpha is
+                                                            one oly_iq_alpha_update call
+
+DeviceIQLearn and DeviceSQIL are the critic side alone and refuse learnable_alpha (the policy never moves there);
+DeviceIQSAC and DeviceSQILSAC are the whole agents.  Not built, each refused by the constructors: the gradient penalty
+(gradient_penalty_lambda > 0), plcy_loss_mode "v0" and gradient clipping of the actor.
+
+The cost of a learnable temperature: K25, K26 and K27 take alpha by value, so with learnable_alpha the `alpha` property
+reads log_alpha back from its device block, four bytes, once per iteration.  The default path has no read-back.
 
 Stated differences from the reference: the minibatches are drawn from torch's device generator (the replay memory's
 indices with replacement, the demonstrations' as the first entries of a fresh permutation): the same distributions,
@@ -460,4 +469,188 @@ class DeviceSQIL(DeviceIQLearn):
         return self.plcy_loss_mode != "plcy"
 
 
-__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL"]
+class _PolicySide:
+    """What DeviceIQSAC and DeviceSQILSAC add to their critic-side parents: update_policy, _update_alpha, iq_update, fit."""
+
+    def _init_policy_side(self, actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
+                          learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc):
+        who = type(self).__name__
+        opt = dict(actor_optimizer or {})
+        if "clipping" in opt:
+            raise OlyError(f"{who}: actor_optimizer['clipping'] is not built (gradient clipping of the actor)")
+        unknown = set(opt) - {"lr", "betas", "eps", "weight_decay"}
+        if unknown:
+            raise OlyError(f"{who}: actor_optimizer has unknown entries {sorted(unknown)}")
+        if int(delay_pi) < 1 or int(warmup_transitions) < 0:
+            raise OlyError(f"{who}: delay_pi >= 1 and warmup_transitions >= 0 are required")
+        betas = opt.get("betas", (0.9, 0.999))
+        self.pi_lr, self.pi_betas = float(opt.get("lr", 3e-4)), (float(betas[0]), float(betas[1]))
+        self.pi_eps, self.pi_weight_decay = float(opt.get("eps", 1e-8)), float(opt.get("weight_decay", 0.0))
+        self.warmup_transitions, self.delay_pi = int(warmup_transitions), int(delay_pi)
+        self.train_policy_only_on_own_states = bool(train_policy_only_on_own_states)
+        self.learnable_alpha, self.lr_alpha = bool(learnable_alpha), float(lr_alpha)
+        self.target_entropy = -float(self.act_dim) if target_entropy is None else float(target_entropy)
+        self.e_thres, self.e_reduc = float(e_thres), float(e_reduc)
+        dev = self.eng.device
+        self.pi_exp_avg = torch.zeros_like(self.policy.param)
+        self.pi_exp_avg_sq = torch.zeros_like(self.policy.param)
+        self.pi_step = 0
+        # log_alpha, exp_avg, exp_avg_sq of Adam([log_alpha], lr_alpha) (iq_sac.py:328-335)
+        self.alpha_state = torch.tensor([np.float32(np.log(init_alpha)), 0.0, 0.0], dtype=torch.float32, device=dev)
+        self.alpha_step = 0
+        self._alpha_read = True          # log_alpha (the host copy) is current
+        self._pi_ws = {}
+
+    @property
+    def alpha(self):
+        if self.learnable_alpha and not self._alpha_read:      # four bytes, once per iteration that stepped it
+            self.log_alpha = float(self.alpha_state[0])
+            self._alpha_read = True
+        return float(torch.tensor(self.log_alpha, dtype=torch.float32).exp())
+
+    def _pi_workspace(self, B):
+        if B not in self._pi_ws:
+            self._pi_ws[B] = self.eng.iq_pi_ws(B, self.in_dim, self.act_dim)
+        return self._pi_ws[B]
+
+    def get_e_lb(self):
+        """IQ_Learn_Policy.get_e_lb in its linear mode (iq_sac.py:169-171): a host number from policy.iter."""
+        return self.e_thres - getattr(self.policy, "iter", 0) * self.e_reduc
+
+    @torch.no_grad()
+    def update_policy(self, obs, n_policy, eps=None, generator=None):
+        """update_policy (iq_sac.py:431-465) on a batch whose rows [0, n_policy) are the policy's: one oly_iq_pi_update
+        on all rows (train_policy_only_on_own_states: on the policy's); on a logging iteration the reference's three
+        further passes in its order (compute_action_and_log_prob_t on all rows with the stepped weights, get_mu_log_sigma
+        on the policy's rows, then on the expert's: each feeds the policy's Standardizer, the first draws noise); with
+        learnable_alpha _update_alpha last, on a logging iteration with the SECOND pass's log-probabilities as the
+        reference's rebound name gives it.  eps: None (drawn from `generator` pass by pass) or a dict with `pi` [Bp,A] and,
+        on a logging iteration, `log` [B,A].  Returns the [4] f64 device block of _abi.IQ_PI_TAGS."""
+        f32 = torch.float32
+        obs = obs.to(f32).contiguous()
+        B, n_policy = int(obs.shape[0]), int(n_policy)
+        eps = eps or {}
+        logging = self._iter % self.logging_iter == 0
+        c, p = self.critic, self.policy
+        x = obs[:n_policy].contiguous() if self.train_policy_only_on_own_states else obs
+        Bp = int(x.shape[0])
+        noise = p._noise(Bp, eps.get("pi"), generator).contiguous()
+        cs, ccs = p._colstats(), c._colstats(c.stand)
+        o = self.eng.iq_pi_update(x, noise, p.central, p.delta, cs, p.param, self.pi_exp_avg, self.pi_exp_avg_sq, p.packed,
+                                  c.packed, c.param, ccs, self._pi_workspace(Bp), self.pi_step, self.pi_lr,
+                                  alpha=self.alpha, log_std_min=p.log_std_min, log_std_max=p.log_std_max,
+                                  beta1=self.pi_betas[0], beta2=self.pi_betas[1], adam_eps=self.pi_eps,
+                                  weight_decay=self.pi_weight_decay)
+        self.pi_step += 1
+        if cs is not None:
+            p.stand._fresh = False
+        if ccs is not None:
+            c.stand._fresh = False
+        log_prob = o["log_prob"]
+        if logging:
+            _, log_prob = self._policy_pass(obs, eps.get("log"), generator)
+            ls_p = p.get_mu_log_sigma(obs[:n_policy])[1]
+            e_lb = self.get_e_lb()
+            ls_e = p.get_mu_log_sigma(obs[n_policy:])[1]
+            if self.sw is not None:
+                host, it, sw = o["out"].cpu().numpy(), self._iter, self.sw
+                sw.add_scalar(_abi.IQ_PI_TAGS[1], float(host[1]), it)
+                sw.add_scalar(_abi.IQ_PI_TAGS[0], float(host[0]), it)
+                sw.add_scalar("Actor/Entropy Expert States", float(torch.mean(-log_prob[n_policy:])), it)
+                sw.add_scalar("Actor/Entropy Policy States", float(torch.mean(-log_prob[:n_policy])), it)
+                sw.add_scalar("Actor/Entropy from Gaussian Policy States", float(torch.mean(p.entropy_from_logsigma(ls_p))), it)
+                sw.add_scalar("Actor/Entropy Lower Bound", float(e_lb), it)
+                sw.add_scalar("Actor/Entropy from Gaussian Expert States", float(torch.mean(p.entropy_from_logsigma(ls_e))), it)
+        if self.learnable_alpha:
+            self.eng.iq_alpha_update(log_prob.contiguous(), self.alpha_state, self.alpha_step, self.lr_alpha,
+                                     self.target_entropy)
+            self.alpha_step += 1
+            self._alpha_read = False
+        return o["out"]
+
+    @torch.no_grad()
+    def iq_update(self, obs, act, next_obs, absorbing, n_policy, eps=None, generator=None):
+        """iq_update (iq_sac.py:408-419; sqil_sac.py:16-62): update_Q_function every delay_Q iterations, update_policy
+        once the replay memory holds more than warmup_transitions and every delay_pi iterations.  The target update runs
+        inside the critic's call (K26), before the policy update instead of after it: the policy update neither reads
+        nor writes the target, so the order does not show.  eps: None or dict(q=update_Q_function's, pi=update_policy's).
+        Returns (the critic's scalars or None, the policy's or None)."""
+        eps = eps or {}
+        out_q = out_pi = None
+        if self._iter % self.delay_Q == 0:
+            out_q = self.update_Q_function(obs, act, next_obs, absorbing, n_policy, eps=eps.get("q"), generator=generator)
+        if self.replay.size > self.warmup_transitions and self._iter % self.delay_pi == 0:
+            out_pi = self.update_policy(obs, n_policy, eps=eps.get("pi"), generator=generator)
+        return out_q, out_pi
+
+    @torch.no_grad()
+    def fit(self, dataset, generator=None):
+        """IQ_SAC.fit (:373-406): the dataset goes into the replay memory; once that is initialised, n_fits times a
+        policy minibatch from it and as many demonstration rows make one batch for iq_update.  Then _iter and
+        policy.iter advance.  Returns the last iq_update's pair, or None."""
+        self.replay.add(dataset)
+        out = None
+        if self.replay.initialized:
+            for _ in range(self.n_fits):
+                s, a, _r, ns, ab, _l = self.replay.get(self.batch_size, generator)
+                idx = self.draw_demo_idx(int(s.shape[0]), generator)
+                d = self.demo
+                out = self.iq_update(torch.cat([s, d["states"][idx]]), torch.cat([a, d["actions"][idx]]),
+                                     torch.cat([ns, d["next_states"][idx]]), torch.cat([ab, d["absorbing"][idx]]),
+                                     int(s.shape[0]), generator=generator)
+        self._iter += 1
+        self.policy.iter = getattr(self.policy, "iter", 0) + 1
+        return out
+
+    def state_dict(self):
+        d = super().state_dict()
+        d["log_alpha"] = float(self.alpha_state[0]) if self.learnable_alpha else float(self.log_alpha)
+        d.update(pi_exp_avg=self.pi_exp_avg.clone(), pi_exp_avg_sq=self.pi_exp_avg_sq.clone(), pi_step=int(self.pi_step),
+                 alpha_state=self.alpha_state.clone(), alpha_step=int(self.alpha_step))
+        return d
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """In place (every device buffer keeps its pointer)."""
+        super().load_state_dict(d)
+        self.pi_exp_avg.copy_(d["pi_exp_avg"])
+        self.pi_exp_avg_sq.copy_(d["pi_exp_avg_sq"])
+        self.alpha_state.copy_(d["alpha_state"])
+        self.pi_step, self.alpha_step = int(d["pi_step"]), int(d["alpha_step"])
+        self._alpha_read = True
+
+
+class DeviceIQSAC(_PolicySide, DeviceIQLearn):
+    """IQ_SAC whole (iq_sac.py:256-420, 431-465, 587-595): DeviceIQLearn's critic side with the policy and the
+    temperature trained on the device (K27).  actor_optimizer: dict(lr, betas, eps, weight_decay) of
+    torch.optim.Adam (a `clipping` entry is refused); warmup_transitions, delay_pi, train_policy_only_on_own_states,
+    learnable_alpha, lr_alpha and target_entropy (None: -A) as the reference's.  e_thres / e_reduc: the policy's entropy
+    lower bound (linear mode), logged only.  The policy's Adam moments and step count and the [3] device block
+    (log_alpha, exp_avg, exp_avg_sq) live here."""
+
+    KIND = "iq_sac"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
+                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
+                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
+                         learnable_alpha=False, **kw)
+        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
+                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
+
+
+class DeviceSQILSAC(_PolicySide, DeviceSQIL):
+    """SQIL whole (sqil_sac.py): DeviceSQIL's critic side with DeviceIQSAC's policy side."""
+
+    KIND = "sqil_sac"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
+                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
+                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
+                         learnable_alpha=False, **kw)
+        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
+                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
+
+
+__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceIQSAC", "DeviceSQILSAC"]
