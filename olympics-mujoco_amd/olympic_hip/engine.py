@@ -1937,7 +1937,7 @@ class Engine:
     def disc_reparam(self, mu, logvar, eps, z=None):
         for t, nme in ((mu, "mu"), (logvar, "logvar"), (eps, "eps")):
             _req(t, nme, mu.shape, torch.float32, self.device)
-        z = _req(z if z is not None else torch.empty_like(mu), "z", mu.shape, torch.float32, self.device)
+        z = _req(z if z is not None else self._new(tuple(mu.shape), torch.float32), "z", mu.shape, torch.float32, self.device)
         self.ctx.call("oly_disc_reparam", C.c_int64(mu.numel()), ptr(mu), ptr(logvar), ptr(eps), ptr(z), self._s())
         return z
 

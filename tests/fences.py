@@ -1,6 +1,6 @@
 """Fenced and poisoned buffers for the GPU tests: what a kernel does to memory it does not own, and which elements of
 its outputs it forgets.  No tests here: tests/test_fences_cpu.py holds the helper itself to its word without a GPU,
-tests/test_gpu_fences.py and tests/test_gpu_il_fences.py run the kernels on it.
+tests/test_gpu_env_fences.py, tests/test_gpu_fences.py and tests/test_gpu_il_fences.py run the kernels on it.
 
 Fenced(shape, dtype) is a tensor `t` that is the interior of a uint8 buffer with MARGIN bytes of 0xFF on either side.
 In 0xFF bytes float32 and float64 are NaN, int32 and int64 are -1 and uint8 is 255, so
@@ -17,14 +17,18 @@ In 0xFF bytes float32 and float64 are NaN, int32 and int64 are -1 and uint8 is 2
     tests/test_gpu_fences.py) and use unwritten() on flag bytes only where 255 is no flag value.
 
 The interior starts ALIGN-byte aligned, so the alignment the entry points ask of their operands (16 bytes in
-oly_ppo_update_grads, 8 in the K24 entries) holds as it does for a tensor of torch's own.
+oly_ppo_update_grads, 8 in the K24 entries) holds as it does for a tensor of torch's own.  With skew=k (bytes, a
+multiple of the element size, below ALIGN) it starts k bytes after an ALIGN boundary instead, between the same two
+MARGIN-byte margins: a skew of one float32 sends an entry point that picks its vector kernel by the pointer's alignment
+down its scalar path, on fenced operands.
 
 fence_engine(eng) does the same to every tensor the Engine allocates for its caller while the context is open.
 
 Bufs is the {name: Fenced} of one case that the GPU tests fill and close with done().
 
-What runs fenced: K10-K14, K23 and K24 in tests/test_gpu_fences.py, K15-K22 and K25 in tests/test_gpu_il_fences.py, K26
-in tests/test_gpu_iq_q.py; tests/il_fence_ledger.py names the test of every entry point, and
+What runs fenced: K1-K9, the expert-data entries and the two host batchers in tests/test_gpu_env_fences.py, K10-K14,
+K23 and K24 in tests/test_gpu_fences.py, K15-K22 and K25 in tests/test_gpu_il_fences.py, K26 in tests/test_gpu_iq_q.py,
+K27 in tests/test_gpu_iq_pi.py; tests/il_fence_ledger.py names the test of every entry point of the header, and
 tests/test_il_fence_ledger_cpu.py holds that table to the header without a GPU.
 
 New tests use this helper.  The two older ones stay as they are, and only in the tests that already have them: `_Guard`
@@ -41,7 +45,7 @@ POISON = 0xFF
 
 
 class Fenced:
-    def __init__(self, shape, dtype, device="cuda", init=None, gathered=False):
+    def __init__(self, shape, dtype, device="cuda", init=None, gathered=False, skew=0):
         shape = (shape,) if isinstance(shape, int) else tuple(int(s) for s in shape)
         self.shape, self.dtype = shape, dtype
         self.n = int(np.prod(shape, dtype=np.int64))
@@ -50,12 +54,14 @@ class Fenced:
         if gathered:
             pitch = (self.n // shape[0] if shape and shape[0] else 0) * self.item
             assert pitch <= MARGIN, f"a row of {pitch} bytes: a gather through index -1 would pass the {MARGIN}-byte fence"
-        raw = torch.full((self.nbytes + 2 * MARGIN + ALIGN,), POISON, dtype=torch.uint8, device=device)
-        start = MARGIN + (-(raw.data_ptr() + MARGIN)) % ALIGN
+        self.skew = int(skew)
+        assert 0 <= self.skew < ALIGN and self.skew % self.item == 0, f"a skew of {skew} bytes for {self.item}-byte elements"
+        raw = torch.full((self.nbytes + 2 * MARGIN + 2 * ALIGN,), POISON, dtype=torch.uint8, device=device)
+        start = MARGIN + (-(raw.data_ptr() + MARGIN)) % ALIGN + self.skew
         self.buf = raw[start - MARGIN:start + self.nbytes + MARGIN]       # margin | interior | margin
         self.bytes = self.buf[MARGIN:MARGIN + self.nbytes]
         self.t = self.bytes.view(dtype).view(shape)
-        assert self.t.data_ptr() % ALIGN == 0 and self.t.is_contiguous()
+        assert self.t.data_ptr() % ALIGN == self.skew and self.t.is_contiguous()
         if init is not None:
             src = torch.as_tensor(np.ascontiguousarray(init) if isinstance(init, np.ndarray) else init)
             assert src.numel() == self.n, (tuple(src.shape), shape)
@@ -83,12 +89,12 @@ class Fenced:
         return bool(torch.equal(self.buf, snap))
 
 
-def fenced(a, device="cuda", dtype=None, gathered=False):
+def fenced(a, device="cuda", dtype=None, gathered=False, skew=0):
     """A Fenced copy of the array or tensor `a` (None stays None)."""
     if a is None:
         return None
     src = torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a)
-    return Fenced(tuple(src.shape), dtype or src.dtype, device, init=src, gathered=gathered)
+    return Fenced(tuple(src.shape), dtype or src.dtype, device, init=src, gathered=gathered, skew=skew)
 
 
 def broken(bufs):
@@ -125,10 +131,10 @@ class Bufs(dict):
         self[name] = fenced(a, **kw)
         return self[name].t
 
-    def out(self, name, shape, dtype):
+    def out(self, name, shape, dtype, skew=0):
         """A fenced, poisoned tensor."""
         assert name not in self, name
-        self[name] = Fenced(shape, dtype)
+        self[name] = Fenced(shape, dtype, skew=skew)
         return self[name].t
 
     def host(self, name):

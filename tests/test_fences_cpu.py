@@ -96,6 +96,56 @@ def test_snapshot_sees_every_byte():
     assert not f.same_as(s)
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("elems", [1, 3])
+def test_a_skewed_interior_starts_where_it_was_asked_to(dtype, elems):
+    """skew=k: the interior starts k bytes after an ALIGN boundary, between the same two margins of poison."""
+    item = torch.empty(0, dtype=dtype).element_size()
+    skew = elems * item
+    f = fn.Fenced((5, 3), dtype, device="cpu", skew=skew)
+    assert f.t.data_ptr() % fn.ALIGN == skew and f.skew == skew
+    assert f.t.shape == (5, 3) and f.t.dtype == dtype and f.t.is_contiguous()
+    assert f.t.data_ptr() == f.buf.data_ptr() + fn.MARGIN
+    lo, hi = f.margins()
+    assert len(lo) == fn.MARGIN and len(hi) == fn.MARGIN and len(f.buf) == 2 * fn.MARGIN + f.nbytes
+    assert bool((f.buf == fn.POISON).all()) and f.intact() and f.unwritten() == 15
+    if item == 4:
+        assert f.t.data_ptr() % 16 == (4 if elems == 1 else 12)
+    # intact(), unwritten() and same_as() as on an aligned interior
+    f.t.fill_(0)
+    assert f.intact() and f.unwritten() == 0
+    g = fn.Fenced((5, 3), dtype, device="cpu", skew=skew)
+    g.t[1, 2] = 0
+    g.t[4, 2] = 0                                  # the last element
+    assert g.unwritten() == 13 and g.intact()
+    s = g.snapshot()
+    assert g.same_as(s)
+    g.t[0, 0] = 1
+    assert not g.same_as(s)
+    # one byte just before and one byte just after the interior
+    for at in (fn.MARGIN - 1, fn.MARGIN + f.nbytes):
+        h = fn.Fenced((5, 3), dtype, device="cpu", skew=skew)
+        h.t.fill_(0)
+        assert h.intact()
+        h.buf[at] = 0xFE
+        assert not h.intact(), at
+    for where in (-1, 1):
+        h = fn.Fenced((5, 3), dtype, device="cpu", skew=skew)
+        outside(h, where).fill_(0)
+        assert not h.intact(), where
+    # fenced() and Bufs pass it on; the default is no skew
+    a = (np.arange(15).reshape(5, 3) % 7).astype(np.float64)
+    k = fn.fenced(torch.as_tensor(a).to(dtype), device="cpu", skew=skew)
+    assert k.t.data_ptr() % fn.ALIGN == skew and torch.equal(k.t, torch.as_tensor(a).to(dtype)) and k.intact()
+    assert fn.Fenced(3, dtype, device="cpu").skew == 0
+
+
+def test_a_skew_is_whole_elements_below_the_alignment():
+    for dtype, skew in ((torch.float32, 2), (torch.float64, 4), (torch.float32, fn.ALIGN), (torch.float32, -4)):
+        with pytest.raises(AssertionError):
+            fn.Fenced(4, dtype, device="cpu", skew=skew)
+
+
 def test_a_gathered_table_is_held_to_the_row_pitch():
     fn.Fenced((3, 1024), torch.float32, device="cpu", gathered=True)            # 4096 bytes
     with pytest.raises(AssertionError, match="4096"):

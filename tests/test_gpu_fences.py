@@ -297,7 +297,7 @@ K13_OUTPUTS = ("ro.buf_states", "ro.buf_actions", "ro.buf_rewards", "ro.buf_valu
 
 @pytest.mark.parametrize("N,T,max_len,det,normalize", [(16, 5, 3, True, False), (70, 6, 2, False, True)])
 def test_k13_persistent_rollout(eng, oracle, N, T, max_len, det, normalize):
-    """The set-up and the bars of test_persistent_rollout_against_the_oracle_directly
+    """oly_a3_rollout_persistent: the set-up and the bars of test_persistent_rollout_against_the_oracle_directly
     (helpers.check_persistent_rollout_against_oracle), every buffer fenced and the pure outputs poisoned."""
     b = Bufs()
 
