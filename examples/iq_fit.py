@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""IQ-Learn (imitation_lib/imitation/iq_sac.py) or SQIL (imitation_lib/imitation/sqil_sac.py) whole on synthetic
+"""IQ-Learn (imitation_lib/imitation/iq_sac.py), SQIL (imitation_lib/imitation/sqil_sac.py) or LSIQ
+(imitation_lib/imitation/lsiq.py) whole on synthetic
 transitions (olympic_hip.synthetic, as examples/iq_q_fit.py): DeviceIQSAC.fit runs iq_update on the GPU, the critic update
 (the policy passes of K25 and one oly_iq_q_update, K26) and the policy update (one oly_iq_pi_update, K27; with
 --learnable-alpha one oly_iq_alpha_update after it).  The expert's and the policy's transitions are seeded stand-ins; the
 policy that is trained does not collect them.
 
-    python examples/iq_fit.py --algo iq|sqil [--learnable-alpha] [--log] [--updates 200] [--batch 32] [--json FILE]
+    python examples/iq_fit.py --algo iq|sqil|lsiq [--learnable-alpha] [--log] [--updates 200] [--batch 32] [--json FILE]
+    python examples/iq_fit.py --algo lsiq --q-exp-loss MSE|Huber [--lossq-type iq_like|sqil_like]
+        [--loss-mode-exp fix|bootstrap] [--q-min -1] [--q-max 1] [--no-target-clipping] [--plcy-loss-mode MODE]
 """
 import argparse
 import json
@@ -20,7 +23,7 @@ from olympic_hip import _abi  # noqa: E402
 from olympic_hip.bc import DeviceSquashedGaussianPolicy  # noqa: E402
 from olympic_hip.engine import Engine  # noqa: E402
 from olympic_hip.gail import DeviceStandardizer  # noqa: E402
-from olympic_hip.iq import DeviceIQSAC, DeviceSoftQCritic, DeviceSQILSAC  # noqa: E402
+from olympic_hip.iq import DeviceIQSAC, DeviceLSIQSAC, DeviceSoftQCritic, DeviceSQILSAC  # noqa: E402
 from olympic_hip.synthetic import il_synthetic_transitions  # noqa: E402
 
 
@@ -31,7 +34,14 @@ class PrintingWriter:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=("iq", "sqil"), default="iq")
+    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq"), default="iq")
+    ap.add_argument("--lossq-type", choices=("iq_like", "sqil_like"), default="iq_like", help="lsiq: lossQ_type")
+    ap.add_argument("--loss-mode-exp", choices=("fix", "bootstrap"), default="fix", help="lsiq: loss_mode_exp")
+    ap.add_argument("--q-exp-loss", choices=("MSE", "Huber"), default=None, help="lsiq: Q_exp_loss (fix and sqil_like need one)")
+    ap.add_argument("--q-min", type=float, default=-1.0, help="lsiq: Q_min")
+    ap.add_argument("--q-max", type=float, default=1.0, help="lsiq: Q_max")
+    ap.add_argument("--no-target-clipping", action="store_true", help="lsiq: target_clipping=False")
+    ap.add_argument("--plcy-loss-mode", default=None, help="plcy_loss_mode (default: the algorithm's)")
     ap.add_argument("--updates", type=int, default=200)
     ap.add_argument("--batch", type=int, default=32, help="policy rows per update; as many expert rows are added")
     ap.add_argument("--in-dim", type=int, default=32)
@@ -54,7 +64,12 @@ def main():
     kw = dict(gamma=0.99, batch_size=args.batch, use_target=True, logging_iter=max(1, args.updates // 4),
               sw=PrintingWriter() if args.log else None, max_replay_size=50000, actor_optimizer=dict(lr=3e-4),
               warmup_transitions=1024, learnable_alpha=args.learnable_alpha, lr_alpha=3e-4, init_alpha=0.1)
-    agent = (DeviceIQSAC if args.algo == "iq" else DeviceSQILSAC)(eng, policy, critic, demo, **kw)
+    if args.plcy_loss_mode is not None:
+        kw["plcy_loss_mode"] = args.plcy_loss_mode
+    if args.algo == "lsiq":
+        kw.update(lossQ_type=args.lossq_type, loss_mode_exp=args.loss_mode_exp, Q_exp_loss=args.q_exp_loss, Q_min=args.q_min,
+                  Q_max=args.q_max, target_clipping=not args.no_target_clipping)
+    agent = dict(iq=DeviceIQSAC, sqil=DeviceSQILSAC, lsiq=DeviceLSIQSAC)[args.algo](eng, policy, critic, demo, **kw)
     w0 = policy.param.clone()
     first_pi = last_q = last_pi = None
     for u in range(args.updates):

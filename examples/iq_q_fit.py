@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""The critic side of IQ-Learn (imitation_lib/imitation/iq_sac.py) or SQIL (imitation_lib/imitation/sqil_sac.py) on
+"""The critic side of IQ-Learn (imitation_lib/imitation/iq_sac.py), SQIL (imitation_lib/imitation/sqil_sac.py) or LSIQ
+(imitation_lib/imitation/lsiq.py) on
 synthetic transitions (olympic_hip.synthetic): a squashed-Gaussian policy with random weights supplies the actions the
 critic's loss needs, the expert's and the policy's transitions are seeded stand-ins, and DeviceIQLearn.fit_Q runs
 update_Q_function and the soft target update on the GPU: three oly_sg_act calls at most (K25) and one oly_iq_q_update
 (K26) per update.  The policy is not trained here: examples/iq_fit.py runs the whole agent (DeviceIQSAC, K27).
 
-    python examples/iq_q_fit.py --algo iq|sqil [--updates 200] [--batch 32] [--no-target] [--log] [--json FILE]
+    python examples/iq_q_fit.py --algo iq|sqil|lsiq [--updates 200] [--batch 32] [--no-target] [--log] [--json FILE]
+    python examples/iq_q_fit.py --algo lsiq --q-exp-loss MSE|Huber [--lossq-type iq_like|sqil_like]
+        [--loss-mode-exp fix|bootstrap] [--q-min -1] [--q-max 1] [--no-target-clipping] [--plcy-loss-mode MODE]
 """
 import argparse
 import json
@@ -20,7 +23,7 @@ from olympic_hip import _abi  # noqa: E402
 from olympic_hip.bc import DeviceSquashedGaussianPolicy  # noqa: E402
 from olympic_hip.engine import Engine  # noqa: E402
 from olympic_hip.gail import DeviceStandardizer  # noqa: E402
-from olympic_hip.iq import DeviceIQLearn, DeviceSoftQCritic, DeviceSQIL  # noqa: E402
+from olympic_hip.iq import DeviceIQLearn, DeviceLSIQ, DeviceSoftQCritic, DeviceSQIL  # noqa: E402
 from olympic_hip.synthetic import il_synthetic_transitions  # noqa: E402
 
 
@@ -31,7 +34,14 @@ class PrintingWriter:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=("iq", "sqil"), default="iq")
+    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq"), default="iq")
+    ap.add_argument("--lossq-type", choices=("iq_like", "sqil_like"), default="iq_like", help="lsiq: lossQ_type")
+    ap.add_argument("--loss-mode-exp", choices=("fix", "bootstrap"), default="fix", help="lsiq: loss_mode_exp")
+    ap.add_argument("--q-exp-loss", choices=("MSE", "Huber"), default=None, help="lsiq: Q_exp_loss (fix and sqil_like need one)")
+    ap.add_argument("--q-min", type=float, default=-1.0, help="lsiq: Q_min")
+    ap.add_argument("--q-max", type=float, default=1.0, help="lsiq: Q_max")
+    ap.add_argument("--no-target-clipping", action="store_true", help="lsiq: target_clipping=False")
+    ap.add_argument("--plcy-loss-mode", default=None, help="plcy_loss_mode (default: the algorithm's)")
     ap.add_argument("--updates", type=int, default=200)
     ap.add_argument("--batch", type=int, default=32, help="policy rows per update; as many expert rows are added")
     ap.add_argument("--in-dim", type=int, default=32)
@@ -53,7 +63,12 @@ def main():
     demo = il_synthetic_transitions(20000, D, A, seed=1)
     kw = dict(gamma=0.99, batch_size=args.batch, use_target=not args.no_target, logging_iter=max(1, args.updates // 4),
               sw=PrintingWriter() if args.log else None, max_replay_size=50000)
-    agent = (DeviceIQLearn if args.algo == "iq" else DeviceSQIL)(eng, policy, critic, demo, **kw)
+    if args.plcy_loss_mode is not None:
+        kw["plcy_loss_mode"] = args.plcy_loss_mode
+    if args.algo == "lsiq":
+        kw.update(lossQ_type=args.lossq_type, loss_mode_exp=args.loss_mode_exp, Q_exp_loss=args.q_exp_loss, Q_min=args.q_min,
+                  Q_max=args.q_max, target_clipping=not args.no_target_clipping)
+    agent = dict(iq=DeviceIQLearn, sqil=DeviceSQIL, lsiq=DeviceLSIQ)[args.algo](eng, policy, critic, demo, **kw)
     first = last = None
     for u in range(args.updates):
         # what the collection loop would hand over: the transitions of one vec step of 256 environments
@@ -63,7 +78,7 @@ def main():
             first = out.clone()
         last = out
     first, last = first.cpu().numpy(), last.cpu().numpy()
-    name = "IQ-Loss/LossQ" if args.algo == "sqil" else "Loss1 + Loss2 + Chi2"
+    name = "IQ-Loss/LossQ" if args.algo == "sqil" else "Loss1 + Loss2 + Chi2"      # LSIQ's sqil_like: Chi2 is 0
     tot = lambda o: float(o[0]) if args.algo == "sqil" else float(o[0] + o[1] + o[2])
     print(f"{args.algo}: {critic.step} critic updates at batch {2 * args.batch} ({'a target' if not args.no_target else 'no target'}); "
           f"{name} {tot(first):.5f} -> {tot(last):.5f}; Q for expert {first[4]:.4f} -> {last[4]:.4f}, "

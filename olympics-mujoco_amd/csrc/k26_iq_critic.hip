@@ -1,6 +1,7 @@
 // K26: the soft-Q critic update of the SAC-family imitation agents, IQ_SAC.update_Q_function with _lossQ, getV,
 // get_targetV, regularizer_loss, update_Q_parameters and _update_all_targets (imitation_lib/imitation/iq_sac.py:421-429,
-// 467-595, 674-676) and SQIL's loss (imitation_lib/imitation/sqil_sac.py:64-136).  The critic is a
+// 467-595, 674-676), SQIL's loss (imitation_lib/imitation/sqil_sac.py:64-136) and LSIQ's two losses with their clipped
+// target (imitation_lib/imitation/lsiq.py:9-195).  The critic is a
 // FullyConnectedNetwork((obs | act) -> [512, 256] -> 1, relu / relu / identity) whose Standardizer takes the whole
 // concatenated row.  The policy passes (compute_action_and_log_prob_t on next_obs and on obs) are K25's and come in as
 // the blocks a_next / logp_next and a_pi / logp_pi.
@@ -12,8 +13,9 @@
 //                          with the statistics its network's Standardizer holds AT that pass (live: S + X0, then
 //                          + X1 without a target, then + X2; target: T + X1), the forward on the f32 matrix cores in
 //                          the forward kernel's chain order (ilmlp_common.h), so Q has oly_ilmlp_forward's bits.  Then
-//                          per row V, y, the loss terms and the coefficients dL/dQ, dL/dQ', dL/dV (fp64 from the f32
-//                          values, narrowed once), and the backward of every pass that carries a gradient through the
+//                          per row V, y (LSIQ: from the clipped next_v), the loss terms and the coefficients dL/dQ,
+//                          dL/dQ', dL/dV (fp64 from the f32 values, narrowed once; the per-row section has the split), and
+//                          the backward of every pass that carries a gradient through the
 //                          relus from the stored outputs.  Activations and deltas go to the workspace in row quads, one
 //                          slot of BP rows per gradient pass; the tile's loss sums to fixed slots.
 //   B  iq_weights_kernel   the launch B of ilmlp_fit.h, as K24: one 16 x 16 weight tile per workgroup, dW summed over the slots' rows in a
@@ -22,6 +24,9 @@
 //                          products, one add) into target_param and its packed stream; the tile's sum of squared
 //                          gradients to a fixed slot.
 //   F  iq_fold_kernel      one workgroup: the 16 scalars from the per-tile partials, the two Standardizers' sums.
+// LSIQ's sqil_like / value_plcy runs the third pass on the policy's rows alone (QArgs::n_v): the column sums of X2, the
+// count its Standardizer takes and the rows' coefficients cover rows [0, n_policy), and nothing of a_pi / logp_pi past
+// them is read.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits.  The Standardizer's head, the
 // hidden layers, dZ1, the dW chain and the waves' meeting are ilmlp_fit.h's, shared with K18 and K24.
 #include <cstdlib>
@@ -41,7 +46,8 @@ constexpr int NTERM = 12;    // per-row loss terms, by subset (policy rows, expe
 static_assert(MAX_BATCH <= 16 * THREADS, "the fold kernel's loops run over at most 256 tiles");
 
 // terms of a row: Q, Q^2, reward = Q - y, y, V, V - y, w reward^2, Q [absorbing], [absorbing],
-//                 SQIL (Q - (R + y))^2, SQIL (V - (R_min + y))^2, unused
+//                 SQIL (Q - (R + y))^2, SQIL (V - (R_min + y))^2, unused; LSIQ keeps the row's expert loss (term 1) in
+//                 T_SQ and its policy loss (sqil_like's term 2) in T_SV
 enum { T_Q, T_Q2, T_R, T_Y, T_V, T_VY, T_CHI, T_QABS, T_ABS, T_SQ, T_SV };
 
 // workspace (floats), BP = batch rounded up to 16 rows, RP = NSLOT BP; [RP][W] arrays in row quads, element (row, col) at
@@ -75,6 +81,11 @@ __host__ __device__ inline WsL ws_layout(int batch) {
 struct QArgs {
   int in_dim, act_dim, D, B, n_policy;
   int algo, loss_mode, reg_mode, treat_abs, use_target, update_target, has_v;
+  int iq_like;                 // the loss family: IQ's three terms (IQ, LSIQ iq_like) or squared / Huber residuals
+  int exp_mode, exp_loss, clip;   // LSIQ: loss_mode_exp, Q_exp_loss, target_clipping
+  int n_v;                     // rows of the third pass: B, or n_policy for LSIQ's sqil_like / value_plcy
+  float q_min, q_max;          // LSIQ's bounds
+  float inv_rm, g1;            // LSIQ sqil_like: f32(1 / reg_mult) and 1 / (1 - gamma) in float32
   int slot[3];                 // the workspace slot of each pass's gradient rows, -1: the pass has no gradient
   int n_slots;
   const float *obs, *act, *next_obs, *absorbing, *a_next, *logp_next, *a_pi, *logp_pi;
@@ -104,7 +115,8 @@ __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
   const int src = blockIdx.x / NSP, s = blockIdx.x % NSP;
   if (src >= 3 || (src == 2 && !a.has_v) || (!a.colstats && !a.tcolstats)) return;
   const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
-  const int per = (a.B + NSP - 1) / NSP, r0 = s * per, r1 = min(a.B, r0 + per);
+  const int nb = src == 2 ? a.n_v : a.B;     // the rows of this pass
+  const int per = (nb + NSP - 1) / NSP, r0 = s * per, r1 = min(nb, r0 + per);
   double sum = 0.0, ss = 0.0;
   if (k < a.D)
     for (int r = r0 + grp; r < r1; r += 4) {
@@ -123,6 +135,25 @@ __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
 constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16;
 constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (3 * 2 * IN_MAX + 16 * NTERM);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
+
+static_assert(OLY_LSIQ_VALUE == OLY_IQ_VALUE && OLY_LSIQ_VALUE_EXPERT == OLY_IQ_VALUE_EXPERT &&
+                  OLY_LSIQ_VALUE_POLICY == OLY_IQ_VALUE_POLICY && OLY_LSIQ_Q_OLD_POLICY == OLY_IQ_Q_OLD_POLICY &&
+                  OLY_LSIQ_V0 == OLY_IQ_V0,
+              "LSIQ's iq_like modes extend IQ's: the rows and fold kernels read both through OLY_IQ_*");
+
+// One residual d under LSIQ's Q_exp_loss: F.mse_loss / torch.square (d^2) or F.huber_loss with delta 1 (0.5 d^2 below 1,
+// |d| - 0.5 from there; torch's backward passes d inside [-1, 1] and its sign outside).  The value and d(value)/dd.
+__device__ __forceinline__ void point_loss(int kind, float d, double& value, double& grad) {
+  const double x = (double)d;
+  if (kind == OLY_LSIQ_LOSS_HUBER) {
+    const double ax = fabs(x);
+    value = ax < 1.0 ? 0.5 * x * x : ax - 0.5;
+    grad = x < -1.0 ? -1.0 : x > 1.0 ? 1.0 : x;
+  } else {
+    value = x * x;
+    grad = 2.0 * x;
+  }
+}
 
 template <int G1>
 __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
@@ -169,7 +200,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
         pq = have ? a.tcolstats[2 * D + tid] + ss[1] : 0.0;
       } else {
         have = a.colstats != nullptr;
-        if (p < 2 || a.has_v) cnt += (double)B, sum += s[p], sq += ss[p];
+        if (p < 2 || a.has_v) cnt += (double)(p == 2 ? a.n_v : B), sum += s[p], sq += ss[p];
         pc = cnt, ps = sum, pq = sq;
       }
       double mean = 0.0, sd = 1.0;
@@ -196,7 +227,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
     for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
       const int m = e / IN_MAX, k = e & (IN_MAX - 1);
       float v = 0.f;
-      if (sub[m] >= 0 && k < D) {
+      if (sub[m] >= 0 && k < D && (p < 2 || row0 + m < a.n_v)) {   // a row the pass does not take goes through as zeros
         v = input_at(a, p, (size_t)(row0 + m), k);
         // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
         if (standardise) v = (float)(((double)v - mean[k]) / sd[k]);
@@ -241,10 +272,17 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
       const float Q = z[0][tid];
       const float nv = z[1][tid] - a.alpha * a.logp_next[i];          // getV / get_targetV (:571-585)
       const float cy = (1.f - ab) * a.gamma;
-      const float y = cy * nv;                                        // :482
-      const float V = a.has_v ? z[2][tid] - a.alpha * a.logp_pi[i] : 0.f;
+      // LSIQ's target_clipping (lsiq.py:46-49, 125-128): torch.clip keeps a NaN and lets the gradient through where
+      // q_min <= next_v <= q_max, bounds included
+      const bool lsiq = a.algo == OLY_IQ_ALGO_LSIQ, clip = lsiq && a.clip;
+      const float nvc = clip ? (nv < a.q_min ? a.q_min : nv > a.q_max ? a.q_max : nv) : nv;
+      const bool through = !clip || (nv >= a.q_min && nv <= a.q_max);
+      const float y = cy * nvc;                                       // :482
+      const float V = a.has_v && i < (size_t)a.n_v ? z[2][tid] - a.alpha * a.logp_pi[i] : 0.f;
       const float r = Q - y, vy = V - y;
-      double dr = 0.0, dV = 0.0, dy = 0.0;      // dL/d(reward) (= dL/dQ), dL/dV, dL/dy beside -dL/d(reward)
+      // dL/d(reward) (on Q and, negated, on y), dL/dQ beside it (LSIQ's fix losses see Q alone), dL/dV, dL/dy beside
+      // -dL/d(reward)
+      double dr = 0.0, dq = 0.0, dV = 0.0, dy = 0.0;
       t[T_Q] = Q;
       t[T_Q2] = (double)Q * (double)Q;
       t[T_R] = r;
@@ -253,12 +291,22 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
       t[T_VY] = vy;
       t[T_QABS] = ab != 0.f ? (double)Q : 0.0;
       t[T_ABS] = ab != 0.f ? 1.0 : 0.0;
-      if (a.algo == OLY_IQ_ALGO_IQ) {
-        if (e) dr -= 1.0 / n_e;                                       // loss_term1 = -mean(reward[expert])
-        if (a.loss_mode == OLY_IQ_VALUE) dV = 1.0 / n_all;
-        else if (a.loss_mode == OLY_IQ_VALUE_EXPERT) dV = e ? 1.0 / n_e : 0.0;
-        else if (a.loss_mode == OLY_IQ_VALUE_POLICY) dV = e ? 0.0 : 1.0 / n_p;
-        else if (!e) dr += 1.0 / n_p;                                 // q_old_policy: mean(reward[~expert])
+      if (a.iq_like) {
+        if (e) {
+          if (!lsiq || a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP) {
+            dr -= 1.0 / n_e;                                          // loss_term1 = -mean(reward[expert])
+          } else {                                                    // lsiq.py:56-60: Q[expert] against the constant Q_max
+            double g;
+            point_loss(a.exp_loss, Q - a.q_max, t[T_SQ], g);
+            dq = g / n_e;
+          }
+        }
+        const int md = a.loss_mode;          // LSIQ adds value_q_old_policy (both terms) and off (neither), lsiq.py:87-94
+        if (md == OLY_IQ_VALUE || md == OLY_LSIQ_VALUE_Q_OLD_POLICY) dV = 1.0 / n_all;
+        else if (md == OLY_IQ_VALUE_EXPERT) dV = e ? 1.0 / n_e : 0.0;
+        else if (md == OLY_IQ_VALUE_POLICY) dV = e ? 0.0 : 1.0 / n_p;
+        if ((md == OLY_IQ_Q_OLD_POLICY || md == OLY_LSIQ_VALUE_Q_OLD_POLICY) && !e)
+          dr += 1.0 / n_p;                                            // q_old_policy: mean(reward[~expert])
         dy = -dV;
         const double ra = a.treat_abs ? (double)ab : 0.0;
         const double w = (1.0 - ra) * (double)a.reg_mult + ra * (1.0 - (double)a.gamma) * (double)a.reg_mult;
@@ -268,6 +316,26 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
           const double n = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY ? n_all : n_own;
           dr += 2.0 * w * (double)r / n;
           t[T_CHI] = w * (double)r * (double)r;
+        }
+      } else if (lsiq) {           // sqil_like (lsiq.py:130-178): no factor 0.5, no reg_mult multiplier, no chi2 term
+        // r_max = -r_min in float32, the reference's order: (1 - ab) (1 / reg_mult) + (ab (1 / (1 - gamma))) (1 / reg_mult)
+        const float rw = a.treat_abs ? (1.f - ab) * a.inv_rm + (ab * a.g1) * a.inv_rm : a.inv_rm;
+        double g;
+        if (e) {
+          const float d = a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP ? Q - (rw + y) : Q - a.q_max;   // :146-148, :153-155
+          point_loss(a.exp_loss, d, t[T_SQ], g);
+          if (a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP) dr += g / n_e;
+          else dq = g / n_e;
+        }
+        // mode value (:165): r_min[~expert] and then as many plain -1 / reg_mult, which land on the expert rows
+        const float rmin = e ? -a.inv_rm : -rw;
+        if (a.loss_mode == OLY_LSIQ_SQ_VALUE || (a.loss_mode == OLY_LSIQ_SQ_VALUE_PLCY && !e)) {
+          point_loss(a.exp_loss, V - (rmin + y), t[T_SV], g);         // :162-168, 173-176
+          dV = g / (a.loss_mode == OLY_LSIQ_SQ_VALUE ? n_all : n_p);
+          dy = -dV;
+        } else if (a.loss_mode == OLY_LSIQ_SQ_Q_OLD_POLICY && !e) {
+          point_loss(a.exp_loss, Q - (rmin + y), t[T_SV], g);         // :169-171
+          dr += g / n_p;
         }
       } else {
         const double rm = (double)a.reg_mult;
@@ -287,9 +355,10 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
           t[T_SV] = (double)d * (double)d;
         }
       }
-      cQ = (float)dr;
+      cQ = (float)(dr + dq);
       cV = (float)dV;
-      cN = a.use_target ? 0.f : (float)((double)cy * (dy - dr));     // y = cy next_v carries a gradient without a target
+      // y = cy clip(next_v) carries a gradient without a target, where the clip lets it through
+      cN = a.use_target || !through ? 0.f : (float)((double)cy * (dy - dr));
     }
     coef[0][tid] = cQ;
     coef[1][tid] = cN;
@@ -444,23 +513,29 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
     const double n_all = (double)a.B, n_p = (double)a.n_policy, n_e = n_all - n_p;
     double o[16];
     for (int j = 0; j < 16; ++j) o[j] = 0.0;
-    if (a.algo == OLY_IQ_ALGO_IQ) {
-      o[0] = -Se[T_R] / n_e;
+    const bool lsiq = a.algo == OLY_IQ_ALGO_LSIQ;
+    if (a.iq_like) {
+      o[0] = lsiq && a.exp_mode == OLY_LSIQ_EXP_FIX ? Se[T_SQ] / n_e : -Se[T_R] / n_e;
       o[1] = a.loss_mode == OLY_IQ_VALUE ? (Sp[T_VY] + Se[T_VY]) / n_all
              : a.loss_mode == OLY_IQ_VALUE_EXPERT ? Se[T_VY] / n_e
              : a.loss_mode == OLY_IQ_VALUE_POLICY ? Sp[T_VY] / n_p
-                                                  : Sp[T_R] / n_p;
+             : a.loss_mode == OLY_IQ_Q_OLD_POLICY ? Sp[T_R] / n_p
+             : a.loss_mode == OLY_LSIQ_VALUE_Q_OLD_POLICY ? Sp[T_R] / n_p + (Sp[T_VY] + Se[T_VY]) / n_all
+                                                         : 0.0;
       o[2] = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY ? (Sp[T_CHI] + Se[T_CHI]) / n_all
              : a.reg_mode == OLY_IQ_REG_EXP ? Se[T_CHI] / n_e
              : a.reg_mode == OLY_IQ_REG_PLCY ? Sp[T_CHI] / n_p
                                              : 0.0;
+    } else if (lsiq) {   // sqil_like returns (loss_term1, loss_term2, 0.0), lsiq.py:195
+      o[0] = Se[T_SQ] / n_e;
+      o[1] = a.loss_mode == OLY_LSIQ_SQ_VALUE ? (Sp[T_SV] + Se[T_SV]) / n_all : Sp[T_SV] / n_p;
     } else {
       const double second = a.loss_mode == OLY_SQIL_VALUE ? 0.5 * (Sp[T_SV] + Se[T_SV]) / n_all
                             : a.loss_mode == OLY_SQIL_VALUE_PLCY ? 0.5 * Sp[T_SV] / n_p
                                                                  : 0.5 * Sp[T_SQ] / n_p;
       o[0] = (double)a.reg_mult * (0.5 * Se[T_SQ] / n_e + second);
     }
-    o[3] = a.has_v ? (Sp[T_V] + Se[T_V]) / n_all : 0.0;
+    o[3] = a.has_v && (a.iq_like || !lsiq) ? (Sp[T_V] + Se[T_V]) / n_all : 0.0;
     o[4] = Se[T_Q] / n_e;
     o[5] = Se[T_Q2] / n_e;
     o[6] = Sp[T_Q] / n_p;
@@ -482,7 +557,7 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
       double cnt = a.colstats[tid], sum = a.colstats[D + tid], sq = a.colstats[2 * D + tid];
       for (int p = 0; p < 3; ++p) {
         if ((p == 1 && a.use_target) || (p == 2 && !a.has_v)) continue;
-        cnt += Bd;
+        cnt += p == 2 ? (double)a.n_v : Bd;
         sum += d[p * 2 * IN_MAX + tid];
         sq += d[p * 2 * IN_MAX + IN_MAX + tid];
       }
@@ -521,19 +596,41 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
              "%s: supported: 2 <= batch <= %d, in_dim >= 1, 1 <= act_dim <= %d, in_dim + act_dim <= %d, 1 <= n_policy < "
              "batch (got batch %d, in %d, act %d, n_policy %d)",
              name, MAX_BATCH, MAX_ACT, IN_MAX, B, in_dim, A, f->n_policy);
-  const bool iq = f->algo == OLY_IQ_ALGO_IQ, sqil = f->algo == OLY_IQ_ALGO_SQIL;
-  if (!iq && !sqil) OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown algorithm %d", name, f->algo);
-  if (iq && f->plcy_loss_mode == OLY_IQ_V0)
-    OLY_FAIL(ctx, OLY_EINVAL, "%s: plcy_loss_mode v0 is not built", name);
-  if (iq ? (f->plcy_loss_mode < OLY_IQ_VALUE || f->plcy_loss_mode > OLY_IQ_Q_OLD_POLICY)
-         : (f->plcy_loss_mode < OLY_SQIL_PLCY || f->plcy_loss_mode > OLY_SQIL_VALUE_PLCY))
-    OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown plcy_loss_mode %d", name, f->plcy_loss_mode);
+  const bool iq = f->algo == OLY_IQ_ALGO_IQ, sqil = f->algo == OLY_IQ_ALGO_SQIL, lsiq = f->algo == OLY_IQ_ALGO_LSIQ;
+  if (!iq && !sqil && !lsiq) OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown algorithm %d", name, f->algo);
+  const oly_lsiq* ls = lsiq ? f->lsiq : nullptr;      // read for LSIQ alone
+  if (lsiq && !ls) OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL lsiq block with algo OLY_IQ_ALGO_LSIQ", name);
+  const int md = f->plcy_loss_mode;
+  bool iq_like = iq;
+  if (lsiq) {
+    if (ls->lossQ_type != OLY_LSIQ_IQ_LIKE && ls->lossQ_type != OLY_LSIQ_SQIL_LIKE)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown lossQ_type %d", name, ls->lossQ_type);
+    if (ls->loss_mode_exp != OLY_LSIQ_EXP_FIX && ls->loss_mode_exp != OLY_LSIQ_EXP_BOOTSTRAP)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown loss_mode_exp %d", name, ls->loss_mode_exp);
+    if (ls->Q_exp_loss < OLY_LSIQ_LOSS_NONE || ls->Q_exp_loss > OLY_LSIQ_LOSS_HUBER)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown Q_exp_loss %d", name, ls->Q_exp_loss);
+    if (!(ls->Q_min < ls->Q_max)) OLY_FAIL(ctx, OLY_EINVAL, "%s: Q_min %g must lie below Q_max %g", name, ls->Q_min, ls->Q_max);
+    iq_like = ls->lossQ_type == OLY_LSIQ_IQ_LIKE;
+    if (ls->Q_exp_loss == OLY_LSIQ_LOSS_NONE && (!iq_like || ls->loss_mode_exp == OLY_LSIQ_EXP_FIX))
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: loss_mode_exp fix and lossQ_type sqil_like need a Q_exp_loss (MSE or Huber)", name);
+    if (!iq_like && md == OLY_LSIQ_SQ_VALUE && 2 * f->n_policy != B)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: sqil_like with plcy_loss_mode value needs as many policy rows as expert rows (n_policy %d of %d)",
+               name, f->n_policy, B);
+  }
+  if ((iq || (lsiq && iq_like)) && md == OLY_IQ_V0) OLY_FAIL(ctx, OLY_EINVAL, "%s: plcy_loss_mode v0 is not built", name);
+  if (iq     ? (md < OLY_IQ_VALUE || md > OLY_IQ_Q_OLD_POLICY)
+      : sqil ? (md < OLY_SQIL_PLCY || md > OLY_SQIL_VALUE_PLCY)
+      : iq_like ? (md < OLY_LSIQ_VALUE || md > OLY_LSIQ_OFF)
+                : (md < OLY_LSIQ_SQ_VALUE || md > OLY_LSIQ_SQ_Q_OLD_POLICY))
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown plcy_loss_mode %d", name, md);
   if (f->regularizer_mode < OLY_IQ_REG_EXP_AND_PLCY || f->regularizer_mode > OLY_IQ_REG_OFF)
     OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown regularizer_mode %d", name, f->regularizer_mode);
   if (f->gradient_penalty_lambda > 0.f || f->gradient_penalty_lambda != f->gradient_penalty_lambda)
     OLY_FAIL(ctx, OLY_EINVAL, "%s: the gradient penalty is not built (gradient_penalty_lambda must be 0)", name);
   if (!(f->tau >= 0.0 && f->tau <= 1.0)) OLY_FAIL(ctx, OLY_EINVAL, "%s: tau %g outside [0, 1]", name, f->tau);
-  const bool has_v = iq || f->plcy_loss_mode != OLY_SQIL_PLCY;
+  // the pass on (obs | a_pi): always in IQ's family (getV(obs) runs in every mode, lsiq.py:72), in SQIL's but for plcy, in
+  // LSIQ's sqil_like but for q_old_policy
+  const bool has_v = iq_like || (sqil ? md != OLY_SQIL_PLCY : md != OLY_LSIQ_SQ_Q_OLD_POLICY);
   const bool need_target = f->use_target || f->update_target;
   if (!f->obs || !f->act || !f->next_obs || !f->absorbing || !f->a_next || !f->logp_next || !f->param || !f->m || !f->v ||
       !f->packed || !f->ws || !f->out || (has_v && (!f->a_pi || !f->logp_pi)) ||
@@ -563,6 +660,18 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
   a.use_target = f->use_target != 0;
   a.update_target = f->update_target != 0;
   a.has_v = has_v;
+  a.iq_like = iq_like;
+  a.n_v = B;
+  if (lsiq) {
+    a.exp_mode = ls->loss_mode_exp;
+    a.exp_loss = ls->Q_exp_loss;
+    a.clip = ls->target_clipping != 0;
+    a.q_min = ls->Q_min;
+    a.q_max = ls->Q_max;
+    a.inv_rm = (float)(1.0 / (double)f->reg_mult);
+    a.g1 = 1.f / (1.f - f->gamma);
+    if (!iq_like && md == OLY_LSIQ_SQ_VALUE_PLCY) a.n_v = f->n_policy;
+  }
   int ns = 0;
   a.slot[0] = ns++;
   a.slot[1] = a.use_target ? -1 : ns++;

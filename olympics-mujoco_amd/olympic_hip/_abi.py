@@ -270,8 +270,14 @@ class SGAct(C.Structure):
                 ("out_flags", C.c_int32), ("pad", C.c_int32)]
 
 
+class LSIQ(C.Structure):
+    """oly_lsiq (K26): LSIQ's own parameters, the block oly_iq_q.lsiq points to."""
+    _fields_ = [("lossQ_type", C.c_int32), ("loss_mode_exp", C.c_int32), ("Q_exp_loss", C.c_int32),
+                ("target_clipping", C.c_int32), ("Q_min", C.c_float), ("Q_max", C.c_float)]
+
+
 class IQQ(C.Structure):
-    """oly_iq_q (K26): one soft-Q critic update of IQ-Learn / SQIL for oly_iq_q_update."""
+    """oly_iq_q (K26): one soft-Q critic update of IQ-Learn / SQIL / LSIQ for oly_iq_q_update."""
     _fields_ = [("in_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32), ("n_policy", C.c_int32),
                 ("algo", C.c_int32), ("plcy_loss_mode", C.c_int32), ("regularizer_mode", C.c_int32),
                 ("treat_absorbing", C.c_int32), ("use_target", C.c_int32), ("update_target", C.c_int32),
@@ -282,7 +288,8 @@ class IQQ(C.Structure):
                 ("act", vp), ("next_obs", vp), ("absorbing", vp), ("a_next", vp), ("logp_next", vp), ("a_pi", vp),
                 ("logp_pi", vp), ("colstats", vp), ("target_colstats", vp), ("param", vp), ("m", vp), ("v", vp),
                 ("packed", vp), ("target_param", vp), ("target_packed", vp), ("packed_floats", C.c_int64),
-                ("target_packed_floats", C.c_int64), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp)]
+                ("target_packed_floats", C.c_int64), ("ws", vp), ("ws_floats", C.c_int64), ("out", vp),
+                ("lsiq", C.POINTER(LSIQ))]
 
 
 class IQPi(C.Structure):
@@ -306,10 +313,17 @@ class IQAlpha(C.Structure):
 # out [4] of oly_iq_pi_update (iq_sac.py:441-443); slots 2 and 3 are the means of log_prob and of Q(x | a_new)
 IQ_PI_TAGS = ("Actor/Loss", "Gradients/Norm2 Gradient Q wrt. Pi-parameters", "mean(log_prob)", "mean(Q)")
 
-IQ_ALGO = {"iq": 0, "sqil": 1}
+IQ_ALGO = {"iq": 0, "sqil": 1, "lsiq": 2}
 IQ_PLCY_LOSS_MODES = {"value": 0, "value_expert": 1, "value_policy": 2, "q_old_policy": 3, "v0": 4}
 SQIL_PLCY_LOSS_MODES = {"plcy": 0, "value": 1, "value_plcy": 2}
 IQ_REGULARIZER_MODES = {"exp_and_plcy": 0, "exp": 1, "plcy": 2, "off": 3}
+# LSIQ (lsiq.py:11-23): plcy_loss_mode by lossQ_type (OLY_LSIQ_* / OLY_LSIQ_SQ_*), and the enumerants of oly_lsiq
+LSIQ_PLCY_LOSS_MODES = {"value": 0, "value_expert": 1, "value_policy": 2, "q_old_policy": 3, "v0": 4,
+                        "value_q_old_policy": 5, "off": 6}
+LSIQ_SQIL_LIKE_MODES = {"value": 0, "value_plcy": 1, "q_old_policy": 2}
+LSIQ_LOSSQ_TYPES = {"iq_like": 0, "sqil_like": 1}
+LSIQ_LOSS_MODES_EXP = {"fix": 0, "bootstrap": 1}
+LSIQ_Q_EXP_LOSSES = {None: 0, "MSE": 1, "Huber": 2}
 # out [16] of oly_iq_q_update: the reference's tags (iq_sac.py:426-428, 494, 535, 624-643); SQIL logs slot 0 as IQ-Loss/LossQ
 IQ_Q_TAGS = ("IQ-Loss/Loss1", "IQ-Loss/Loss2", "IQ-Loss/Chi2 Loss", "V for policy on all states",
              "Action-Value/Q for expert", "Action-Value/Q^2 for expert", "Action-Value/Q for policy",

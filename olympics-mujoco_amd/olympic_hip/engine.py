@@ -1166,13 +1166,18 @@ class Engine:
                     target_colstats, param, m, v, packed, target_param, target_packed, ws, step, lr, algo="iq",
                     plcy_loss_mode="value", regularizer_mode="exp_and_plcy", treat_absorbing=False, use_target=True,
                     update_target=True, gamma=0.99, alpha=1e-3, reg_mult=0.5, R_min=0.0, R_max=1.0, tau=0.005, beta1=0.9,
-                    beta2=0.999, eps=1e-8, weight_decay=0.0, gradient_penalty_lambda=0.0, out=None):
-        """oly_iq_q_update: one update_Q_function and _update_all_targets of IQ_SAC (algo "iq") or SQIL ("sqil").  obs /
+                    beta2=0.999, eps=1e-8, weight_decay=0.0, gradient_penalty_lambda=0.0, out=None, lsiq=None):
+        """oly_iq_q_update: one update_Q_function and _update_all_targets of IQ_SAC (algo "iq"), SQIL ("sqil") or LSIQ
+        ("lsiq").  obs /
         next_obs [B,in] f32, act / a_next / a_pi [B,A] f32, absorbing / logp_next / logp_pi [B] f32; rows [0, n_policy)
         are the policy's, the rest the expert's.  colstats / target_colstats [3,in+A] f64 or None; param / m / v /
         target_param flat in torch order (W1 [512,in+A] | b1 | W2 | b2 | W3 [1,256] | b3); packed / target_packed their
         ilmlp_pack streams, kept current by the call; step = Adam steps taken before.  a_pi / logp_pi may be None for
-        SQIL's plcy mode.  Returns out [16] f64 (_abi.IQ_Q_TAGS).  No synchronisation."""
+        SQIL's plcy mode.  lsiq (algo "lsiq" only, required there): dict(lossQ_type "iq_like" | "sqil_like", loss_mode_exp
+        "fix" | "bootstrap", Q_exp_loss None | "MSE" | "Huber", target_clipping, Q_min, Q_max), LSIQ's keywords;
+        plcy_loss_mode is then one of _abi.LSIQ_PLCY_LOSS_MODES (iq_like) or _abi.LSIQ_SQIL_LIKE_MODES (sqil_like).  With
+        sqil_like / value_plcy a_pi is [n_policy, A] and logp_pi [n_policy]; with sqil_like / q_old_policy both may be
+        None.  Returns out [16] f64 (_abi.IQ_Q_TAGS).  No synchronisation."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
         if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or not isinstance(act, torch.Tensor) or act.dim() != 2:
@@ -1188,7 +1193,36 @@ class Engine:
         if algo not in _abi.IQ_ALGO:
             raise OlyError(f"iq_q_update: unknown algorithm {algo!r}")
         modes = _abi.IQ_PLCY_LOSS_MODES if algo == "iq" else _abi.SQIL_PLCY_LOSS_MODES
-        if plcy_loss_mode not in modes or (algo == "iq" and plcy_loss_mode == "v0"):
+        block, sqil_like = None, False
+        if algo == "lsiq":
+            if lsiq is None:
+                raise OlyError("iq_q_update: algo 'lsiq' needs the lsiq block")
+            ls = dict(lossQ_type="iq_like", loss_mode_exp="fix", Q_exp_loss=None, target_clipping=True, Q_min=-1.0, Q_max=1.0)
+            unknown = set(lsiq) - set(ls)
+            if unknown:
+                raise OlyError(f"iq_q_update: the lsiq block has unknown entries {sorted(unknown)}")
+            ls.update(lsiq)
+            for key, table in (("lossQ_type", _abi.LSIQ_LOSSQ_TYPES), ("loss_mode_exp", _abi.LSIQ_LOSS_MODES_EXP),
+                               ("Q_exp_loss", _abi.LSIQ_Q_EXP_LOSSES)):
+                if ls[key] not in table:
+                    raise OlyError(f"iq_q_update: {key} {ls[key]!r} is not one of {list(table)}")
+            sqil_like = ls["lossQ_type"] == "sqil_like"
+            if ls["Q_exp_loss"] is None and (sqil_like or ls["loss_mode_exp"] == "fix"):
+                raise OlyError("iq_q_update: loss_mode_exp 'fix' and lossQ_type 'sqil_like' need Q_exp_loss 'MSE' or 'Huber'")
+            if not float(ls["Q_min"]) < float(ls["Q_max"]):
+                raise OlyError(f"iq_q_update: Q_min={ls['Q_min']} must lie below Q_max={ls['Q_max']}")
+            modes = _abi.LSIQ_SQIL_LIKE_MODES if sqil_like else _abi.LSIQ_PLCY_LOSS_MODES
+            if sqil_like and plcy_loss_mode == "value" and 2 * int(n_policy) != B:
+                raise OlyError(f"iq_q_update: sqil_like with plcy_loss_mode 'value' needs 2 n_policy == batch (got "
+                               f"{n_policy} of {B})")
+            block = _abi.LSIQ(lossQ_type=_abi.LSIQ_LOSSQ_TYPES[ls["lossQ_type"]],
+                              loss_mode_exp=_abi.LSIQ_LOSS_MODES_EXP[ls["loss_mode_exp"]],
+                              Q_exp_loss=_abi.LSIQ_Q_EXP_LOSSES[ls["Q_exp_loss"]],
+                              target_clipping=int(bool(ls["target_clipping"])), Q_min=float(ls["Q_min"]),
+                              Q_max=float(ls["Q_max"]))
+        elif lsiq is not None:
+            raise OlyError(f"iq_q_update: the lsiq block goes with algo 'lsiq', not {algo!r}")
+        if plcy_loss_mode not in modes or (not sqil_like and algo != "sqil" and plcy_loss_mode == "v0"):
             raise OlyError(f"iq_q_update: plcy_loss_mode {plcy_loss_mode!r} is not one of "
                            f"{[k for k in modes if k != 'v0']} (v0 is not built)")
         if regularizer_mode not in _abi.IQ_REGULARIZER_MODES:
@@ -1198,7 +1232,8 @@ class Engine:
         if not 0.0 <= float(tau) <= 1.0:
             raise OlyError(f"iq_q_update: tau={tau} outside [0, 1]")
         D = in_dim + A
-        need_pi = algo == "iq" or plcy_loss_mode != "plcy"
+        need_pi = not ((algo == "sqil" and plcy_loss_mode == "plcy") or (sqil_like and plcy_loss_mode == "q_old_policy"))
+        n_pi = int(n_policy) if sqil_like and plcy_loss_mode == "value_plcy" else B      # the rows of the third pass
         need_target = bool(use_target) or bool(update_target)
         n_par = 512 * D + 512 + 256 * 512 + 256 + 256 + 1
         npk = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 1))
@@ -1208,8 +1243,8 @@ class Engine:
         _req(absorbing, "absorbing", (B,), f32, dv)
         _req(a_next, "a_next", (B, A), f32, dv)
         _req(logp_next, "logp_next", (B,), f32, dv)
-        _req(a_pi, "a_pi", (B, A), f32, dv, optional=not need_pi)
-        _req(logp_pi, "logp_pi", (B,), f32, dv, optional=not need_pi)
+        _req(a_pi, "a_pi", (n_pi, A), f32, dv, optional=not need_pi)
+        _req(logp_pi, "logp_pi", (n_pi,), f32, dv, optional=not need_pi)
         _req(colstats, "colstats", (3, D), f64, dv, optional=True)
         _req(target_colstats, "target_colstats", (3, D), f64, dv, optional=True)
         for t, name in ((param, "param"), (m, "m"), (v, "v")):
@@ -1231,7 +1266,8 @@ class Engine:
                      colstats=ptr(colstats), target_colstats=ptr(target_colstats), param=param.data_ptr(),
                      m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(), target_param=ptr(target_param),
                      target_packed=ptr(target_packed), packed_floats=npk, target_packed_floats=npk if need_target else 0,
-                     ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr())
+                     ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr(),
+                     lsiq=C.pointer(block) if block is not None else None)
         self.ctx.call("oly_iq_q_update", C.byref(f), self._s())
         return out
 

@@ -1,5 +1,5 @@
-"""The critic side of the SAC-family imitation agents on the device: IQ-Learn (imitation_lib/imitation/iq_sac.py) and
-SQIL (imitation_lib/imitation/sqil_sac.py).
+"""The critic side of the SAC-family imitation agents on the device: IQ-Learn (imitation_lib/imitation/iq_sac.py),
+SQIL (imitation_lib/imitation/sqil_sac.py) and LSIQ (imitation_lib/imitation/lsiq.py).
 
   Regressor(FullyConnectedNetwork((obs | act) -> [512, 256] -> 1)) x 2, _init_target, the critic's optimiser
                                                          -> DeviceSoftQCritic (parameters, target, Adam moments, packed
@@ -14,6 +14,10 @@ SQIL (imitation_lib/imitation/sqil_sac.py).
                                                             ONE oly_iq_q_update call (K26)
   IQ_SAC.fit (:373-406), iq_update's critic part (:408-419)  -> DeviceIQLearn.fit_Q
   SQIL._lossQ (sqil_sac.py:64-136)                       -> DeviceSQIL
+  LSIQ._lossQ, _lossQ_iq_like, _lossQ_sqil_like (lsiq.py:9-195)  -> DeviceLSIQ: the same ONE oly_iq_q_update call with
+                                                            algo "lsiq" and the block of LSIQ's own keywords; the
+                                                            policy passes in the order of the loss type; DeviceLSIQSAC
+                                                            adds DeviceIQSAC's policy side unchanged
 
   IQ_SAC.update_policy, _actor_loss, _update_alpha (:431-465, 587-595), iq_update (:408-419) and fit (:373-406) whole;
   SQIL.iq_update (sqil_sac.py:16-62)                     -> DeviceIQSAC / DeviceSQILSAC: update_policy is ONE
@@ -22,7 +26,7 @@ SQIL (imitation_lib/imitation/sqil_sac.py).
                                                             one oly_iq_alpha_update call
 
 DeviceIQLearn and DeviceSQIL are the critic side alone and refuse learnable_alpha (the policy never moves there);
-DeviceIQSAC and DeviceSQILSAC are the whole agents.  Not built, each refused by the constructors: the gradient penalty
+DeviceIQSAC and DeviceSQILSAC are the whole agents; DeviceLSIQ and DeviceLSIQSAC are the same pair for LSIQ.  Not built, each refused by the constructors: the gradient penalty
 (gradient_penalty_lambda > 0), plcy_loss_mode "v0" and gradient clipping of the actor.
 
 The cost of a learnable temperature: K25, K26 and K27 take alpha by value, so with learnable_alpha the `alpha` property
@@ -314,6 +318,19 @@ class DeviceIQLearn:
     def _has_v(self):
         return True
 
+    def _logs_before_value(self):
+        """Whether logging_loss (and its draw_action on the expert rows) runs before the pass on obs: IQ's order; SQIL
+        logs after its loss is formed (sqil_sac.py:94-113)."""
+        return self.ALGO == "iq"
+
+    def _value_rows(self, obs, n_policy):
+        """The rows getV(.) takes in the loss."""
+        return obs
+
+    def _algo_block(self):
+        """What the algorithm adds to iq_q_update's keywords."""
+        return {}
+
     def _workspace(self, B):
         if B not in self._ws:
             self._ws[B] = self.eng.iq_q_ws(B, self.in_dim, self.act_dim)
@@ -345,11 +362,12 @@ class DeviceIQLearn:
 
         def expert_pass():
             return self._policy_pass(obs[n_policy:], eps.get("expert"), generator, want_log_prob=False)[0]
-        if logging and self.ALGO == "iq":
+        before = self._logs_before_value()
+        if logging and before:
             a_exp = expert_pass()
         if self._has_v():
-            a_pi, lp_pi = self._policy_pass(obs, eps.get("pi"), generator)
-        if logging and self.ALGO != "iq":          # SQIL logs after its loss is formed (sqil_sac.py:94-113)
+            a_pi, lp_pi = self._policy_pass(self._value_rows(obs, n_policy), eps.get("pi"), generator)
+        if logging and not before:
             a_exp = expert_pass()
         w_norm = torch.linalg.vector_norm(c.param.double()) if logging and self.sw is not None else None
         cs, tcs = c._colstats(c.stand), c._colstats(c.target_stand)
@@ -359,7 +377,8 @@ class DeviceIQLearn:
                                    regularizer_mode=self.regularizer_mode, treat_absorbing=self.treat_absorbing_states,
                                    use_target=self.use_target, update_target=True, gamma=self.gamma, alpha=self.alpha,
                                    reg_mult=self.reg_mult, R_min=self.R_min, R_max=self.R_max, tau=c.tau,
-                                   beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, weight_decay=c.weight_decay)
+                                   beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, weight_decay=c.weight_decay,
+                                   **self._algo_block())
         c.step += 1
         if c.stand is not None:
             c.stand._fresh = False
@@ -372,11 +391,11 @@ class DeviceIQLearn:
     def _log(self, out, act, a_exp, n_policy, w_norm):
         host, it, sw = out.cpu().numpy(), self._iter, self.sw
         tags = _abi.IQ_Q_TAGS
-        if self.ALGO == "iq":
+        if self.ALGO != "sqil":
             for k in (0, 1, 2):
                 sw.add_scalar(tags[k], float(host[k]), it)
             sw.add_scalar("IQ-Loss/Alpha", self.alpha, it)
-            skip = ()
+            skip = self._unlogged_slots()
         else:
             sw.add_scalar("IQ-Loss/LossQ", float(host[0]), it)
             sw.add_scalar("Action-Value/R_min", self.R_min, it)
@@ -390,6 +409,9 @@ class DeviceIQLearn:
         sw.add_scalar("Actions/mean squared action expert (from policy)", msq(a_exp), it)
         sw.add_scalar("Actions/mean squared action policy", msq(act[:n_policy]), it)
         sw.add_scalar("Actions/mean squared action both", msq(act), it)
+
+    def _unlogged_slots(self):
+        return ()
 
     def draw_demo_idx(self, n, generator=None):
         """The first n entries of a fresh permutation of the demonstrations (minibatch_generator's first batch)."""
@@ -467,6 +489,61 @@ class DeviceSQIL(DeviceIQLearn):
 
     def _has_v(self):
         return self.plcy_loss_mode != "plcy"
+
+
+class DeviceLSIQ(DeviceIQLearn):
+    """LSIQ (lsiq.py:9-195): DeviceIQLearn with LSIQ's two losses and its clipped target.  The keywords are the
+    reference's: Q_max / Q_min bound the target (target_clipping) and Q_max is the constant the expert's Q is fitted to
+    with loss_mode_exp "fix" (Q_exp_loss "MSE" or "Huber"; None is refused there, as the reference raises);
+    lossQ_type "iq_like" takes IQ's plcy_loss_mode names and value_q_old_policy / off, "sqil_like" takes value, value_plcy
+    and q_old_policy and always needs a Q_exp_loss.  sqil_like / value needs as many policy rows as expert rows (the
+    reference's r_min vector, lsiq.py:165), which the update checks per batch.  sqil_like logs after its loss is formed
+    and runs the pass on obs for value (all rows), value_plcy (the policy's rows alone) or not at all."""
+
+    ALGO = "lsiq"
+    KIND = "lsiq_critic"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, Q_max=1.0, Q_min=-1.0,
+                 loss_mode_exp="fix", Q_exp_loss=None, treat_absorbing_states=False, target_clipping=True,
+                 lossQ_type="iq_like", plcy_loss_mode="value", **kw):
+        who = type(self).__name__
+        if lossQ_type not in _abi.LSIQ_LOSSQ_TYPES:
+            raise OlyError(f"{who}: lossQ_type {lossQ_type!r} is not one of {list(_abi.LSIQ_LOSSQ_TYPES)}")
+        if loss_mode_exp not in _abi.LSIQ_LOSS_MODES_EXP:
+            raise OlyError(f"{who}: loss_mode_exp {loss_mode_exp!r} is not one of {list(_abi.LSIQ_LOSS_MODES_EXP)}")
+        if Q_exp_loss not in _abi.LSIQ_Q_EXP_LOSSES:
+            raise OlyError(f"{who}: Q_exp_loss {Q_exp_loss!r} is not one of {list(_abi.LSIQ_Q_EXP_LOSSES)}")
+        sqil_like = lossQ_type == "sqil_like"
+        if Q_exp_loss is None and (sqil_like or loss_mode_exp == "fix"):
+            raise OlyError(f"{who}: loss_mode_exp 'fix' and lossQ_type 'sqil_like' need Q_exp_loss 'MSE' or 'Huber'; None is "
+                           "not valid there")
+        if not float(Q_min) < float(Q_max):
+            raise OlyError(f"{who}: Q_min={Q_min} must lie below Q_max={Q_max}")
+        self.MODES = tuple(_abi.LSIQ_SQIL_LIKE_MODES) if sqil_like else \
+            tuple(k for k in _abi.LSIQ_PLCY_LOSS_MODES if k != "v0")
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target,
+                         plcy_loss_mode=plcy_loss_mode, treat_absorbing_states=treat_absorbing_states, **kw)
+        self.Q_max, self.Q_min = float(Q_max), float(Q_min)
+        self.loss_mode_exp, self.Q_exp_loss = loss_mode_exp, Q_exp_loss
+        self.target_clipping, self.lossQ_type = bool(target_clipping), lossQ_type
+
+    def _has_v(self):
+        return self.lossQ_type == "iq_like" or self.plcy_loss_mode != "q_old_policy"
+
+    def _logs_before_value(self):
+        return self.lossQ_type == "iq_like"
+
+    def _value_rows(self, obs, n_policy):
+        if self.lossQ_type == "sqil_like" and self.plcy_loss_mode == "value_plcy":
+            return obs[:n_policy]                # getV(obs[~is_expert]), lsiq.py:167
+        return obs
+
+    def _algo_block(self):
+        return dict(lsiq=dict(lossQ_type=self.lossQ_type, loss_mode_exp=self.loss_mode_exp, Q_exp_loss=self.Q_exp_loss,
+                              target_clipping=self.target_clipping, Q_min=self.Q_min, Q_max=self.Q_max))
+
+    def _unlogged_slots(self):
+        return () if self.lossQ_type == "iq_like" else (3,)       # sqil_like never logs V
 
 
 class _PolicySide:
@@ -653,4 +730,20 @@ class DeviceSQILSAC(_PolicySide, DeviceSQIL):
                                learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
 
 
-__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceIQSAC", "DeviceSQILSAC"]
+class DeviceLSIQSAC(_PolicySide, DeviceLSIQ):
+    """LSIQ whole (lsiq.py: an IQ_SAC that overrides _lossQ alone): DeviceLSIQ's critic side with DeviceIQSAC's policy
+    side."""
+
+    KIND = "lsiq_sac"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
+                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
+                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
+                         learnable_alpha=False, **kw)
+        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
+                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
+
+
+__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceIQSAC",
+           "DeviceSQILSAC", "DeviceLSIQSAC"]
