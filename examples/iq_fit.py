@@ -7,6 +7,8 @@ transitions (olympic_hip.synthetic, as examples/iq_q_fit.py): DeviceIQSAC.fit ru
 policy that is trained does not collect them.
 
     python examples/iq_fit.py --algo iq|sqil|lsiq [--learnable-alpha] [--log] [--updates 200] [--batch 32] [--json FILE]
+    python examples/iq_fit.py --algo lsiq_h|lsiq_hc --q-exp-loss MSE [--h-loss-mode MSE|Huber] [--h-tau 0.005]
+        (LSIQ_H / LSIQ_HC, lsiq_h.py / lsiq_hc.py: a second critic H learns the entropy, the actor follows Q + H)
     python examples/iq_fit.py --algo lsiq --q-exp-loss MSE|Huber [--lossq-type iq_like|sqil_like]
         [--loss-mode-exp fix|bootstrap] [--q-min -1] [--q-max 1] [--no-target-clipping] [--plcy-loss-mode MODE]
 """
@@ -23,7 +25,8 @@ from olympic_hip import _abi  # noqa: E402
 from olympic_hip.bc import DeviceSquashedGaussianPolicy  # noqa: E402
 from olympic_hip.engine import Engine  # noqa: E402
 from olympic_hip.gail import DeviceStandardizer  # noqa: E402
-from olympic_hip.iq import DeviceIQSAC, DeviceLSIQSAC, DeviceSoftQCritic, DeviceSQILSAC  # noqa: E402
+from olympic_hip.iq import (DeviceIQSAC, DeviceLSIQHCSAC, DeviceLSIQHSAC, DeviceLSIQSAC, DeviceSoftQCritic,  # noqa: E402
+                            DeviceSQILSAC)
 from olympic_hip.synthetic import il_synthetic_transitions  # noqa: E402
 
 
@@ -34,7 +37,9 @@ class PrintingWriter:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq"), default="iq")
+    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq", "lsiq_h", "lsiq_hc"), default="iq")
+    ap.add_argument("--h-loss-mode", choices=("MSE", "Huber"), default="Huber", help="lsiq_hc: H_loss_mode")
+    ap.add_argument("--h-tau", type=float, default=0.005, help="lsiq_hc: H_tau, the H target's own rate")
     ap.add_argument("--lossq-type", choices=("iq_like", "sqil_like"), default="iq_like", help="lsiq: lossQ_type")
     ap.add_argument("--loss-mode-exp", choices=("fix", "bootstrap"), default="fix", help="lsiq: loss_mode_exp")
     ap.add_argument("--q-exp-loss", choices=("MSE", "Huber"), default=None, help="lsiq: Q_exp_loss (fix and sqil_like need one)")
@@ -66,10 +71,16 @@ def main():
               warmup_transitions=1024, learnable_alpha=args.learnable_alpha, lr_alpha=3e-4, init_alpha=0.1)
     if args.plcy_loss_mode is not None:
         kw["plcy_loss_mode"] = args.plcy_loss_mode
-    if args.algo == "lsiq":
+    if args.algo in ("lsiq_h", "lsiq_hc"):      # the second critic: the same shape, its own optimiser
+        h_lins = [torch.nn.Linear(D + A, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
+        kw["h_critic"] = DeviceSoftQCritic(eng, h_lins, standardizer=DeviceStandardizer(eng, D + A), lr=3e-4, tau=0.005)
+        if args.algo == "lsiq_hc":
+            kw.update(H_tau=args.h_tau, H_loss_mode=args.h_loss_mode)
+    if args.algo.startswith("lsiq"):
         kw.update(lossQ_type=args.lossq_type, loss_mode_exp=args.loss_mode_exp, Q_exp_loss=args.q_exp_loss, Q_min=args.q_min,
                   Q_max=args.q_max, target_clipping=not args.no_target_clipping)
-    agent = dict(iq=DeviceIQSAC, sqil=DeviceSQILSAC, lsiq=DeviceLSIQSAC)[args.algo](eng, policy, critic, demo, **kw)
+    agent = dict(iq=DeviceIQSAC, sqil=DeviceSQILSAC, lsiq=DeviceLSIQSAC, lsiq_h=DeviceLSIQHSAC,
+                 lsiq_hc=DeviceLSIQHCSAC)[args.algo](eng, policy, critic, demo, **kw)
     w0 = policy.param.clone()
     first_pi = last_q = last_pi = None
     for u in range(args.updates):

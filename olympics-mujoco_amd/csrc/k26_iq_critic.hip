@@ -27,6 +27,11 @@
 // LSIQ's sqil_like / value_plcy runs the third pass on the policy's rows alone (QArgs::n_v): the column sums of X2, the
 // count its Standardizer takes and the rows' coefficients cover rows [0, n_policy), and nothing of a_pi / logp_pi past
 // them is read.
+// OLY_IQ_ALGO_LSIQ_H is the TD update of the second critic H of LSIQ_H / LSIQ_HC (update_H_function,
+// imitation_lib/imitation/lsiq_h.py:57-102, imitation_lib/imitation/lsiq_hc.py:23-88): the block's network fields carry H,
+// passes 0 (live, a gradient) and 1 (target) run, the last workgroup of P also forms the batch's count of absorbing rows
+// and the running maximum of -log pi, launch A runs in instantiations of its own (iq_rows_kernel<G1, true>: the other
+// algorithms' code is compiled without the branch), and F commits the running maximum.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits.  The Standardizer's head, the
 // hidden layers, dZ1, the dW chain and the waves' meeting are ilmlp_fit.h's, shared with K18 and K24.
 #include <cstdlib>
@@ -54,9 +59,10 @@ enum { T_Q, T_Q2, T_R, T_Y, T_V, T_VY, T_CHI, T_QABS, T_ABS, T_SQ, T_SV };
 // ((row / 4) W + col) 4 + row % 4, slot s in rows [s BP, (s + 1) BP):
 //   xs [RP][64] | h1 [RP][512] | h2 [RP][256] | dZ1 [RP][512] | dZ2 [RP][256] | dZ3 [RP] | the raw outputs qv [3][BP] of
 //   the three passes | loss partials [BP / 16][2][NTERM] f64 | statistics partials [3][NSP][2][64] f64 | the inputs'
-//   column sums [3][2][64] f64 | gradient-norm partials [weight tiles] f64 | the transposed stream W2T
+//   column sums [3][2][64] f64 | gradient-norm partials [weight tiles] f64 | the transposed stream W2T | LSIQ_H's batch
+//   scalars [4]: the updated running maximum, the count of absorbing rows
 struct WsL {
-  size_t xs, h1, h2, dz1, dz2, dz3, qv, lossp, statp, delta, gnp, w2t, total;
+  size_t xs, h1, h2, dz1, dz2, dz3, qv, lossp, statp, delta, gnp, w2t, hsc, total;
 };
 constexpr int MAX_WTILES = 32 * (IN_MAX / 16) + 512 + 16;
 __host__ __device__ inline WsL ws_layout(int batch) {
@@ -74,7 +80,8 @@ __host__ __device__ inline WsL ws_layout(int batch) {
   W.delta = W.statp + (size_t)3 * NSP * 2 * IN_MAX * 2;
   W.gnp = W.delta + (size_t)3 * 2 * IN_MAX * 2;
   W.w2t = W.gnp + (size_t)MAX_WTILES * 2;
-  W.total = W.w2t + (size_t)H2 * H1;
+  W.hsc = W.w2t + (size_t)H2 * H1;
+  W.total = W.hsc + 4;
   return W;
 }
 
@@ -86,6 +93,11 @@ struct QArgs {
   int n_v;                     // rows of the third pass: B, or n_policy for LSIQ's sqil_like / value_plcy
   float q_min, q_max;          // LSIQ's bounds
   float inv_rm, g1;            // LSIQ sqil_like: f32(1 / reg_mult) and 1 / (1 - gamma) in float32
+  int h_loss, h_cost, h_clip;  // LSIQ_H: the block's h_loss, h_cost, h_clip_expert
+  float h_tu, h_omu, h_td, h_omd;   // LSIQ_H: f32(tau_up), f32(1 - tau_up), f32(tau_down), f32(1 - tau_down)
+  float h_lo, h_hi, h_omg;     // LSIQ_H: the target's clip bounds; 1 - gamma in float32
+  float* h_max;                // LSIQ_H: the block's h_max_state
+  const float *h_q_t, *h_v_t;
   int slot[3];                 // the workspace slot of each pass's gradient rows, -1: the pass has no gradient
   int n_slots;
   const float *obs, *act, *next_obs, *absorbing, *a_next, *logp_next, *a_pi, *logp_pi;
@@ -106,12 +118,50 @@ __device__ __forceinline__ float input_at(const QArgs& a, int src, size_t row, i
   return k < a.in_dim ? s[row * a.in_dim + k] : u[row * a.act_dim + (k - a.in_dim)];
 }
 
+// LSIQ_H, one workgroup: n1 = the count of absorbing rows and cur = max(-logp_next[0, n_policy)), thread t over rows t,
+// t + THREADS, ... and a halving tree (a count of at most 4096 ones and a maximum: exact in any order); thread 0 then
+// forms the running maximum as lsiq_h.py:64-74 does, in float32: the first call takes cur, a later one
+// f32(1 - tau) M + f32(tau) cur (two float32 products, one add) with tau_up where cur > M, else tau_down.  Both go to the
+// workspace; h_max_state itself is written by launch F.
+__device__ __forceinline__ void h_batch_scalars(const QArgs& a, double* part) {
+  const int tid = threadIdx.x;
+  float* cnt = reinterpret_cast<float*>(part);
+  float* mx = cnt + THREADS;
+  float n1 = 0.f, cur = -INFINITY;
+  for (int r = tid; r < a.B; r += THREADS) {
+    n1 += a.absorbing[r] != 0.f ? 1.f : 0.f;
+    if (r < a.n_policy) cur = fmaxf(cur, -a.logp_next[r]);
+  }
+  cnt[tid] = n1;
+  mx[tid] = cur;
+  __syncthreads();
+  for (int h = THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      cnt[tid] += cnt[tid + h];
+      mx[tid] = fmaxf(mx[tid], mx[tid + h]);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    float M = 0.f;
+    if (a.h_clip) {
+      const float M0 = a.h_max[0];
+      cur = mx[0];
+      M = a.h_max[1] == 0.f ? cur : cur > M0 ? a.h_omu * M0 + a.h_tu * cur : a.h_omd * M0 + a.h_td * cur;
+    }
+    a.ws[a.W.hsc] = M;
+    a.ws[a.W.hsc + 1] = cnt[0];
+  }
+  __syncthreads();
+}
+
 // grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. 3 NSP - 1, slice b % NSP of input
 // b / NSP: four row-strided chains per column, met in a fixed order (fit_common.h's fold_chains)
 static_assert(3 * NSP <= PRO_BLOCKS, "one workgroup per statistics slice");
 __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
   __shared__ double part[8 * IN_MAX];
   build_w2t(a);
+  if (a.algo == OLY_IQ_ALGO_LSIQ_H && blockIdx.x == PRO_BLOCKS - 1) h_batch_scalars(a, part);
   const int src = blockIdx.x / NSP, s = blockIdx.x % NSP;
   if (src >= 3 || (src == 2 && !a.has_v) || (!a.colstats && !a.tcolstats)) return;
   const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
@@ -155,7 +205,44 @@ __device__ __forceinline__ void point_loss(int kind, float d, double& value, dou
   }
 }
 
-template <int G1>
+// LSIQ_H's row (lsiq_h.py:57-83, lsiq_hc.py:23-69): the two targets of the [B, B] broadcast, t0 against the n0
+// non-absorbing columns and t1 against the n1 absorbing ones, in float32 in the reference's order; the row's share of the
+// loss sum n0 l(H - t0) + n1 l(H - t1) and dL/dH = (n0 l'(H - t0) + n1 l'(H - t1)) / B^2 in fp64.
+__device__ __forceinline__ float h_row(const QArgs& a, size_t i, int expert, float H, float Ht, double* t) {
+  const float M = a.ws[a.W.hsc], n1 = a.ws[a.W.hsc + 1];
+  const float neg = -a.logp_next[i];
+  float nc = neg;
+  if (a.h_clip && expert) {                                   // torch.clip(neg[expert], M, 100000): min(max(., M), 1e5)
+    nc = nc < M ? M : nc;
+    nc = nc > 100000.f ? 100000.f : nc;
+  }
+  const float nH = Ht + a.alpha * nc;
+  const float cy0 = (1.f - 0.f) * a.gamma, cy1 = (1.f - 1.f) * a.gamma;    // (1 - absorbing[j]) * gamma
+  float t0 = cy0 * nH, t1 = cy1 * nH;
+  if (a.h_cost) {
+    const float Q = a.h_q_t[i], V = a.h_v_t[i];
+    const float Vc = V < a.q_min ? a.q_min : V > a.q_max ? a.q_max : V;
+    const float d0 = Q - cy0 * Vc, d1 = Q - cy1 * Vc;
+    const float rn = d0 < -a.inv_rm ? -a.inv_rm : d0 > a.inv_rm ? a.inv_rm : d0;
+    const float ra = d1 < a.q_min ? a.q_min : d1 > a.q_max ? a.q_max : d1;
+    // (1 - ab) reg_mult reward_non_abs + (ab (1 - gamma)) reg_mult reward_abs: the other product is an exact zero
+    t0 = a.reg_mult * (rn * rn) + t0;
+    t1 = (a.h_omg * a.reg_mult) * (ra * ra) + t1;
+  }
+  t0 = t0 < a.h_lo ? a.h_lo : t0 > a.h_hi ? a.h_hi : t0;
+  t1 = t1 < a.h_lo ? a.h_lo : t1 > a.h_hi ? a.h_hi : t1;
+  double l0, g0, l1, g1;
+  point_loss(a.h_loss, H - t0, l0, g0);
+  point_loss(a.h_loss, H - t1, l1, g1);
+  const double c1 = (double)n1, c0 = (double)a.B - c1, n = (double)a.B;
+  t[T_Q] = H;
+  t[T_R] = neg;
+  // a count of zero takes its term out (0 x inf would be NaN; torch's mean has no such column)
+  t[T_SQ] = (c0 != 0.0 ? c0 * l0 : 0.0) + (c1 != 0.0 ? c1 * l1 : 0.0);
+  return (float)(((c0 != 0.0 ? c0 * g0 : 0.0) + (c1 != 0.0 ? c1 * g1 : 0.0)) / (n * n));
+}
+
+template <int G1, bool HB = false>
 __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xT = lds;                       // [64 x 16]   standardised input (act16 images, mlp_tiles.h)
@@ -264,7 +351,9 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
     double t[NTERM];
     for (int j = 0; j < NTERM; ++j) t[j] = 0.0;
     float cQ = 0.f, cN = 0.f, cV = 0.f;
-    if (e >= 0) {
+    if constexpr (HB) {
+      if (e >= 0) cQ = h_row(a, (size_t)row0 + tid, e, z[0][tid], z[1][tid], t);
+    } else if (e >= 0) {
       const size_t i = (size_t)row0 + tid;
       const double n_all = (double)B, n_p = (double)a.n_policy, n_e = (double)(B - a.n_policy);
       const double n_own = e ? n_e : n_p;
@@ -514,7 +603,22 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
     double o[16];
     for (int j = 0; j < 16; ++j) o[j] = 0.0;
     const bool lsiq = a.algo == OLY_IQ_ALGO_LSIQ;
-    if (a.iq_like) {
+    if (a.algo == OLY_IQ_ALGO_LSIQ_H) {      // the seven scalars of lsiq_h.py:94-100, the gradient's norm, the maximum
+      const float M = a.ws[a.W.hsc];
+      o[0] = (Sp[T_SQ] + Se[T_SQ]) / (n_all * n_all);
+      o[1] = (Sp[T_Q] + Se[T_Q]) / n_all;
+      o[2] = Sp[T_Q] / n_p;
+      o[3] = Se[T_Q] / n_e;
+      o[4] = (Sp[T_R] + Se[T_R]) / n_all;
+      o[5] = Sp[T_R] / n_p;
+      o[6] = Se[T_R] / n_e;
+      o[7] = sqrt(dred[0]);
+      o[8] = a.h_clip ? (double)M : 0.0;
+      if (a.h_clip) {
+        a.h_max[0] = M;
+        a.h_max[1] = 1.f;
+      }
+    } else if (a.iq_like) {
       o[0] = lsiq && a.exp_mode == OLY_LSIQ_EXP_FIX ? Se[T_SQ] / n_e : -Se[T_R] / n_e;
       o[1] = a.loss_mode == OLY_IQ_VALUE ? (Sp[T_VY] + Se[T_VY]) / n_all
              : a.loss_mode == OLY_IQ_VALUE_EXPERT ? Se[T_VY] / n_e
@@ -535,19 +639,21 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
                                                                  : 0.5 * Sp[T_SQ] / n_p;
       o[0] = (double)a.reg_mult * (0.5 * Se[T_SQ] / n_e + second);
     }
-    o[3] = a.has_v && (a.iq_like || !lsiq) ? (Sp[T_V] + Se[T_V]) / n_all : 0.0;
-    o[4] = Se[T_Q] / n_e;
-    o[5] = Se[T_Q2] / n_e;
-    o[6] = Sp[T_Q] / n_p;
-    o[7] = Sp[T_Q2] / n_p;
-    o[8] = (Sp[T_R] + Se[T_R]) / n_all;
-    o[9] = Se[T_R] / n_e;
-    o[10] = Sp[T_R] / n_p;
-    o[11] = Se[T_Y] / n_e;
-    o[12] = Sp[T_Y] / n_p;
-    o[13] = Se[T_QABS] / Se[T_ABS];      // 0 / 0 = NaN for an empty subset, as torch.mean of nothing
-    o[14] = Sp[T_QABS] / Sp[T_ABS];
-    o[15] = sqrt(dred[0]);
+    if (a.algo != OLY_IQ_ALGO_LSIQ_H) {
+      o[3] = a.has_v && (a.iq_like || !lsiq) ? (Sp[T_V] + Se[T_V]) / n_all : 0.0;
+      o[4] = Se[T_Q] / n_e;
+      o[5] = Se[T_Q2] / n_e;
+      o[6] = Sp[T_Q] / n_p;
+      o[7] = Sp[T_Q2] / n_p;
+      o[8] = (Sp[T_R] + Se[T_R]) / n_all;
+      o[9] = Se[T_R] / n_e;
+      o[10] = Sp[T_R] / n_p;
+      o[11] = Se[T_Y] / n_e;
+      o[12] = Sp[T_Y] / n_p;
+      o[13] = Se[T_QABS] / Se[T_ABS];      // 0 / 0 = NaN for an empty subset, as torch.mean of nothing
+      o[14] = Sp[T_QABS] / Sp[T_ABS];
+      o[15] = sqrt(dred[0]);
+    }
     for (int j = 0; j < 16; ++j) a.out[j] = o[j];
   }
   if (tid < D) {
@@ -597,11 +703,29 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
              "batch (got batch %d, in %d, act %d, n_policy %d)",
              name, MAX_BATCH, MAX_ACT, IN_MAX, B, in_dim, A, f->n_policy);
   const bool iq = f->algo == OLY_IQ_ALGO_IQ, sqil = f->algo == OLY_IQ_ALGO_SQIL, lsiq = f->algo == OLY_IQ_ALGO_LSIQ;
-  if (!iq && !sqil && !lsiq) OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown algorithm %d", name, f->algo);
-  const oly_lsiq* ls = lsiq ? f->lsiq : nullptr;      // read for LSIQ alone
-  if (lsiq && !ls) OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL lsiq block with algo OLY_IQ_ALGO_LSIQ", name);
+  const bool hb = f->algo == OLY_IQ_ALGO_LSIQ_H;
+  if (!iq && !sqil && !lsiq && !hb) OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown algorithm %d", name, f->algo);
+  const oly_lsiq* ls = lsiq || hb ? f->lsiq : nullptr;      // read for LSIQ and LSIQ_H alone
+  if ((lsiq || hb) && !ls) OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL lsiq block with algo OLY_IQ_ALGO_LSIQ / _LSIQ_H", name);
   const int md = f->plcy_loss_mode;
   bool iq_like = iq;
+  if (hb) {      // the H update reads the block's bounds and its tail; the Q loss's enumerants are not its own
+    if (!(ls->Q_min < ls->Q_max)) OLY_FAIL(ctx, OLY_EINVAL, "%s: Q_min %g must lie below Q_max %g", name, ls->Q_min, ls->Q_max);
+    if (ls->h_loss != OLY_LSIQ_LOSS_MSE && ls->h_loss != OLY_LSIQ_LOSS_HUBER)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: h_loss %d is neither OLY_LSIQ_LOSS_MSE nor OLY_LSIQ_LOSS_HUBER", name, ls->h_loss);
+    if (ls->h_cost != 0 && ls->h_cost != 1) OLY_FAIL(ctx, OLY_EINVAL, "%s: h_cost %d is neither 0 nor 1", name, ls->h_cost);
+    if (!(ls->h_tau_up >= 0.0 && ls->h_tau_up <= 1.0) || !(ls->h_tau_down >= 0.0 && ls->h_tau_down <= 1.0))
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: h_tau_up %g / h_tau_down %g outside [0, 1]", name, ls->h_tau_up, ls->h_tau_down);
+    if (!f->use_target) OLY_FAIL(ctx, OLY_EINVAL, "%s: the H update needs use_target (H' is the target H)", name);
+    if (md != 0 || f->regularizer_mode != 0)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: the H update takes plcy_loss_mode 0 and regularizer_mode 0 (got %d, %d)", name, md,
+               f->regularizer_mode);
+    if (!(f->reg_mult > 0.f) && ls->h_cost) OLY_FAIL(ctx, OLY_EINVAL, "%s: h_cost needs reg_mult > 0", name);
+    if ((ls->h_clip_expert && !ls->h_max_state) || (ls->h_cost && (!ls->h_q_t || !ls->h_v_t)))
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL h_max_state (with h_clip_expert) or h_q_t / h_v_t (with h_cost)", name);
+    if ((reinterpret_cast<uintptr_t>(ls->h_max_state) & 3) != 0)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: h_max_state must be 4-byte aligned", name);
+  }
   if (lsiq) {
     if (ls->lossQ_type != OLY_LSIQ_IQ_LIKE && ls->lossQ_type != OLY_LSIQ_SQIL_LIKE)
       OLY_FAIL(ctx, OLY_EINVAL, "%s: unknown lossQ_type %d", name, ls->lossQ_type);
@@ -618,7 +742,8 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
                name, f->n_policy, B);
   }
   if ((iq || (lsiq && iq_like)) && md == OLY_IQ_V0) OLY_FAIL(ctx, OLY_EINVAL, "%s: plcy_loss_mode v0 is not built", name);
-  if (iq     ? (md < OLY_IQ_VALUE || md > OLY_IQ_Q_OLD_POLICY)
+  if (hb     ? false
+      : iq   ? (md < OLY_IQ_VALUE || md > OLY_IQ_Q_OLD_POLICY)
       : sqil ? (md < OLY_SQIL_PLCY || md > OLY_SQIL_VALUE_PLCY)
       : iq_like ? (md < OLY_LSIQ_VALUE || md > OLY_LSIQ_OFF)
                 : (md < OLY_LSIQ_SQ_VALUE || md > OLY_LSIQ_SQ_Q_OLD_POLICY))
@@ -630,7 +755,7 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
   if (!(f->tau >= 0.0 && f->tau <= 1.0)) OLY_FAIL(ctx, OLY_EINVAL, "%s: tau %g outside [0, 1]", name, f->tau);
   // the pass on (obs | a_pi): always in IQ's family (getV(obs) runs in every mode, lsiq.py:72), in SQIL's but for plcy, in
   // LSIQ's sqil_like but for q_old_policy
-  const bool has_v = iq_like || (sqil ? md != OLY_SQIL_PLCY : md != OLY_LSIQ_SQ_Q_OLD_POLICY);
+  const bool has_v = !hb && (iq_like || (sqil ? md != OLY_SQIL_PLCY : md != OLY_LSIQ_SQ_Q_OLD_POLICY));
   const bool need_target = f->use_target || f->update_target;
   if (!f->obs || !f->act || !f->next_obs || !f->absorbing || !f->a_next || !f->logp_next || !f->param || !f->m || !f->v ||
       !f->packed || !f->ws || !f->out || (has_v && (!f->a_pi || !f->logp_pi)) ||
@@ -672,6 +797,31 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
     a.g1 = 1.f / (1.f - f->gamma);
     if (!iq_like && md == OLY_LSIQ_SQ_VALUE_PLCY) a.n_v = f->n_policy;
   }
+  if (hb) {
+    a.q_min = ls->Q_min;
+    a.q_max = ls->Q_max;
+    a.inv_rm = (float)(1.0 / (double)f->reg_mult);
+    a.h_loss = ls->h_loss;
+    a.h_cost = ls->h_cost;
+    a.h_clip = ls->h_clip_expert != 0;
+    a.h_tu = (float)ls->h_tau_up;
+    a.h_omu = (float)(1.0 - ls->h_tau_up);
+    a.h_td = (float)ls->h_tau_down;
+    a.h_omd = (float)(1.0 - ls->h_tau_down);
+    a.h_omg = 1.f - f->gamma;
+    a.h_lo = ls->h_cost ? -1000.f : -10000.f;
+    a.h_hi = 1000.f;
+    if (ls->h_cost) {   // Q2_max + 100, Q2_max = (1 / reg_mult)^2 / (1 - gamma): a double over a float32 tensor, which torch
+                        // evaluates as the tensor's float32 reciprocal times the float32 of the double (lsiq_hc.py:61-62)
+      const double r = 1.0 / (double)f->reg_mult;
+      const float rec = 1.f / a.h_omg;
+      const float q2 = rec * (float)(r * r);
+      a.h_hi = q2 + 100.f;
+    }
+    a.h_max = ls->h_max_state;
+    a.h_q_t = ls->h_q_t;
+    a.h_v_t = ls->h_v_t;
+  }
   int ns = 0;
   a.slot[0] = ns++;
   a.slot[1] = a.use_target ? -1 : ns++;
@@ -709,7 +859,9 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
 
   const int tiles_a = (B + 15) / 16, tiles_b = weight_tiles(D, 1);
   hipLaunchKernelGGL(iq_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
-  rc = launch_rows(ctx, ctx->iqq_attr_done, 1u, iq_rows_kernel<2>, iq_rows_kernel<4>, D, dim3(tiles_a), ROWS_LDS, stream, a);
+  rc = hb ? launch_rows(ctx, ctx->iqq_attr_done, 4u, iq_rows_kernel<2, true>, iq_rows_kernel<4, true>, D, dim3(tiles_a),
+                        ROWS_LDS, stream, a)
+          : launch_rows(ctx, ctx->iqq_attr_done, 1u, iq_rows_kernel<2>, iq_rows_kernel<4>, D, dim3(tiles_a), ROWS_LDS, stream, a);
   if (rc != OLY_OK) return rc;
   hipLaunchKernelGGL(iq_weights_kernel, dim3(tiles_b), dim3(THREADS), 0, oly_s(stream), a);
   hipLaunchKernelGGL(iq_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), a, tiles_a, tiles_b);

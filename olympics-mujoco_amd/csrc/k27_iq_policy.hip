@@ -35,6 +35,14 @@
 //   dL/dmu_j         = dL/du_j
 //   dL/dlog_sigma_j  = dL/du_j sigma eps - alpha / Bp, 0 where the clamp cuts (inclusive mask)
 // (the Normal's quadratic term is eps^2 / 2: it carries no gradient).
+//
+// LSIQ_H / LSIQ_HC's _actor_loss (imitation_lib/imitation/lsiq_h.py:104-108) is mean(alpha log_prob - (q + H)) over TWO live
+// critics on the same rows (x | a_new), each standardised with its own Standardizer, which the call updates by the Bp rows.
+// With h_packed set P also builds H's transposed W2 stream and its action columns of W1 in the second workspace h_ws (the
+// layout of the first, of which cw2t, cw1a and qv are used), A2 runs in instantiations of its own (iqpi_grad_kernel<GC,
+// true>): the critic's forward and data gradients, then H's, each net's dX on an action column divided by THAT net's std
+// of the column in fp64 and added, the critic's first, before the chain; F adds the rows to both Standardizers and
+// reports mean(q + H) with q + H formed in float32 as the reference's soft_q.  Neither critic's parameters are written.
 #include <cstdlib>
 
 #include "ilmlp_fit.h"
@@ -92,6 +100,9 @@ struct PiArgs {
   float *param, *m, *v, *packed, *ws;
   const float *cpacked, *cparam;
   float *action, *log_prob;
+  const float *hpacked, *hparam;   // LSIQ_H's second critic H (NULL: one critic), its statistics and its workspace
+  double* hcolstats;
+  float* hws;
   float alpha, ls_min, ls_max, coef;   // coef: f32(-1 / Bp), dL/dq of every row
   oly_fit::AdamK ad;
   float wd;
@@ -110,6 +121,12 @@ __global__ __launch_bounds__(THREADS) void iqpi_prologue_kernel(PiArgs a) {
   for (int e = g0; e < MAX_ACT * H1; e += gs) {
     const int j = e / H1, n = e % H1;
     a.ws[a.W.cw1a + e] = j < a.act_dim ? a.cparam[a.CP.w1 + (size_t)n * a.D + a.in_dim + j] : 0.f;
+  }
+  if (!a.hparam) return;               // H's streams, into its own workspace
+  for (int e = g0; e < H2 * H1; e += gs) a.hws[a.W.cw2t + pt_index(H2, e / H1, e % H1)] = a.hparam[a.CP.w2 + e];
+  for (int e = g0; e < MAX_ACT * H1; e += gs) {
+    const int j = e / H1, n = e % H1;
+    a.hws[a.W.cw1a + e] = j < a.act_dim ? a.hparam[a.CP.w1 + (size_t)n * a.D + a.in_dim + j] : 0.f;
   }
 }
 
@@ -218,9 +235,10 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_act_kernel(PiArgs a) {
 // Launch A2.  The critic's forward and data gradients, the chain through the squash, the policy's backward.
 constexpr size_t A2_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16 + OUTP * 16 + 2 * 16 * MAX_ACT;
 constexpr size_t A2_LDS = sizeof(float) * A2_LDS_FLOATS + sizeof(double) * (2 * IN_MAX);
+constexpr size_t A2H_LDS = A2_LDS + sizeof(double) * 16 * MAX_ACT;     // two critics: the critic's dX / std by (row, action)
 static_assert(A2_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
 
-template <int GC>
+template <int GC, bool HB = false>
 __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xT = lds;                       // [64 x 16]   the critic's standardised input
@@ -230,18 +248,28 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
   float* gz3 = gz + H2 * 16;             // [32 x 16]   the policy's dZ3
   float* dxp = gz3 + OUTP * 16;          // [2][16][16] the halves of dX by (row, action)
   double* st = reinterpret_cast<double*>(lds + A2_LDS_FLOATS);   // [2][IN_MAX] mean, std of the critic's columns
+  double* dq = st + 2 * IN_MAX;          // HB: [16][16] the critic's dX / std, while H's pass runs
   __shared__ float zq[16];
-  const float* CPk = a.cpacked;
-  const float4* CP4 = reinterpret_cast<const float4*>(CPk);
+  __shared__ float zh[16];               // HB: H's raw outputs by row
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, h4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row0 = blockIdx.x * 16, B = a.B, in_dim = a.in_dim, A = a.act_dim, D = a.D;
   const int rows = min(16, B - row0);
-  const bool standardise = a.ccolstats != nullptr;
   float* ws = a.ws;
   float4* ws4 = reinterpret_cast<float4*>(ws);
   const size_t quad = (size_t)(row0 >> 2) + h4;
+  gz3[tid] = 0.f;                        // RTHREADS = 32 x 16
+  static_assert(RTHREADS == OUTP * 16, "one thread per element of the dZ3 image");
 
+#pragma unroll
+  for (int net = 0; net < (HB ? 2 : 1); ++net) {   // the critic, then (HB) H: the same rows, each net's own statistics
+  const float* CPk = net ? a.hpacked : a.cpacked;
+  const float4* CP4 = reinterpret_cast<const float4*>(CPk);
+  const float* cparam = net ? a.hparam : a.cparam;
+  const double* ccol = net ? a.hcolstats : a.ccolstats;
+  const float* nws = net ? a.hws : ws;             // where P left this net's cw2t and cw1a
+  float* zo = net ? zh : zq;
+  const bool standardise = ccol != nullptr;
   if (tid < D) {   // Standardizer.update_mean_std with all Bp rows of (x | a_new) (networks.py:76-81): the tiles' slots in order
     const double* cp = reinterpret_cast<const double*>(ws + a.W.cpart);
     double s = 0.0, ss = 0.0;
@@ -249,19 +277,16 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
       s += cp[(size_t)t * 2 * IN_MAX + tid];
       ss += cp[(size_t)t * 2 * IN_MAX + IN_MAX + tid];
     }
-    if (blockIdx.x == 0) {
+    if (blockIdx.x == 0 && net == 0) {
       double* d = reinterpret_cast<double*>(ws + a.W.cdelta);
       d[tid] = s;
       d[IN_MAX + tid] = ss;
     }
     double mean = 0.0, sd = 1.0;
-    if (standardise)
-      col_moments(a.ccolstats[tid] + (double)B, a.ccolstats[D + tid] + s, a.ccolstats[2 * D + tid] + ss, mean, sd);
+    if (standardise) col_moments(ccol[tid] + (double)B, ccol[D + tid] + s, ccol[2 * D + tid] + ss, mean, sd);
     st[tid] = mean;
     st[IN_MAX + tid] = sd;
   }
-  gz3[tid] = 0.f;                        // RTHREADS = 32 x 16
-  static_assert(RTHREADS == OUTP * 16, "one thread per element of the dZ3 image");
   __syncthreads();
   for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
     const int m = e / IN_MAX, k = e & (IN_MAX - 1);
@@ -288,8 +313,8 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float q = acc[0][0][i] + bv;
-        zq[4 * h4 + i] = q;
-        ws[a.W.qv + row0 + 4 * h4 + i] = q;
+        zo[4 * h4 + i] = q;
+        (net ? a.hws : ws)[a.W.qv + row0 + 4 * h4 + i] = q;
       }
     }
   }
@@ -297,7 +322,7 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int col = 16 * (2 * wave + t) + c;
-      const float w3 = a.cparam[a.CP.w3 + col];
+      const float w3 = cparam[a.CP.w3 + col];
       const float4 h = get_quad(hB, col, h4);
       const float g0 = a.coef * w3;
       float4 g;
@@ -314,7 +339,7 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float4* a4[1] = {reinterpret_cast<const float4*>(gz)};
-    tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(ws) + (a.W.cw2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
+    tiles<H2 / 16, 4, 1>(a4, reinterpret_cast<const float4*>(nws) + (a.W.cw2t >> 2) + (size_t)(4 * wave) * (H2 / 16) * 64,
                          (H2 / 16) * 64, lane, acc);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -331,18 +356,25 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
   __syncthreads();
   {  // ---- dX on the action columns: thread (row m, action j, half hf) one fma chain over its 256 units in order
     const int m = tid >> 5, j = (tid >> 1) & 15, hf = tid & 1;
-    const float* w = ws + a.W.cw1a + (size_t)j * H1;
+    const float* w = nws + a.W.cw1a + (size_t)j * H1;
     float s = 0.f;
     for (int n = hf * (H1 / 2); n < (hf + 1) * (H1 / 2); ++n) s = fmaf(hA[act16_index(n, m)], w[n], s);
     dxp[(hf * 16 + m) * MAX_ACT + j] = s;
   }
   __syncthreads();
+  if (HB && net == 0) {   // the critic's dX / std_Q in fp64, kept while H's pass reuses dxp and st
+    if (tid < 256) dq[tid] = (tid & 15) < A ? (double)(dxp[tid] + dxp[256 + tid]) / st[IN_MAX + in_dim + (tid & 15)] : 0.0;
+    __syncthreads();
+  }
+  }   // net
   if (tid < 256) {  // ---- the chain through the action's bounds, the squash and the sample: thread (row m, action j), fp64
     const int m = tid >> 4, j = tid & 15;
     if (m < rows && j < A) {
       const size_t row = (size_t)row0 + m;
       const double Bd = (double)B, al = (double)a.alpha;
-      const double dxa = (double)(dxp[m * MAX_ACT + j] + dxp[(16 + m) * MAX_ACT + j]) / st[IN_MAX + in_dim + j];
+      // d(q [+ H])/da_new: each net's dX over that net's std of the column, the critic's term first
+      double dxa = (double)(dxp[m * MAX_ACT + j] + dxp[(16 + m) * MAX_ACT + j]) / st[IN_MAX + in_dim + j];
+      if (HB) dxa = dq[m * MAX_ACT + j] + dxa;
       const double th = tanh((double)ws[a.W.th + row * MAX_ACT + j]);   // from the stored sample u, as A1 formed it
       const float raw = ws[a.W.zr + row * OUTP + A + j];
       const float ls = fminf(fmaxf(raw, a.ls_min), a.ls_max);
@@ -362,7 +394,7 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
   if (tid < 3) {    // this tile's loss partials, rows in order: alpha log_prob - q, log_prob, q
     double s = 0.0;
     for (int r = 0; r < rows; ++r) {
-      const double lp = (double)a.log_prob[row0 + r], q = (double)zq[r];
+      const double lp = (double)a.log_prob[row0 + r], q = (double)(HB ? zq[r] + zh[r] : zq[r]);   // soft_q = q + H in float32
       s += tid == 0 ? (double)a.alpha * lp - q : tid == 1 ? lp : q;
     }
     reinterpret_cast<double*>(ws + a.W.lossp)[(size_t)blockIdx.x * 4 + tid] = s;
@@ -486,13 +518,19 @@ __global__ __launch_bounds__(THREADS) void iqpi_fold_kernel(PiArgs a, int tiles_
     a.out[0] = S[0] / n;           // Actor/Loss
     a.out[1] = sqrt(dred[0]);      // the gradient's 2-norm
     a.out[2] = S[1] / n;           // mean(log_prob)
-    a.out[3] = S[2] / n;           // mean(Q)
+    a.out[3] = S[2] / n;           // mean(Q), with H mean(Q + H)
   }
   if (tid < D && a.ccolstats) {
     const double* d = reinterpret_cast<const double*>(a.ws + a.W.cdelta);
     a.ccolstats[tid] += (double)a.B;
     a.ccolstats[D + tid] += d[tid];
     a.ccolstats[2 * D + tid] += d[IN_MAX + tid];
+  }
+  if (tid < D && a.hpacked && a.hcolstats) {   // H's Standardizer takes the same rows: the same sums
+    const double* d = reinterpret_cast<const double*>(a.ws + a.W.cdelta);
+    a.hcolstats[tid] += (double)a.B;
+    a.hcolstats[D + tid] += d[tid];
+    a.hcolstats[2 * D + tid] += d[IN_MAX + tid];
   }
 }
 
@@ -566,6 +604,18 @@ extern "C" int oly_iq_pi_update(oly_ctx* ctx, const oly_iq_pi* f, oly_stream str
   if ((reinterpret_cast<uintptr_t>(f->out) & 7) != 0 || (reinterpret_cast<uintptr_t>(f->colstats) & 7) != 0 ||
       (reinterpret_cast<uintptr_t>(f->critic_colstats) & 7) != 0)
     OLY_FAIL(ctx, OLY_EINVAL, "%s: out and the colstats must be 8-byte aligned", name);
+  const bool hb = f->h_packed != nullptr;
+  if (hb) {
+    if (!f->h_param || !f->h_ws) OLY_FAIL(ctx, OLY_EINVAL, "%s: h_packed needs h_param and h_ws", name);
+    if ((reinterpret_cast<uintptr_t>(f->h_packed) & 15) != 0 || (reinterpret_cast<uintptr_t>(f->h_ws) & 15) != 0)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: h_packed and h_ws must be 16-byte aligned", name);
+    if (f->h_packed_floats < (int64_t)P_TOTAL) OLY_FAIL(ctx, OLY_EINVAL, "%s: a packed stream holds %ld floats", name, (long)P_TOTAL);
+    if (f->h_ws_floats < (int64_t)W.total)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: h_ws holds %ld floats, %ld are needed", name, (long)f->h_ws_floats, (long)W.total);
+    if ((reinterpret_cast<uintptr_t>(f->h_colstats) & 7) != 0) OLY_FAIL(ctx, OLY_EINVAL, "%s: h_colstats must be 8-byte aligned", name);
+    if (f->h_ws == f->ws || f->h_packed == f->critic_packed)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: H needs a stream and a workspace of its own", name);
+  }
 
   PiArgs a{};
   a.in_dim = in_dim;
@@ -586,6 +636,10 @@ extern "C" int oly_iq_pi_update(oly_ctx* ctx, const oly_iq_pi* f, oly_stream str
   a.ws = f->ws;
   a.cpacked = f->critic_packed;
   a.cparam = f->critic_param;
+  a.hpacked = f->h_packed;
+  a.hparam = hb ? f->h_param : nullptr;
+  a.hcolstats = hb ? f->h_colstats : nullptr;
+  a.hws = hb ? f->h_ws : nullptr;
   a.action = f->action;
   a.log_prob = f->log_prob;
   a.alpha = f->alpha;
@@ -607,7 +661,9 @@ extern "C" int oly_iq_pi_update(oly_ctx* ctx, const oly_iq_pi* f, oly_stream str
   hipLaunchKernelGGL(iqpi_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   rc = launch_rows(ctx, ctx->iqpi_attr_done, 1u, iqpi_act_kernel<2>, iqpi_act_kernel<4>, in_dim, dim3(tiles_a), A1_LDS, stream, a);
   if (rc != OLY_OK) return rc;
-  rc = launch_rows(ctx, ctx->iqpi_attr_done, 4u, iqpi_grad_kernel<2>, iqpi_grad_kernel<4>, D, dim3(tiles_a), A2_LDS, stream, a);
+  rc = hb ? launch_rows(ctx, ctx->iqpi_attr_done, 16u, iqpi_grad_kernel<2, true>, iqpi_grad_kernel<4, true>, D, dim3(tiles_a),
+                        A2H_LDS, stream, a)
+          : launch_rows(ctx, ctx->iqpi_attr_done, 4u, iqpi_grad_kernel<2>, iqpi_grad_kernel<4>, D, dim3(tiles_a), A2_LDS, stream, a);
   if (rc != OLY_OK) return rc;
   hipLaunchKernelGGL(iqpi_weights_kernel, dim3(tiles_b), dim3(THREADS), 0, oly_s(stream), a);
   hipLaunchKernelGGL(iqpi_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), a, tiles_a, tiles_b);

@@ -5,8 +5,8 @@ its absence is an error, not a fallback."""
 from . import _abi, specs  # noqa: F401
 
 __all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy", "DeviceSoftQCritic",
-           "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceIQSAC", "DeviceSQILSAC",
-           "DeviceLSIQSAC"]
+           "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceLSIQH", "DeviceLSIQHC", "DeviceIQSAC",
+           "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC"]
 
 
 def __getattr__(name):
@@ -15,8 +15,8 @@ def __getattr__(name):
         from . import bc
         return getattr(bc, name)
     # the SAC family (iq.py: the critic side K26, the whole agents with the policy side K27)
-    if name in ("DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceIQSAC",
-                "DeviceSQILSAC", "DeviceLSIQSAC"):
+    if name in ("DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceLSIQH",
+                "DeviceLSIQHC", "DeviceIQSAC", "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC"):
         from . import iq
         return getattr(iq, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

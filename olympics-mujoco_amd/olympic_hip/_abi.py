@@ -271,9 +271,12 @@ class SGAct(C.Structure):
 
 
 class LSIQ(C.Structure):
-    """oly_lsiq (K26): LSIQ's own parameters, the block oly_iq_q.lsiq points to."""
+    """oly_lsiq (K26): LSIQ's own parameters, the block oly_iq_q.lsiq points to; the h_* tail is read for the H update
+    (algo "lsiq_h") alone."""
     _fields_ = [("lossQ_type", C.c_int32), ("loss_mode_exp", C.c_int32), ("Q_exp_loss", C.c_int32),
-                ("target_clipping", C.c_int32), ("Q_min", C.c_float), ("Q_max", C.c_float)]
+                ("target_clipping", C.c_int32), ("Q_min", C.c_float), ("Q_max", C.c_float), ("h_loss", C.c_int32),
+                ("h_cost", C.c_int32), ("h_clip_expert", C.c_int32), ("h_pad", C.c_int32), ("h_tau_up", C.c_double),
+                ("h_tau_down", C.c_double), ("h_max_state", vp), ("h_q_t", vp), ("h_v_t", vp)]
 
 
 class IQQ(C.Structure):
@@ -300,7 +303,8 @@ class IQPi(C.Structure):
                 ("x", vp), ("eps", vp), ("central", vp), ("delta", vp), ("colstats", vp), ("param", vp), ("m", vp),
                 ("v", vp), ("packed", vp), ("packed_floats", C.c_int64), ("critic_packed", vp),
                 ("critic_packed_floats", C.c_int64), ("critic_param", vp), ("critic_colstats", vp), ("ws", vp),
-                ("ws_floats", C.c_int64), ("action", vp), ("log_prob", vp), ("out", vp)]
+                ("ws_floats", C.c_int64), ("action", vp), ("log_prob", vp), ("out", vp), ("h_packed", vp),
+                ("h_packed_floats", C.c_int64), ("h_param", vp), ("h_colstats", vp), ("h_ws", vp), ("h_ws_floats", C.c_int64)]
 
 
 class IQAlpha(C.Structure):
@@ -313,7 +317,7 @@ class IQAlpha(C.Structure):
 # out [4] of oly_iq_pi_update (iq_sac.py:441-443); slots 2 and 3 are the means of log_prob and of Q(x | a_new)
 IQ_PI_TAGS = ("Actor/Loss", "Gradients/Norm2 Gradient Q wrt. Pi-parameters", "mean(log_prob)", "mean(Q)")
 
-IQ_ALGO = {"iq": 0, "sqil": 1, "lsiq": 2}
+IQ_ALGO = {"iq": 0, "sqil": 1, "lsiq": 2, "lsiq_h": 3}
 IQ_PLCY_LOSS_MODES = {"value": 0, "value_expert": 1, "value_policy": 2, "q_old_policy": 3, "v0": 4}
 SQIL_PLCY_LOSS_MODES = {"plcy": 0, "value": 1, "value_plcy": 2}
 IQ_REGULARIZER_MODES = {"exp_and_plcy": 0, "exp": 1, "plcy": 2, "off": 3}
@@ -324,6 +328,12 @@ LSIQ_SQIL_LIKE_MODES = {"value": 0, "value_plcy": 1, "q_old_policy": 2}
 LSIQ_LOSSQ_TYPES = {"iq_like": 0, "sqil_like": 1}
 LSIQ_LOSS_MODES_EXP = {"fix": 0, "bootstrap": 1}
 LSIQ_Q_EXP_LOSSES = {None: 0, "MSE": 1, "Huber": 2}
+LSIQ_H_LOSSES = {"MSE": 1, "Huber": 2}      # oly_lsiq.h_loss (LSIQ_HC's H_loss_mode), OLY_LSIQ_LOSS_*
+# out [16] of oly_iq_q_update with algo "lsiq_h": the reference's seven tags (lsiq_h.py:94-100), then the gradient's norm
+# and the running maximum of -log pi, which the reference does not log; slots 9-15 are 0
+LSIQ_H_TAGS = ("H function/Loss", "H function/H", "H function/H plcy", "H function/H expert", "H function/H_step",
+               "H function/H_step plcy", "H function/H_step expert", "Gradients/Norm2 Gradient LossH wrt. H-parameters",
+               "H function/max_H_policy")
 # out [16] of oly_iq_q_update: the reference's tags (iq_sac.py:426-428, 494, 535, 624-643); SQIL logs slot 0 as IQ-Loss/LossQ
 IQ_Q_TAGS = ("IQ-Loss/Loss1", "IQ-Loss/Loss2", "IQ-Loss/Chi2 Loss", "V for policy on all states",
              "Action-Value/Q for expert", "Action-Value/Q^2 for expert", "Action-Value/Q for policy",

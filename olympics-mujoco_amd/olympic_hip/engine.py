@@ -1177,7 +1177,15 @@ class Engine:
         "fix" | "bootstrap", Q_exp_loss None | "MSE" | "Huber", target_clipping, Q_min, Q_max), LSIQ's keywords;
         plcy_loss_mode is then one of _abi.LSIQ_PLCY_LOSS_MODES (iq_like) or _abi.LSIQ_SQIL_LIKE_MODES (sqil_like).  With
         sqil_like / value_plcy a_pi is [n_policy, A] and logp_pi [n_policy]; with sqil_like / q_old_policy both may be
-        None.  Returns out [16] f64 (_abi.IQ_Q_TAGS).  No synchronisation."""
+        None.
+        algo "lsiq_h" is the H update of LSIQ_H / LSIQ_HC (update_H_function): param .. target_packed, colstats,
+        target_colstats, lr and tau are H's network, a_next / logp_next the update's own policy pass on next_obs, a_pi /
+        logp_pi are not read (None), use_target must hold and plcy_loss_mode / regularizer_mode keep their defaults.
+        The lsiq block then also takes h=dict(loss "MSE" | "Huber", cost (False: LSIQ_H's target, True: LSIQ_HC's),
+        clip_expert, tau_up, tau_down, max_state [2] f32 (the running maximum and its flag, on the device; needed with
+        clip_expert), q_t / v_t [B] f32 (Q_target(obs | act), Q_target(obs | a_pi); needed with cost)); out holds
+        _abi.LSIQ_H_TAGS in its first nine slots.
+        Returns out [16] f64 (_abi.IQ_Q_TAGS).  No synchronisation."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
         if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or not isinstance(act, torch.Tensor) or act.dim() != 2:
@@ -1193,11 +1201,13 @@ class Engine:
         if algo not in _abi.IQ_ALGO:
             raise OlyError(f"iq_q_update: unknown algorithm {algo!r}")
         modes = _abi.IQ_PLCY_LOSS_MODES if algo == "iq" else _abi.SQIL_PLCY_LOSS_MODES
-        block, sqil_like = None, False
-        if algo == "lsiq":
+        block, sqil_like, hb = None, False, algo == "lsiq_h"
+        if algo in ("lsiq", "lsiq_h"):
             if lsiq is None:
-                raise OlyError("iq_q_update: algo 'lsiq' needs the lsiq block")
+                raise OlyError(f"iq_q_update: algo {algo!r} needs the lsiq block")
             ls = dict(lossQ_type="iq_like", loss_mode_exp="fix", Q_exp_loss=None, target_clipping=True, Q_min=-1.0, Q_max=1.0)
+            if hb:
+                ls["h"] = None
             unknown = set(lsiq) - set(ls)
             if unknown:
                 raise OlyError(f"iq_q_update: the lsiq block has unknown entries {sorted(unknown)}")
@@ -1206,8 +1216,8 @@ class Engine:
                                ("Q_exp_loss", _abi.LSIQ_Q_EXP_LOSSES)):
                 if ls[key] not in table:
                     raise OlyError(f"iq_q_update: {key} {ls[key]!r} is not one of {list(table)}")
-            sqil_like = ls["lossQ_type"] == "sqil_like"
-            if ls["Q_exp_loss"] is None and (sqil_like or ls["loss_mode_exp"] == "fix"):
+            sqil_like = ls["lossQ_type"] == "sqil_like" and not hb
+            if not hb and ls["Q_exp_loss"] is None and (ls["lossQ_type"] == "sqil_like" or ls["loss_mode_exp"] == "fix"):
                 raise OlyError("iq_q_update: loss_mode_exp 'fix' and lossQ_type 'sqil_like' need Q_exp_loss 'MSE' or 'Huber'")
             if not float(ls["Q_min"]) < float(ls["Q_max"]):
                 raise OlyError(f"iq_q_update: Q_min={ls['Q_min']} must lie below Q_max={ls['Q_max']}")
@@ -1220,6 +1230,31 @@ class Engine:
                               Q_exp_loss=_abi.LSIQ_Q_EXP_LOSSES[ls["Q_exp_loss"]],
                               target_clipping=int(bool(ls["target_clipping"])), Q_min=float(ls["Q_min"]),
                               Q_max=float(ls["Q_max"]))
+            if hb:
+                hd = dict(loss="MSE", cost=False, clip_expert=True, tau_up=1e-2, tau_down=1e-4, max_state=None, q_t=None,
+                          v_t=None)
+                given = ls["h"]
+                if not isinstance(given, dict) or set(given) - set(hd):
+                    raise OlyError(f"iq_q_update: algo 'lsiq_h' needs lsiq['h'], a dict with entries among {sorted(hd)}")
+                hd.update(given)
+                if hd["loss"] not in _abi.LSIQ_H_LOSSES:
+                    raise OlyError(f"iq_q_update: h loss {hd['loss']!r} is not one of {list(_abi.LSIQ_H_LOSSES)}")
+                for key in ("tau_up", "tau_down"):
+                    if not 0.0 <= float(hd[key]) <= 1.0:
+                        raise OlyError(f"iq_q_update: h {key}={hd[key]} outside [0, 1]")
+                if not use_target:
+                    raise OlyError("iq_q_update: the H update needs use_target")
+                if plcy_loss_mode != "value" or regularizer_mode != "exp_and_plcy":
+                    raise OlyError("iq_q_update: the H update takes no plcy_loss_mode or regularizer_mode")
+                if bool(hd["cost"]) and not float(reg_mult) > 0.0:
+                    raise OlyError("iq_q_update: the H update's cost needs reg_mult > 0")
+                _req(hd["max_state"], "h max_state", (2,), f32, dv, optional=not hd["clip_expert"])
+                _req(hd["q_t"], "h q_t", (B,), f32, dv, optional=not hd["cost"])
+                _req(hd["v_t"], "h v_t", (B,), f32, dv, optional=not hd["cost"])
+                block.h_loss, block.h_cost = _abi.LSIQ_H_LOSSES[hd["loss"]], int(bool(hd["cost"]))
+                block.h_clip_expert = int(bool(hd["clip_expert"]))
+                block.h_tau_up, block.h_tau_down = float(hd["tau_up"]), float(hd["tau_down"])
+                block.h_max_state, block.h_q_t, block.h_v_t = ptr(hd["max_state"]), ptr(hd["q_t"]), ptr(hd["v_t"])
         elif lsiq is not None:
             raise OlyError(f"iq_q_update: the lsiq block goes with algo 'lsiq', not {algo!r}")
         if plcy_loss_mode not in modes or (not sqil_like and algo != "sqil" and plcy_loss_mode == "v0"):
@@ -1232,7 +1267,7 @@ class Engine:
         if not 0.0 <= float(tau) <= 1.0:
             raise OlyError(f"iq_q_update: tau={tau} outside [0, 1]")
         D = in_dim + A
-        need_pi = not ((algo == "sqil" and plcy_loss_mode == "plcy") or (sqil_like and plcy_loss_mode == "q_old_policy"))
+        need_pi = not (hb or (algo == "sqil" and plcy_loss_mode == "plcy") or (sqil_like and plcy_loss_mode == "q_old_policy"))
         n_pi = int(n_policy) if sqil_like and plcy_loss_mode == "value_plcy" else B      # the rows of the third pass
         need_target = bool(use_target) or bool(update_target)
         n_par = 512 * D + 512 + 256 * 512 + 256 + 256 + 1
@@ -1283,13 +1318,16 @@ class Engine:
 
     def iq_pi_update(self, x, eps, central, delta, colstats, param, m, v, packed, critic_packed, critic_param,
                      critic_colstats, ws, step, lr, alpha=1e-3, log_std_min=-20.0, log_std_max=2.0, beta1=0.9, beta2=0.999,
-                     adam_eps=1e-8, weight_decay=0.0, out=None):
+                     adam_eps=1e-8, weight_decay=0.0, out=None, h=None):
         """oly_iq_pi_update: one update_policy of IQ_SAC / SQIL (iq_sac.py:431-439, 587-590) without its logging passes.
         x [Bp,in] f32 the policy_training_states, eps [Bp,A] f32 the noise, central / delta [A] f32; colstats [3,in] f64
         the policy's Standardizer or None (it takes the rows first); param / m / v the policy's flat parameters and Adam
         moments in torch order (W1 [512,in] | b1 | W2 | b2 | W3 [2A,256] | b3), packed their ilmlp_pack stream, kept
         current by the call; critic_packed / critic_param the live critic's (read only), critic_colstats [3,in+A] f64 or
-        None (it takes the rows (x | a_new)); step = Adam steps taken before.  Returns dict(action [Bp,A] f32, log_prob
+        None (it takes the rows (x | a_new)); step = Adam steps taken before.  h (LSIQ_H / LSIQ_HC's _actor_loss over two
+        critics, lsiq_h.py:104-108): None, or dict(packed, param, colstats (or None), ws) of the second live critic H, ws a
+        workspace of its own of iq_pi_ws() floats; the loss is then mean(alpha log_prob - (q + H)), out[3] mean(q + H), and
+        H(x | a_new) lies in h["ws"] at oly_iq_pi_ws_values().  Returns dict(action [Bp,A] f32, log_prob
         [Bp] f32, out [4] f64 (_abi.IQ_PI_TAGS)); `out` may supply the buffers.  No synchronisation."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
@@ -1320,6 +1358,18 @@ class Engine:
         _req(critic_packed, "critic_packed", (ncpk,), f32, dv)
         _req(critic_param, "critic_param", (n_cpar,), f32, dv)
         _req(ws, "ws", (nws,), f32, dv)
+        hk = {}
+        if h is not None:
+            if not isinstance(h, dict) or set(h) != {"packed", "param", "colstats", "ws"}:
+                raise OlyError("iq_pi_update: h must be dict(packed, param, colstats, ws)")
+            _req(h["packed"], "h packed", (ncpk,), f32, dv)
+            _req(h["param"], "h param", (n_cpar,), f32, dv)
+            _req(h["colstats"], "h colstats", (3, D), f64, dv, optional=True)
+            _req(h["ws"], "h ws", (nws,), f32, dv)
+            if h["ws"].data_ptr() == ws.data_ptr() or h["packed"].data_ptr() == critic_packed.data_ptr():
+                raise OlyError("iq_pi_update: H needs a stream and a workspace of its own")
+            hk = dict(h_packed=h["packed"].data_ptr(), h_packed_floats=ncpk, h_param=h["param"].data_ptr(),
+                      h_colstats=ptr(h["colstats"]), h_ws=h["ws"].data_ptr(), h_ws_floats=nws)
         out = out or {}
         o = dict(action=self._out(out, "action", (B, A), f32), log_prob=self._out(out, "log_prob", (B,), f32),
                  out=self._out(out, "out", (4,), f64))
@@ -1331,7 +1381,7 @@ class Engine:
                       critic_packed=critic_packed.data_ptr(), critic_packed_floats=ncpk,
                       critic_param=critic_param.data_ptr(), critic_colstats=ptr(critic_colstats), ws=ws.data_ptr(),
                       ws_floats=nws, action=o["action"].data_ptr(), log_prob=o["log_prob"].data_ptr(),
-                      out=o["out"].data_ptr())
+                      out=o["out"].data_ptr(), **hk)
         self.ctx.call("oly_iq_pi_update", C.byref(f), self._s())
         return o
 

@@ -18,6 +18,11 @@ SQIL (imitation_lib/imitation/sqil_sac.py) and LSIQ (imitation_lib/imitation/lsi
                                                             algo "lsiq" and the block of LSIQ's own keywords; the
                                                             policy passes in the order of the loss type; DeviceLSIQSAC
                                                             adds DeviceIQSAC's policy side unchanged
+  LSIQ_H / LSIQ_HC's critic side: getV / get_targetV without the entropy, update_H_function, _update_all_targets
+  (lsiq_h.py:35-102, 110-126; lsiq_hc.py:23-100)         -> DeviceLSIQH / DeviceLSIQHC: DeviceLSIQ's call with alpha 0, then
+                                                            the H update's own policy pass (K25), for LSIQ_HC the two
+                                                            target-critic passes (oly_col_stats + K16), and ONE
+                                                            oly_iq_q_update call with algo "lsiq_h" on the second critic
 
   IQ_SAC.update_policy, _actor_loss, _update_alpha (:431-465, 587-595), iq_update (:408-419) and fit (:373-406) whole;
   SQIL.iq_update (sqil_sac.py:16-62)                     -> DeviceIQSAC / DeviceSQILSAC: update_policy is ONE
@@ -26,7 +31,9 @@ SQIL (imitation_lib/imitation/sqil_sac.py) and LSIQ (imitation_lib/imitation/lsi
                                                             one oly_iq_alpha_update call
 
 DeviceIQLearn and DeviceSQIL are the critic side alone and refuse learnable_alpha (the policy never moves there);
-DeviceIQSAC and DeviceSQILSAC are the whole agents; DeviceLSIQ and DeviceLSIQSAC are the same pair for LSIQ.  Not built, each refused by the constructors: the gradient penalty
+DeviceIQSAC and DeviceSQILSAC are the whole agents; DeviceLSIQ and DeviceLSIQSAC are the same pair for LSIQ; DeviceLSIQH
+and DeviceLSIQHC are the critic sides of LSIQ_H and LSIQ_HC, DeviceLSIQHSAC and DeviceLSIQHCSAC the whole agents, whose
+actor loss takes the sum of the two critics (K27 with its second critic).  Not built, each refused by the constructors: the gradient penalty
 (gradient_penalty_lambda > 0), plcy_loss_mode "v0" and gradient clipping of the actor.
 
 The cost of a learnable temperature: K25, K26 and K27 take alpha by value, so with learnable_alpha the `alpha` property
@@ -127,9 +134,23 @@ class DeviceSoftQCritic:
         return self.eng.ilmlp_forward(self._rows(obs, act), self.packed, 1, "identity", colstats=self._colstats(self.stand))
 
     @torch.no_grad()
-    def predict_target(self, obs, act):
-        return self.eng.ilmlp_forward(self._rows(obs, act), self.target_packed, 1, "identity",
-                                      colstats=self._colstats(self.target_stand))
+    def predict_target(self, obs, act, update_stats=False):
+        """Q_target(obs | act) [n, 1].  update_stats: the target's Standardizer takes the rows first, as the network's
+        forward does in the reference (oly_col_stats, then K16's forward with the statistics that hold them)."""
+        x, cs = self._rows(obs, act), self._colstats(self.target_stand)
+        if update_stats and cs is not None:
+            self.eng.col_stats(x, cs)
+            self.target_stand._fresh = False
+        return self.eng.ilmlp_forward(x, self.target_packed, 1, "identity", colstats=cs)
+
+    @torch.no_grad()
+    def soft_update_target(self):
+        """_update_target outside K26's call (a caller that passed update_target=False because something still had to
+        read the old target): K26's expression f32(tau) * w + f32(1 - tau) * t, two float32 products and one add, in
+        place, and the target's stream packed again; the bits are those of the in-call update."""
+        tau, omt = float(np.float32(self.tau)), float(np.float32(1.0 - self.tau))
+        self.target_param.copy_(self.param * tau + self.target_param * omt)
+        self.eng.ilmlp_pack(*self._views(self.target_param), packed=self.target_packed)
 
     @torch.no_grad()
     def sync_to_torch(self):
@@ -331,6 +352,14 @@ class DeviceIQLearn:
         """What the algorithm adds to iq_q_update's keywords."""
         return {}
 
+    def _q_alpha(self):
+        """The temperature in the critic's values V = Q - alpha log pi."""
+        return self.alpha
+
+    def _q_update_target(self):
+        """Whether the critic's call also makes its soft target update."""
+        return True
+
     def _workspace(self, B):
         if B not in self._ws:
             self._ws[B] = self.eng.iq_q_ws(B, self.in_dim, self.act_dim)
@@ -375,7 +404,8 @@ class DeviceIQLearn:
                                    c.exp_avg, c.exp_avg_sq, c.packed, c.target_param, c.target_packed, self._workspace(B),
                                    c.step, c.lr, algo=self.ALGO, plcy_loss_mode=self.plcy_loss_mode,
                                    regularizer_mode=self.regularizer_mode, treat_absorbing=self.treat_absorbing_states,
-                                   use_target=self.use_target, update_target=True, gamma=self.gamma, alpha=self.alpha,
+                                   use_target=self.use_target, update_target=self._q_update_target(), gamma=self.gamma,
+                                   alpha=self._q_alpha(),
                                    reg_mult=self.reg_mult, R_min=self.R_min, R_max=self.R_max, tau=c.tau,
                                    beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, weight_decay=c.weight_decay,
                                    **self._algo_block())
@@ -546,6 +576,140 @@ class DeviceLSIQ(DeviceIQLearn):
         return () if self.lossQ_type == "iq_like" else (3,)       # sqil_like never logs V
 
 
+class DeviceLSIQH(DeviceLSIQ):
+    """LSIQ_H's critic side (lsiq_h.py): LSIQ whose Q target carries no entropy (getV / get_targetV return Q(obs | a_pi):
+    DeviceLSIQ's call with alpha 0.0, which is Q - 0 * log_prob = Q bit for bit) and a second critic H that learns the
+    entropy by its own TD update, update_H_function, run after the Q critic has stepped.  h_critic (the reference's
+    H_params): a second DeviceSoftQCritic over the same in + A columns with its own optimiser and learning rate; its
+    `tau` is the agent's.  clip_expert_entropy_to_policy_max, max_H_policy_tau_down and max_H_policy_tau_up are the
+    reference's; the running maximum lives in the [2] device block h_max_state (the value, 1.0 once it is set) and is
+    never read back.  The H update's scalars (_abi.LSIQ_H_TAGS) are left in h_out and go to sw on a logging iteration."""
+
+    KIND = "lsiq_h_critic"
+    H_COST = False
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, h_critic=None,
+                 clip_expert_entropy_to_policy_max=True, max_H_policy_tau_down=1e-4, max_H_policy_tau_up=1e-2, **kw):
+        who = type(self).__name__
+        if not isinstance(h_critic, DeviceSoftQCritic):
+            raise OlyError(f"{who}: h_critic (the reference's H_params) must be a DeviceSoftQCritic")
+        if h_critic is critic:
+            raise OlyError(f"{who}: h_critic must be a network of its own, not the Q critic")
+        for name, t in (("max_H_policy_tau_down", max_H_policy_tau_down), ("max_H_policy_tau_up", max_H_policy_tau_up)):
+            if not 0.0 <= float(t) <= 1.0:
+                raise OlyError(f"{who}: {name}={t} outside [0, 1]")
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, **kw)
+        if int(h_critic.D) != int(critic.D):
+            raise OlyError(f"{who}: h_critic takes {h_critic.D} columns, the Q critic {critic.D}")
+        self.h_critic = h_critic
+        self.clip_expert_entropy_to_policy_max = bool(clip_expert_entropy_to_policy_max)
+        self.max_H_policy_tau_down, self.max_H_policy_tau_up = float(max_H_policy_tau_down), float(max_H_policy_tau_up)
+        self.h_max_state = torch.zeros(2, dtype=torch.float32, device=engine.device)
+        self.h_out = None
+
+    def _q_alpha(self):
+        return 0.0
+
+    def _h_loss(self):
+        return "MSE"
+
+    def _h_tau(self):
+        return self.h_critic.tau
+
+    @torch.no_grad()
+    def update_Q_function(self, obs, act, next_obs, absorbing, n_policy, eps=None, generator=None):
+        """LSIQ's update_Q_function with the entropy-free values, then update_H_function on the same batch and the target
+        updates.  eps: DeviceLSIQ's dict with, in addition, `h_next` [B,A] (the H update's policy pass on next_obs) and,
+        for LSIQ_HC, `h_pi` [B,A] (get_targetV's pass on obs).  Returns the Q critic's [16] block; the H update's is
+        h_out."""
+        out = super().update_Q_function(obs, act, next_obs, absorbing, n_policy, eps=eps, generator=generator)
+        self.h_out = self.update_H_function(obs, act, next_obs, absorbing, n_policy, eps=eps, generator=generator)
+        return out
+
+    @torch.no_grad()
+    def update_H_function(self, obs, act, next_obs, absorbing, n_policy, eps=None, generator=None):
+        """update_H_function and the target updates still due, in the reference's order: a NEW
+        compute_action_and_log_prob_t(next_obs) (it feeds the policy's Standardizer and draws noise); for LSIQ_HC
+        Q_target(obs | act), then get_targetV(obs) = a policy pass on obs and Q_target(obs | a_pi), the target critic's
+        Standardizer taking the rows of both; then one oly_iq_q_update with algo "lsiq_h" on h_critic, which also makes
+        H's soft target update; for LSIQ_HC last the Q critic's soft target update, deferred to here because the H
+        update reads the target from before it."""
+        f32 = torch.float32
+        obs, next_obs = obs.to(f32).contiguous(), next_obs.to(f32).contiguous()
+        act, absorbing = act.to(f32).contiguous(), absorbing.to(f32).reshape(-1).contiguous()
+        B, eps = int(obs.shape[0]), eps or {}
+        h, c = self.h_critic, self.critic
+        # the H call below shares the Q call's workspace: both run in order on the engine's stream and oly_iq_q_ws does
+        # not depend on the algorithm; calls that could overlap would need a workspace each
+        a_next, lp_next = self._policy_pass(next_obs, eps.get("h_next"), generator)
+        q_t = v_t = None
+        if self.H_COST:
+            q_t = c.predict_target(obs, act, update_stats=True).reshape(-1)
+            a_pi = self._policy_pass(obs, eps.get("h_pi"), generator, want_log_prob=False)[0]
+            v_t = c.predict_target(obs, a_pi, update_stats=True).reshape(-1)
+        block = dict(self._algo_block()["lsiq"],
+                     h=dict(loss=self._h_loss(), cost=self.H_COST, clip_expert=self.clip_expert_entropy_to_policy_max,
+                            tau_up=self.max_H_policy_tau_up, tau_down=self.max_H_policy_tau_down,
+                            max_state=self.h_max_state if self.clip_expert_entropy_to_policy_max else None, q_t=q_t, v_t=v_t))
+        out = self.eng.iq_q_update(obs, act, next_obs, absorbing, a_next, lp_next, None, None, int(n_policy),
+                                   h._colstats(h.stand), h._colstats(h.target_stand), h.param, h.exp_avg, h.exp_avg_sq,
+                                   h.packed, h.target_param, h.target_packed, self._workspace(B), h.step, h.lr,
+                                   algo="lsiq_h", use_target=True, update_target=True, gamma=self.gamma, alpha=self.alpha,
+                                   reg_mult=self.reg_mult, tau=self._h_tau(), beta1=h.betas[0], beta2=h.betas[1], eps=h.eps,
+                                   weight_decay=h.weight_decay, lsiq=block)
+        h.step += 1
+        if h.stand is not None:
+            h.stand._fresh = h.target_stand._fresh = False
+        if not self._q_update_target():
+            c.soft_update_target()
+        if self._iter % self.logging_iter == 0 and self.sw is not None:
+            host = out.cpu().numpy()
+            for k in range(7):                       # the reference's seven scalars, lsiq_h.py:94-100
+                self.sw.add_scalar(_abi.LSIQ_H_TAGS[k], float(host[k]), self._iter)
+        return out
+
+    def state_dict(self):
+        d = super().state_dict()
+        d.update(h_critic=self.h_critic.state_dict(), h_max_state=self.h_max_state.clone())
+        return d
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        super().load_state_dict(d)
+        self.h_critic.load_state_dict(d["h_critic"])
+        self.h_max_state.copy_(d["h_max_state"])
+
+
+class DeviceLSIQHC(DeviceLSIQH):
+    """LSIQ_HC's critic side (lsiq_hc.py): LSIQ_H whose H target adds the squared regularised reward of the target Q
+    critic, read BEFORE this iteration's soft update of it (so the Q critic's call runs with update_target=False and
+    the update follows the H update), with the MSE or Huber loss (H_loss_mode) and H's own target rate H_tau."""
+
+    KIND = "lsiq_hc_critic"
+    H_COST = True
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, H_tau=None,
+                 H_loss_mode="Huber", **kw):
+        who = type(self).__name__
+        if H_tau is None or not 0.0 <= float(H_tau) <= 1.0:
+            raise OlyError(f"{who}: H_tau={H_tau} must be given, in [0, 1]")
+        if H_loss_mode not in _abi.LSIQ_H_LOSSES:
+            raise OlyError(f"{who}: Unsupported H_loss {H_loss_mode!r} (one of {list(_abi.LSIQ_H_LOSSES)})")
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, **kw)
+        if not self.reg_mult > 0.0:
+            raise OlyError(f"{who}: reg_mult={self.reg_mult} must be positive (the reward is clipped at 1 / reg_mult)")
+        self.H_tau, self.H_loss_mode = float(H_tau), H_loss_mode
+
+    def _q_update_target(self):
+        return False
+
+    def _h_loss(self):
+        return self.H_loss_mode
+
+    def _h_tau(self):
+        return self.H_tau
+
+
 class _PolicySide:
     """What DeviceIQSAC and DeviceSQILSAC add to their critic-side parents: update_policy, _update_alpha, iq_update, fit."""
 
@@ -576,7 +740,7 @@ class _PolicySide:
         self.alpha_state = torch.tensor([np.float32(np.log(init_alpha)), 0.0, 0.0], dtype=torch.float32, device=dev)
         self.alpha_step = 0
         self._alpha_read = True          # log_alpha (the host copy) is current
-        self._pi_ws = {}
+        self._pi_ws, self._pi_h_ws = {}, {}
 
     @property
     def alpha(self):
@@ -589,6 +753,16 @@ class _PolicySide:
         if B not in self._pi_ws:
             self._pi_ws[B] = self.eng.iq_pi_ws(B, self.in_dim, self.act_dim)
         return self._pi_ws[B]
+
+    def _actor_h(self, Bp):
+        """The second critic of the actor loss (LSIQ_H / LSIQ_HC: mean(alpha log_prob - (q + H))) as iq_pi_update's `h`,
+        with a workspace of its own per batch size; None for the agents with one critic."""
+        h = getattr(self, "h_critic", None)
+        if h is None:
+            return None
+        if Bp not in self._pi_h_ws:
+            self._pi_h_ws[Bp] = self.eng.iq_pi_ws(Bp, self.in_dim, self.act_dim)
+        return dict(packed=h.packed, param=h.param, colstats=h._colstats(h.stand), ws=self._pi_h_ws[Bp])
 
     def get_e_lb(self):
         """IQ_Learn_Policy.get_e_lb in its linear mode (iq_sac.py:169-171): a host number from policy.iter."""
@@ -612,12 +786,14 @@ class _PolicySide:
         x = obs[:n_policy].contiguous() if self.train_policy_only_on_own_states else obs
         Bp = int(x.shape[0])
         noise = p._noise(Bp, eps.get("pi"), generator).contiguous()
-        cs, ccs = p._colstats(), c._colstats(c.stand)
+        cs, ccs, hk = p._colstats(), c._colstats(c.stand), self._actor_h(Bp)
         o = self.eng.iq_pi_update(x, noise, p.central, p.delta, cs, p.param, self.pi_exp_avg, self.pi_exp_avg_sq, p.packed,
                                   c.packed, c.param, ccs, self._pi_workspace(Bp), self.pi_step, self.pi_lr,
                                   alpha=self.alpha, log_std_min=p.log_std_min, log_std_max=p.log_std_max,
                                   beta1=self.pi_betas[0], beta2=self.pi_betas[1], adam_eps=self.pi_eps,
-                                  weight_decay=self.pi_weight_decay)
+                                  weight_decay=self.pi_weight_decay, h=hk)
+        if hk is not None and hk["colstats"] is not None:
+            self.h_critic.stand._fresh = False
         self.pi_step += 1
         if cs is not None:
             p.stand._fresh = False
@@ -745,5 +921,35 @@ class DeviceLSIQSAC(_PolicySide, DeviceLSIQ):
                                learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
 
 
-__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceIQSAC",
-           "DeviceSQILSAC", "DeviceLSIQSAC"]
+class DeviceLSIQHSAC(_PolicySide, DeviceLSIQH):
+    """LSIQ_H whole (lsiq_h.py): DeviceLSIQH's critic side with DeviceIQSAC's policy side, whose actor loss takes the sum
+    of the two live critics, mean(alpha log_prob - (Q + H)) (_actor_loss, :104-108): update_policy hands h_critic to
+    oly_iq_pi_update, which also feeds H's Standardizer the policy update's rows."""
+
+    KIND = "lsiq_h_sac"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
+                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
+                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
+                         learnable_alpha=False, **kw)
+        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
+                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
+
+
+class DeviceLSIQHCSAC(_PolicySide, DeviceLSIQHC):
+    """LSIQ_HC whole (lsiq_hc.py): DeviceLSIQHC's critic side with DeviceLSIQHSAC's policy side."""
+
+    KIND = "lsiq_hc_sac"
+
+    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
+                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
+                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
+        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
+                         learnable_alpha=False, **kw)
+        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
+                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
+
+
+__all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceLSIQH",
+           "DeviceLSIQHC", "DeviceIQSAC", "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC"]
