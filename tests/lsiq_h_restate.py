@@ -99,6 +99,7 @@ class HCritic(LSIQSoftQ):
             e = neg_log_pi[is_expert].detach().double().numpy()
             m["exp_clipped"], m["exp_free"] = int((e < float(bound)).sum()), int((e > float(bound)).sum())
             m["exp_margin"] = float(np.abs(e - float(bound)).min())
+            m["exp_side"] = e < float(bound)        # row by row, for runs compared between two precisions (iq_big_shapes)
             neg_log_pi[is_expert] = torch.clip(neg_log_pi[is_expert], bound, 100000)
         with torch.no_grad():
             next_H = self.forward(np.concatenate([next_obs, a_next], 1), target=True) + alpha * torch.unsqueeze(neg_log_pi, 1)
@@ -112,6 +113,8 @@ class HCritic(LSIQSoftQ):
                 Q2_max = (1.0 / c.reg_mult) ** 2 / (1 - gamma)
                 lo, hi = -1000, float(Q2_max + 100)
                 if self.check:
+                    x, side = (Q_plcy - y).double().numpy(), lambda v, a, b: (v > b).astype(np.int8) - (v < a).astype(np.int8)
+                    m["cost_side"] = (side(x, -1 / c.reg_mult, 1 / c.reg_mult), side(x, c.q_min, c.q_max))   # of this run's y
                     qd, vd, r = Q_plcy.double().reshape(-1).numpy(), V_plcy.double().reshape(-1).numpy(), 1 / c.reg_mult
                     d0 = qd - c.gamma * np.clip(vd, c.q_min, c.q_max)
                     side = lambda v, a, b: (int(((v < a) | (v > b)).sum()), int(((v >= a) & (v <= b)).sum()))
@@ -148,7 +151,8 @@ class HCritic(LSIQSoftQ):
                          above=int((rw.max(axis=-1) > hi).sum()), inside=int((rw.max(axis=-1) <= hi).sum()),
                          huber=c.loss == "Huber", huber_margin=float(np.abs(np.abs(res) - 1.0).min()),
                          quadratic=int((np.abs(res) < 1.0).sum()), linear=int((np.abs(res) >= 1.0).sum()),
-                         abs_policy=int(ab[:n_policy].sum()), abs_expert=int(ab[n_policy:].sum()))
+                         abs_policy=int(ab[:n_policy].sum()), abs_expert=int(ab[n_policy:].sum()),
+                         target_side=(rw > hi).astype(np.int8) - (rw < lo).astype(np.int8), huber_side=np.abs(res) < 1.0)
                 self.margins.append(m)
         return out
 

@@ -197,7 +197,10 @@ class LSIQSoftQ(SoftQ):
                     below=int((nv < c.q_min).sum()), inside=int(((nv >= c.q_min) & (nv <= c.q_max)).sum()),
                     above=int((nv > c.q_max).sum()),
                     huber_margin=float(np.abs(np.abs(h) - 1.0).min()) if len(h) else np.inf,
-                    quadratic=int((np.abs(h) < 1.0).sum()), linear=int((np.abs(h) >= 1.0).sum())))
+                    quadratic=int((np.abs(h) < 1.0).sum()), linear=int((np.abs(h) >= 1.0).sum()),
+                    # row by row, in the rows' order, for runs whose sides are compared between two precisions
+                    # (tests/iq_big_shapes.py): -1 below, 0 inside, 1 above the clip range; Huber's quadratic branch
+                    clip_side=(nv > c.q_max).astype(np.int8) - (nv < c.q_min).astype(np.int8), huber_side=np.abs(h) < 1.0))
         return out
 
 

@@ -151,8 +151,14 @@ def exact_inputs(in_dim, A, B, seed):
 
 @pytest.mark.parametrize("standardizer", (False, True), ids=("nostd", "std"))
 def test_q_values_have_the_forward_kernels_bits(eng, standardizer):
+    check_q_values_have_the_forward_kernels_bits(eng, (12, 5, 18, 9), standardizer)
+
+
+def check_q_values_have_the_forward_kernels_bits(eng, shape, standardizer):
+    """The raw outputs of the three passes in the workspace against oly_ilmlp_forward on the same rows with the statistics
+    the Standardizer holds at each pass (tests/test_gpu_iq_big_shapes.py runs it at a larger shape)."""
     from olympic_hip._ffi import lib
-    in_dim, A, B, n_policy = 12, 5, 18, 9
+    in_dim, A, B, n_policy = shape
     s, params = exact_inputs(in_dim, A, B, seed=3)
     for use_target in (True, False):
         cfg = R.Cfg(use_target=use_target, standardizer=standardizer)
