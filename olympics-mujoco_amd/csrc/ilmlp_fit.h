@@ -3,8 +3,8 @@
 // K26 (csrc/k26_iq_critic.hip, the soft-Q critic, relu) and K27 (csrc/k27_iq_policy.hip, the SAC family's policy update,
 // whose launch A is cut in two where the critic's statistics need every row's action).  Launch A ("rows") takes one 16-row tile per 512-thread
 // workgroup through the forward and the data gradients on the f32 matrix cores; launch B ("weights") takes one 16 x 16
-// weight tile per 256-thread workgroup through dW, Adam and the re-pack.  The loss, the output layer, the Standardizer's
-// accounting and the Adam stores are each kernel's own.  As in fit_common.h, the order of every addition is what the tests
+// weight tile per 256-thread workgroup through dW, Adam and the re-pack.  The loss, the Standardizer's accounting and what
+// a step stores beside the parameter (a target, the transposed streams) are each kernel's own.  As in fit_common.h, the order of every addition is what the tests
 // pin, and every function performs its users' float operations in their order.  These kernels' register allocation and
 // load scheduling turn on small things, so a kernel takes a function from here only where it then ran no longer than with
 // its own text (HIP events, 2048 rows); where one does not, the comment at the function says which and why.
@@ -122,6 +122,48 @@ __device__ __forceinline__ void dz1_tiles(const float* gz, const float4* w2t, H1
   }
 }
 
+// Stage the tile's 16 rows: value_at(m, k) of a row the pass takes (takes(m)) in columns k < D, with `standardise` through
+// the column's mean st[k] and std st[IN_MAX + k] in LDS, a row or column beyond them as zero, into the image xT and, with
+// `keep`, into the workspace's xs array (ws + W.xs) in row quads from row srow0, in the caller's index type (an int; a
+// size_t where slots make it one).  K24's and K26's rows kernels and K27's two call it.
+template <class Takes, class ValueAt, class Row>
+__device__ __forceinline__ void stage_rows(float* xT, int D, bool standardise, const double* st, Takes takes, ValueAt value_at,
+                                           bool keep, float* xs, Row srow0) {
+  for (int e = threadIdx.x; e < 16 * IN_MAX; e += RTHREADS) {
+    const int m = e / IN_MAX, k = e & (IN_MAX - 1);
+    float v = 0.f;
+    if (takes(m) && k < D) {
+      v = value_at(m, k);
+      // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
+      if (standardise) v = (float)(((double)v - st[k]) / st[IN_MAX + k]);
+    }
+    xT[act16_index(k, m)] = v;
+    if (keep) xs[((size_t)((srow0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
+  }
+}
+
+// The one-unit output layer by wave 0: one chain over k < 256 of the image hB against the packed section P + P_W3, as
+// the forward kernel's, plus the bias; row r's value to z[r] and qv[r].  K27's launch A2 calls it for each critic.  K26's
+// rows kernel keeps its own text of it: with this function it is allocated two to four registers fewer and scheduled for
+// one more wave per SIMD (which it never has), and its call ran 0.4 to 1.1 us longer at 512 rows without a target.
+__device__ __forceinline__ void output_unit(const float* hB, const float* P, float* z, float* qv) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (wave != 0) return;
+  f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
+  const float4* a4[1] = {reinterpret_cast<const float4*>(hB)};
+  tiles<H2 / 16, 1, 1>(a4, reinterpret_cast<const float4*>(P) + P_W3 / 4, 0, lane, acc);
+  if ((lane & 15) == 0) {
+    const int h4 = lane >> 4;
+    const float bv = P[P_B3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float q = acc[0][0][i] + bv;
+      z[4 * h4 + i] = q;
+      qv[4 * h4 + i] = q;
+    }
+  }
+}
+
 // ---- the prologue: W2T, the B operand of dH1 = dZ2 W2 (pt_index, N = 256 outputs), from param; grid PRO_BLOCKS x THREADS
 template <class A>
 __device__ __forceinline__ void build_w2t(const A& a) {
@@ -130,16 +172,46 @@ __device__ __forceinline__ void build_w2t(const A& a) {
 }
 
 // ---- launch B.  Tiles (n-tile x k-tile): W1 32 x ceil(in / 16), W2 16 x 32, W3 ceil(out / 16) x 16; the k-tile 0 of each
-// layer also steps the layer's bias.  The decode of the workgroup's (layer, n-tile, k-tile) and the layer's shapes stay in
-// each kernel: behind a function the compiler stops threading the three layers' branches through the loop below, and
-// launch B's code changes (it loses the 32 bytes of scratch it has had and its flat loads: a speed change).  So do the
-// per-layer Adam stores: with one indexed store behind a helper the layer's offsets are fetched after the barrier, and
-// launch B ran about 1 % longer.
+// layer also steps the layer's bias.  K26 and K27 take the decode, the step and the gradient-norm partial from here; K18
+// keeps its own text of all of launch B, K24 of the decode and the step (through them its step ran 0.5 to 0.8 % longer).
+// weight_tile returns its struct from a function on purpose: filled by a constructor instead, the three kernels lost the
+// 32 bytes of scratch they have had and launch B ran 8 us longer per 512 rows of a slot.
 __host__ __device__ inline int weight_tiles(int in_dim, int out_dim) {
   return 32 * ((in_dim + 15) / 16) + 512 + 16 * ((out_dim + 15) / 16);
 }
 
-// The tile's dW and the column sums of delta over this wave's share of the rows (K24 and K26; K18 keeps its own text of
+// The workgroup's tile: layer, n-tile nt and k-tile kt from blockIdx.x, the tile's first output n0 and input k0, and the
+// layer's delta dl [rows][dw] (N columns used) and activation al [rows][aw] (K columns used), both in row quads, from
+// the workspace layout's xs / h1 / h2 / dz1 / dz2 / dz3.  in_dim: the network's inputs; the output layer has out_dim
+// units in a delta of pitch out_pitch (K26: 1 and 1; K24 and K27: 2A and OUT_MAX).
+struct WeightTile {
+  int layer, nt, kt, n0, k0, dw, N, aw, K;
+  const float4 *dl, *al;
+};
+template <class A>
+__device__ __forceinline__ WeightTile weight_tile(const A& a, int in_dim, int out_dim, int out_pitch) {
+  WeightTile T;
+  const int kt0 = (in_dim + 15) / 16;
+  int t = blockIdx.x;
+  if (t < 32 * kt0) {
+    T.layer = 0, T.nt = t / kt0, T.kt = t % kt0;
+  } else if ((t -= 32 * kt0) < 512) {
+    T.layer = 1, T.nt = t / 32, T.kt = t % 32;
+  } else {
+    T.layer = 2, T.nt = (t - 512) / 16, T.kt = (t - 512) % 16;
+  }
+  const int layer = T.layer;
+  T.dw = layer == 0 ? H1 : layer == 1 ? H2 : out_pitch;
+  T.N = layer == 2 ? out_dim : T.dw;
+  T.aw = layer == 0 ? IN_MAX : layer == 1 ? H1 : H2;
+  T.K = layer == 0 ? in_dim : T.aw;
+  T.dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? a.W.dz1 : layer == 1 ? a.W.dz2 : a.W.dz3));
+  T.al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? a.W.xs : layer == 1 ? a.W.h1 : a.W.h2));
+  T.n0 = 16 * T.nt, T.k0 = 16 * T.kt;
+  return T;
+}
+
+// The tile's dW and the column sums of delta over this wave's share of the rows (K24, K26 and K27; K18 keeps its own text of
 // this loop and of meet_waves, with which its launch B ran 1 to 3 % shorter).  delta dl [rows][dw] (N columns used) and
 // activation al [rows][aw] (K columns used) are in row quads.  A step = the 16 rows of one tile of launch A (which wrote
 // all 16: zeros in the deltas beyond the minibatch); lane group h4 takes the step's row quad h4.  Wave w: steps
@@ -180,6 +252,62 @@ __device__ __forceinline__ void meet_waves(float* red, float* bred, const f32x4&
   for (int i = 0; i < 4; ++i) red[wave * 256 + (4 * h4 + i) * 16 + c] = acc[i];
   bred[wave * 64 + lane] = bsum;
   __syncthreads();
+}
+
+// The tile's step after meet_waves.  Thread (n = tid >> 4, k = tid & 15): the element's gradient g, the waves' four
+// partials in order, its flat parameter index i (layout a.P, in_dim columns in W1) and its packed index pk, handed to
+// step(layer, ne, ke, i, pk, g), which makes the Adam step and the caller's stores.  With the layer's k-tile 0, threads
+// < 16 the same for the bias of output n0 + tid (fit_common.h's bias_colsum; ke = -1).  g2, b2: the squares of the two
+// gradients in fp64, 0 where the thread has none.
+template <class A, class Step>
+__device__ __forceinline__ void tile_step(const WeightTile& T, const A& a, int in_dim, const float* red, const float* bred,
+                                          Step step, double& g2, double& b2) {
+  const int tid = threadIdx.x, ne = T.n0 + (tid >> 4), ke = T.k0 + (tid & 15);
+  g2 = b2 = 0.0;
+  if (ne < T.N && ke < T.K) {
+    const float g = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
+    g2 = (double)g * (double)g;
+    size_t i, pk;
+    if (T.layer == 0) i = a.P.w1 + (size_t)ne * in_dim + ke, pk = pk_index(P_W1, IN_MAX / 16, ne, ke);
+    else if (T.layer == 1) i = a.P.w2 + (size_t)ne * H1 + ke, pk = pk_index(P_W2, H1 / 16, ne, ke);
+    else i = a.P.w3 + (size_t)ne * H2 + ke, pk = pk_index(P_W3, H2 / 16, ne, ke);
+    step(T.layer, ne, ke, i, pk, g);
+  }
+  if (T.kt == 0 && tid < 16 && T.n0 + tid < T.N) {   // the bias: the column sums of delta, lane groups then waves in order
+    const float gb = oly_fit::bias_colsum(bred, tid);
+    b2 = (double)gb * (double)gb;
+    const size_t pb = (T.layer == 0 ? a.P.b1 : T.layer == 1 ? a.P.b2 : a.P.b3) + T.n0 + tid;
+    const size_t kb = (T.layer == 0 ? P_B1 : T.layer == 1 ? P_B2 : P_B3) + T.n0 + tid;
+    step(T.layer, T.n0 + tid, -1, pb, kb, gb);
+  }
+}
+
+// The sum of the workgroup's THREADS values v by a halving tree in dred [THREADS]; every thread calls it and gets the sum.
+__device__ __forceinline__ double tree_sum(double* dred, double v) {
+  const int tid = threadIdx.x;
+  dred[tid] = v;
+  __syncthreads();
+  for (int h = THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) dred[tid] += dred[tid + h];
+    __syncthreads();
+  }
+  return dred[0];
+}
+
+// The tile's sum of squared gradients (tile_step's g2 and b2) to its slot of gnp: the tree over the elements, then the 16
+// bias squares in order (bsq [16]).  Launch F's total of the `tiles` slots: thread t adds t, t + THREADS, ..., then the tree.
+__device__ __forceinline__ void gradnorm_partial(double* dred, double* bsq, double g2, double b2, double* gnp) {
+  if (threadIdx.x < 16) bsq[threadIdx.x] = b2;
+  double s = tree_sum(dred, g2);
+  if (threadIdx.x == 0) {
+    for (int j = 0; j < 16; ++j) s += bsq[j];
+    gnp[blockIdx.x] = s;
+  }
+}
+__device__ __forceinline__ double gradnorm_total(double* dred, const double* gnp, int tiles) {
+  double s = 0.0;
+  for (int t = threadIdx.x; t < tiles; t += THREADS) s += gnp[t];
+  return tree_sum(dred, s);
 }
 
 // ---- the host side: launch A for in_dim columns (<2> k-groups in layer 1 up to 32, else <4>), its dynamic LDS allowed on

@@ -23,8 +23,9 @@
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits, and a call of n steps
 // leaves the bits of n calls of one step (the prologue rebuilds from param exactly what launch B keeps current).
 // Adam, the statistics fold and the weights kernel's tail are fit_common.h's, shared with K15, K16 and K18; the two
-// launches' common phases (the Standardizer's head, the activation and its gradient, the row-quad stores, dZ1, the W2T
-// build, the dW chain, the waves' meeting, the rows kernel's dispatch) are ilmlp_fit.h's, shared with K18 and K26.
+// launches' common phases (the Standardizer's head, the rows' staging, the activation and its gradient, the row-quad
+// stores, dZ1, the W2T build, the dW chain, the waves' meeting, the halving tree, the rows kernel's dispatch) are
+// ilmlp_fit.h's, shared with K18, K26 and K27.
 //
 //   oly_bc_fit_steps_log  the same with the whole of logging() (:82-94): on a logging step, after launch B,
 //   L  K25's kernel (k25_sg_act.hip) on the rows idx[s] with the stepped stream and the statistics that hold them twice
@@ -150,17 +151,8 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
   }
   if (tid < 16) rows_x[tid] = row0 + tid < R ? row_at(a, a.off + row0 + tid) : -1;
   __syncthreads();
-  for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
-    const int m = e / IN_MAX, k = e & (IN_MAX - 1), row = rows_x[m];
-    float v = 0.f;
-    if (row >= 0 && k < in_dim) {
-      v = a.x[(size_t)row * in_dim + k];
-      // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
-      if (standardise) v = (float)(((double)v - st[k]) / st[IN_MAX + k]);
-    }
-    xT[act16_index(k, m)] = v;
-    ws[a.W.xs + ((size_t)((row0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
-  }
+  stage_rows(xT, in_dim, standardise, st, [&](int m) { return rows_x[m] >= 0; },
+             [&](int m, int k) { return a.x[(size_t)rows_x[m] * in_dim + k]; }, true, ws + a.W.xs, row0);
   __syncthreads();
   {  // ---- layer 1: [16, in] x [in, 512]
     f32x4 acc[1][4];
@@ -297,7 +289,9 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is (1 or 2) x 16).
+// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is (1 or 2) x 16).  The decode and the step keep their own text here,
+// which is ilmlp_fit.h's weight_tile and tile_step with the W2 / W3 mirrors in the step: through the two functions a step
+// of the fit ran 0.2 to 0.4 us (0.5 to 0.8 %) longer in each of three alternating runs at batch 32 and 256 (HIP events).
 constexpr double HALF_LOG_2PI_P1 = 0.5 + 0.5 * 1.8378770664093454835606594728112;   // 0.5 + 0.5 log(2 pi)
 __global__ __launch_bounds__(THREADS) void bc_weights_kernel(FitArgs a) {
   __shared__ float red[4 * 256];
@@ -390,13 +384,8 @@ __global__ __launch_bounds__(THREADS) void bc_log_fold_kernel(FitArgs a) {
   const float* lp = a.ws + a.W.total;
   double s = 0.0;
   for (int r = 16 * tid; r < min(R, 16 * tid + 16); ++r) s += (double)lp[r];
-  dred[tid] = s;
-  __syncthreads();
-  for (int h = THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) dred[tid] += dred[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) a.out[3] = -dred[0] / (double)R;      // "Squashed Gaussian Entropy (Empirical)"
+  const double sum = tree_sum(dred, s);
+  if (tid == 0) a.out[3] = -sum / (double)R;      // "Squashed Gaussian Entropy (Empirical)"
   if (a.colstats) oly_fit::colstats_add(a, R);
 }
 

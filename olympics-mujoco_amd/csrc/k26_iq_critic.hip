@@ -18,7 +18,8 @@
 //                          the backward of every pass that carries a gradient through the
 //                          relus from the stored outputs.  Activations and deltas go to the workspace in row quads, one
 //                          slot of BP rows per gradient pass; the tile's loss sums to fixed slots.
-//   B  iq_weights_kernel   the launch B of ilmlp_fit.h, as K24: one 16 x 16 weight tile per workgroup, dW summed over the slots' rows in a
+//   B  iq_weights_kernel   ilmlp_fit.h's launch B (weight_tile, dw_accumulate, meet_waves, tile_step, gradnorm_partial):
+//                          one 16 x 16 weight tile per workgroup, dW summed over the slots' rows in a
 //                          fixed order, weight decay, Adam, the stepped value into param, the moments and the packed
 //                          stream; with update_target the soft target update f32(tau) w + f32(1 - tau) t (two float32
 //                          products, one add) into target_param and its packed stream; the tile's sum of squared
@@ -33,7 +34,8 @@
 // and the running maximum of -log pi, launch A runs in instantiations of its own (iq_rows_kernel<G1, true>: the other
 // algorithms' code is compiled without the branch), and F commits the running maximum.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits.  The Standardizer's head, the
-// hidden layers, dZ1, the dW chain and the waves' meeting are ilmlp_fit.h's, shared with K18 and K24.
+// rows' staging, the hidden layers, dZ1, launch B's phases and the gradient norm's sums are ilmlp_fit.h's, shared with
+// K18, K24 and K27.
 #include <cstdlib>
 
 #include "ilmlp_fit.h"
@@ -242,6 +244,90 @@ __device__ __forceinline__ float h_row(const QArgs& a, size_t i, int expert, flo
   return (float)(((c0 != 0.0 ? c0 * g0 : 0.0) + (c1 != 0.0 ? c1 * g1 : 0.0)) / (n * n));
 }
 
+// The three loss families of the Q critic's row (e: 1 expert, 0 policy) from its Q, y = cy clip(next_v), V and absorbing
+// flag ab: the family's terms into t[] and, added to the caller's zeros, dL/d(reward) dr (on Q and, negated, on y),
+// dL/dQ beside it dq (LSIQ's fix losses see Q alone), dL/dV and dL/dy beside -dL/d(reward), all fp64.
+//
+// IQ's three terms (iq_sac.py:467-563) and LSIQ's iq_like (lsiq.py:51-128)
+__device__ __forceinline__ void iq_like_row(const QArgs& a, int e, float Q, float y, float ab, double* t, double& dr,
+                                            double& dq, double& dV, double& dy) {
+  const double n_all = (double)a.B, n_p = (double)a.n_policy, n_e = (double)(a.B - a.n_policy);
+  const double n_own = e ? n_e : n_p;
+  const float r = Q - y;
+  if (e) {
+    if (a.algo != OLY_IQ_ALGO_LSIQ || a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP) {
+      dr -= 1.0 / n_e;                                          // loss_term1 = -mean(reward[expert])
+    } else {                                                    // lsiq.py:56-60: Q[expert] against the constant Q_max
+      double g;
+      point_loss(a.exp_loss, Q - a.q_max, t[T_SQ], g);
+      dq = g / n_e;
+    }
+  }
+  const int md = a.loss_mode;          // LSIQ adds value_q_old_policy (both terms) and off (neither), lsiq.py:87-94
+  if (md == OLY_IQ_VALUE || md == OLY_LSIQ_VALUE_Q_OLD_POLICY) dV = 1.0 / n_all;
+  else if (md == OLY_IQ_VALUE_EXPERT) dV = e ? 1.0 / n_e : 0.0;
+  else if (md == OLY_IQ_VALUE_POLICY) dV = e ? 0.0 : 1.0 / n_p;
+  if ((md == OLY_IQ_Q_OLD_POLICY || md == OLY_LSIQ_VALUE_Q_OLD_POLICY) && !e)
+    dr += 1.0 / n_p;                                            // q_old_policy: mean(reward[~expert])
+  dy = -dV;
+  const double ra = a.treat_abs ? (double)ab : 0.0;
+  const double w = (1.0 - ra) * (double)a.reg_mult + ra * (1.0 - (double)a.gamma) * (double)a.reg_mult;
+  const bool in = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY || (a.reg_mode == OLY_IQ_REG_EXP && e) ||
+                  (a.reg_mode == OLY_IQ_REG_PLCY && !e);
+  if (in) {
+    const double nr = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY ? n_all : n_own;
+    dr += 2.0 * w * (double)r / nr;
+    t[T_CHI] = w * (double)r * (double)r;
+  }
+}
+
+// LSIQ's sqil_like (lsiq.py:130-178): no factor 0.5, no reg_mult multiplier, no chi2 term
+__device__ __forceinline__ void lsiq_sq_row(const QArgs& a, int e, float Q, float y, float V, float ab, double* t, double& dr,
+                                            double& dq, double& dV, double& dy) {
+  const double n_all = (double)a.B, n_p = (double)a.n_policy, n_e = (double)(a.B - a.n_policy);
+  // r_max = -r_min in float32, the reference's order: (1 - ab) (1 / reg_mult) + (ab (1 / (1 - gamma))) (1 / reg_mult)
+  const float rw = a.treat_abs ? (1.f - ab) * a.inv_rm + (ab * a.g1) * a.inv_rm : a.inv_rm;
+  double g;
+  if (e) {
+    const float d = a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP ? Q - (rw + y) : Q - a.q_max;   // :146-148, :153-155
+    point_loss(a.exp_loss, d, t[T_SQ], g);
+    if (a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP) dr += g / n_e;
+    else dq = g / n_e;
+  }
+  // mode value (:165): r_min[~expert] and then as many plain -1 / reg_mult, which land on the expert rows
+  const float rmin = e ? -a.inv_rm : -rw;
+  if (a.loss_mode == OLY_LSIQ_SQ_VALUE || (a.loss_mode == OLY_LSIQ_SQ_VALUE_PLCY && !e)) {
+    point_loss(a.exp_loss, V - (rmin + y), t[T_SV], g);         // :162-168, 173-176
+    dV = g / (a.loss_mode == OLY_LSIQ_SQ_VALUE ? n_all : n_p);
+    dy = -dV;
+  } else if (a.loss_mode == OLY_LSIQ_SQ_Q_OLD_POLICY && !e) {
+    point_loss(a.exp_loss, Q - (rmin + y), t[T_SV], g);         // :169-171
+    dr += g / n_p;
+  }
+}
+
+// SQIL's squared residuals against R_max (expert rows) and R_min (sqil_sac.py:64-92)
+__device__ __forceinline__ void sqil_row(const QArgs& a, int e, float Q, float y, float V, double* t, double& dr, double& dV,
+                                         double& dy) {
+  const double n_all = (double)a.B, n_p = (double)a.n_policy, n_e = (double)(a.B - a.n_policy);
+  const double rm = (double)a.reg_mult;
+  if (e) {
+    const float d = Q - (a.r_max + y);                          // sqil_sac.py:80
+    dr += rm * (double)d / n_e;
+    t[T_SQ] = (double)d * (double)d;
+  } else if (a.loss_mode == OLY_SQIL_PLCY) {
+    const float d = Q - (a.r_min + y);                          // :90
+    dr += rm * (double)d / n_p;
+    t[T_SQ] = (double)d * (double)d;
+  }
+  if (a.loss_mode == OLY_SQIL_VALUE || (a.loss_mode == OLY_SQIL_VALUE_PLCY && !e)) {
+    const float d = V - (a.r_min + y);                          // :85, :88
+    dV = rm * (double)d / (a.loss_mode == OLY_SQIL_VALUE ? n_all : n_p);
+    dy = -dV;
+    t[T_SV] = (double)d * (double)d;
+  }
+}
+
 template <int G1, bool HB = false>
 __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -305,33 +391,25 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
     const bool tgt = p == 1 && a.use_target;
     const bool standardise = tgt ? a.tcolstats != nullptr : a.colstats != nullptr;
     const float* P = tgt ? a.tpacked : a.packed;
-    const float4* P4 = reinterpret_cast<const float4*>(P);
     const int slot = a.slot[p];
     const size_t srow0 = (size_t)(slot < 0 ? 0 : slot) * BP + row0;
     const size_t quad = (srow0 >> 2) + h4;           // this lane's accumulator rows: 4 h4 + i = one row quad
-    const double* mean = st + (p * 2) * IN_MAX;
-    const double* sd = mean + IN_MAX;
-    for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
-      const int m = e / IN_MAX, k = e & (IN_MAX - 1);
-      float v = 0.f;
-      if (sub[m] >= 0 && k < D && (p < 2 || row0 + m < a.n_v)) {   // a row the pass does not take goes through as zeros
-        v = input_at(a, p, (size_t)(row0 + m), k);
-        // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
-        if (standardise) v = (float)(((double)v - mean[k]) / sd[k]);
-      }
-      xT[act16_index(k, m)] = v;
-      if (slot >= 0) ws[a.W.xs + (((srow0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
-    }
+    stage_rows(xT, D, standardise, st + (p * 2) * IN_MAX,      // a row the pass does not take goes through as zeros
+               [&](int m) { return sub[m] >= 0 && (p < 2 || row0 + m < a.n_v); },
+               [&](int m, int k) { return input_at(a, p, (size_t)(row0 + m), k); }, slot >= 0, ws + a.W.xs, srow0);
     __syncthreads();
     // ---- layer 1: [16, D] x [D, 512], layer 2: [16, 512] x [512, 256]; a pass without a gradient keeps no activations
     hidden_layer<Relu, G1, IN_MAX / 16, 4, P_W1, P_B1>(xT, P, hA, slot >= 0, ws4, a.W.h1, quad);
     __syncthreads();
     hidden_layer<Relu, H1 / 16, H1 / 16, 2, P_W2, P_B2>(hA, P, hB, slot >= 0, ws4, a.W.h2, quad);
     __syncthreads();
-    if (wave == 0) {  // ---- the output unit: one chain over k < 256, as the forward kernel
+    // ---- the output unit: ilmlp_fit.h's output_unit in its own text.  Through the function this kernel is allocated two
+    // to four registers fewer and scheduled for one more wave per SIMD (which a 512-thread workgroup with this much LDS
+    // never has), and the call ran 0.4 to 1.1 us longer at 512 rows without a target in each of three alternating runs.
+    if (wave == 0) {
       f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
       const float4* a4[1] = {reinterpret_cast<const float4*>(hB)};
-      tiles<H2 / 16, 1, 1>(a4, P4 + P_W3 / 4, 0, lane, acc);
+      tiles<H2 / 16, 1, 1>(a4, reinterpret_cast<const float4*>(P) + P_W3 / 4, 0, lane, acc);
       if (c == 0) {
         const float bv = P[P_B3];
 #pragma unroll
@@ -355,8 +433,6 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
       if (e >= 0) cQ = h_row(a, (size_t)row0 + tid, e, z[0][tid], z[1][tid], t);
     } else if (e >= 0) {
       const size_t i = (size_t)row0 + tid;
-      const double n_all = (double)B, n_p = (double)a.n_policy, n_e = (double)(B - a.n_policy);
-      const double n_own = e ? n_e : n_p;
       const float ab = a.absorbing[i];
       const float Q = z[0][tid];
       const float nv = z[1][tid] - a.alpha * a.logp_next[i];          // getV / get_targetV (:571-585)
@@ -380,70 +456,9 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
       t[T_VY] = vy;
       t[T_QABS] = ab != 0.f ? (double)Q : 0.0;
       t[T_ABS] = ab != 0.f ? 1.0 : 0.0;
-      if (a.iq_like) {
-        if (e) {
-          if (!lsiq || a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP) {
-            dr -= 1.0 / n_e;                                          // loss_term1 = -mean(reward[expert])
-          } else {                                                    // lsiq.py:56-60: Q[expert] against the constant Q_max
-            double g;
-            point_loss(a.exp_loss, Q - a.q_max, t[T_SQ], g);
-            dq = g / n_e;
-          }
-        }
-        const int md = a.loss_mode;          // LSIQ adds value_q_old_policy (both terms) and off (neither), lsiq.py:87-94
-        if (md == OLY_IQ_VALUE || md == OLY_LSIQ_VALUE_Q_OLD_POLICY) dV = 1.0 / n_all;
-        else if (md == OLY_IQ_VALUE_EXPERT) dV = e ? 1.0 / n_e : 0.0;
-        else if (md == OLY_IQ_VALUE_POLICY) dV = e ? 0.0 : 1.0 / n_p;
-        if ((md == OLY_IQ_Q_OLD_POLICY || md == OLY_LSIQ_VALUE_Q_OLD_POLICY) && !e)
-          dr += 1.0 / n_p;                                            // q_old_policy: mean(reward[~expert])
-        dy = -dV;
-        const double ra = a.treat_abs ? (double)ab : 0.0;
-        const double w = (1.0 - ra) * (double)a.reg_mult + ra * (1.0 - (double)a.gamma) * (double)a.reg_mult;
-        const bool in = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY || (a.reg_mode == OLY_IQ_REG_EXP && e) ||
-                        (a.reg_mode == OLY_IQ_REG_PLCY && !e);
-        if (in) {
-          const double n = a.reg_mode == OLY_IQ_REG_EXP_AND_PLCY ? n_all : n_own;
-          dr += 2.0 * w * (double)r / n;
-          t[T_CHI] = w * (double)r * (double)r;
-        }
-      } else if (lsiq) {           // sqil_like (lsiq.py:130-178): no factor 0.5, no reg_mult multiplier, no chi2 term
-        // r_max = -r_min in float32, the reference's order: (1 - ab) (1 / reg_mult) + (ab (1 / (1 - gamma))) (1 / reg_mult)
-        const float rw = a.treat_abs ? (1.f - ab) * a.inv_rm + (ab * a.g1) * a.inv_rm : a.inv_rm;
-        double g;
-        if (e) {
-          const float d = a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP ? Q - (rw + y) : Q - a.q_max;   // :146-148, :153-155
-          point_loss(a.exp_loss, d, t[T_SQ], g);
-          if (a.exp_mode == OLY_LSIQ_EXP_BOOTSTRAP) dr += g / n_e;
-          else dq = g / n_e;
-        }
-        // mode value (:165): r_min[~expert] and then as many plain -1 / reg_mult, which land on the expert rows
-        const float rmin = e ? -a.inv_rm : -rw;
-        if (a.loss_mode == OLY_LSIQ_SQ_VALUE || (a.loss_mode == OLY_LSIQ_SQ_VALUE_PLCY && !e)) {
-          point_loss(a.exp_loss, V - (rmin + y), t[T_SV], g);         // :162-168, 173-176
-          dV = g / (a.loss_mode == OLY_LSIQ_SQ_VALUE ? n_all : n_p);
-          dy = -dV;
-        } else if (a.loss_mode == OLY_LSIQ_SQ_Q_OLD_POLICY && !e) {
-          point_loss(a.exp_loss, Q - (rmin + y), t[T_SV], g);         // :169-171
-          dr += g / n_p;
-        }
-      } else {
-        const double rm = (double)a.reg_mult;
-        if (e) {
-          const float d = Q - (a.r_max + y);                          // sqil_sac.py:80
-          dr += rm * (double)d / n_e;
-          t[T_SQ] = (double)d * (double)d;
-        } else if (a.loss_mode == OLY_SQIL_PLCY) {
-          const float d = Q - (a.r_min + y);                          // :90
-          dr += rm * (double)d / n_p;
-          t[T_SQ] = (double)d * (double)d;
-        }
-        if (a.loss_mode == OLY_SQIL_VALUE || (a.loss_mode == OLY_SQIL_VALUE_PLCY && !e)) {
-          const float d = V - (a.r_min + y);                          // :85, :88
-          dV = rm * (double)d / (a.loss_mode == OLY_SQIL_VALUE ? n_all : n_p);
-          dy = -dV;
-          t[T_SV] = (double)d * (double)d;
-        }
-      }
+      if (a.iq_like) iq_like_row(a, e, Q, y, ab, t, dr, dq, dV, dy);
+      else if (lsiq) lsiq_sq_row(a, e, Q, y, V, ab, t, dr, dq, dV, dy);
+      else sqil_row(a, e, Q, y, V, t, dr, dV, dy);
       cQ = (float)(dr + dq);
       cV = (float)dV;
       // y = cy clip(next_v) carries a gradient without a target, where the clip lets it through
@@ -508,67 +523,19 @@ __global__ __launch_bounds__(THREADS) void iq_weights_kernel(QArgs a) {
   __shared__ float bred[4 * 64];
   __shared__ double dred[THREADS];
   __shared__ double bsq[16];
-  const int tid = threadIdx.x;
-  const WsL& W = a.W;
-  const ParamLayout& PL = a.P;
-  const int kt0 = (a.D + 15) / 16;
-  int t = blockIdx.x, layer, nt, kt;
-  if (t < 32 * kt0) {
-    layer = 0, nt = t / kt0, kt = t % kt0;
-  } else if ((t -= 32 * kt0) < 512) {
-    layer = 1, nt = t / 32, kt = t % 32;
-  } else {
-    layer = 2, nt = 0, kt = t - 512;
-  }
-  // delta [R][dw] (N columns used) and activation [R][aw] (K columns used) of the layer, both in row quads
-  const int dw = layer == 0 ? H1 : layer == 1 ? H2 : 1;
-  const int N = dw;
-  const int aw = layer == 0 ? IN_MAX : layer == 1 ? H1 : H2;
-  const int K = layer == 0 ? a.D : aw;
-  const float4* dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.dz1 : layer == 1 ? W.dz2 : W.dz3));
-  const float4* al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.xs : layer == 1 ? W.h1 : W.h2));
-  const int n0 = 16 * nt, k0 = 16 * kt;
+  const WeightTile T = weight_tile(a, a.D, 1, 1);
   // the steps run over the rows of every slot
   f32x4 acc;
   float bsum;
-  dw_accumulate(dl, al, dw, aw, n0, N, k0, K, a.n_slots * ((a.B + 15) / 16), acc, bsum);
+  dw_accumulate(T.dl, T.al, T.dw, T.aw, T.n0, T.N, T.k0, T.K, a.n_slots * ((a.B + 15) / 16), acc, bsum);
   meet_waves(red, bred, acc, bsum);
-  {
-    const int nn = tid >> 4, kk = tid & 15, ne = n0 + nn, ke = k0 + kk;
-    double g2 = 0.0;
-    if (ne < N && ke < K) {
-      const float g = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
-      g2 = (double)g * (double)g;
-      size_t i, pk;
-      if (layer == 0) i = PL.w1 + (size_t)ne * a.D + ke, pk = pk_index(P_W1, IN_MAX / 16, ne, ke);
-      else if (layer == 1) i = PL.w2 + (size_t)ne * H1 + ke, pk = pk_index(P_W2, H1 / 16, ne, ke);
-      else i = PL.w3 + ke, pk = pk_index(P_W3, H2 / 16, 0, ke);
-      const float p = adam1(a, i, g);
-      a.packed[pk] = p;
-      step_target(a, i, pk, p);
-    }
-    dred[tid] = g2;
-    if (tid < 16) bsq[tid] = 0.0;
-    if (kt == 0 && tid < 16 && n0 + tid < N) {   // the bias: the column sums of delta, lane groups then waves in order
-      const float gb = oly_fit::bias_colsum(bred, tid);
-      bsq[tid] = (double)gb * (double)gb;
-      const size_t pb = (layer == 0 ? PL.b1 : layer == 1 ? PL.b2 : PL.b3) + n0 + tid;
-      const size_t kb = (layer == 0 ? P_B1 : layer == 1 ? P_B2 : P_B3) + n0 + tid;
-      const float p = adam1(a, pb, gb);
-      a.packed[kb] = p;
-      step_target(a, pb, kb, p);
-    }
-  }
-  __syncthreads();
-  for (int h = THREADS / 2; h > 0; h >>= 1) {     // the tile's sum of squared gradients: a halving tree, then the biases
-    if (tid < h) dred[tid] += dred[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    double s = dred[0];
-    for (int j = 0; j < 16; ++j) s += bsq[j];
-    reinterpret_cast<double*>(a.ws + W.gnp)[blockIdx.x] = s;
-  }
+  double g2, b2;
+  tile_step(T, a, a.D, red, bred, [&](int, int, int, size_t i, size_t pk, float g) {
+    const float p = adam1(a, i, g);
+    a.packed[pk] = p;
+    step_target(a, i, pk, p);
+  }, g2, b2);
+  gradnorm_partial(dred, bsq, g2, b2, reinterpret_cast<double*>(a.ws + a.W.gnp));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -585,17 +552,7 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
     for (int t = 0; t < tiles_a; ++t) s += lp[(size_t)t * 2 * NTERM + tid];
     S[tid] = s;
   }
-  {
-    const double* gp = reinterpret_cast<const double*>(a.ws + a.W.gnp);
-    double s = 0.0;
-    for (int t = tid; t < tiles_b; t += THREADS) s += gp[t];
-    dred[tid] = s;
-  }
-  __syncthreads();
-  for (int h = THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) dred[tid] += dred[tid + h];
-    __syncthreads();
-  }
+  const double gn2 = gradnorm_total(dred, reinterpret_cast<const double*>(a.ws + a.W.gnp), tiles_b);
   if (tid == 0) {
     const double* Sp = S;            // policy rows
     const double* Se = S + NTERM;    // expert rows
@@ -612,7 +569,7 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
       o[4] = (Sp[T_R] + Se[T_R]) / n_all;
       o[5] = Sp[T_R] / n_p;
       o[6] = Se[T_R] / n_e;
-      o[7] = sqrt(dred[0]);
+      o[7] = sqrt(gn2);
       o[8] = a.h_clip ? (double)M : 0.0;
       if (a.h_clip) {
         a.h_max[0] = M;
@@ -652,7 +609,7 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
       o[12] = Sp[T_Y] / n_p;
       o[13] = Se[T_QABS] / Se[T_ABS];      // 0 / 0 = NaN for an empty subset, as torch.mean of nothing
       o[14] = Sp[T_QABS] / Sp[T_ABS];
-      o[15] = sqrt(dred[0]);
+      o[15] = sqrt(gn2);
     }
     for (int j = 0; j < 16; ++j) a.out[j] = o[j];
   }

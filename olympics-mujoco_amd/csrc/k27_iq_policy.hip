@@ -20,7 +20,8 @@
 //                             parameters do not step: dZ2 = f32(-1 / Bp) W3 [h2 > 0], dZ1 on the matrix cores over the
 //                             transposed stream, dX on the action columns divided by the column's std), the chain through
 //                             the squash and the sample in fp64 per element narrowed once, then K24's policy backward.
-//   B   iqpi_weights_kernel   the launch B of ilmlp_fit.h over the policy's weights, as K24: dW, weight decay, Adam, the
+//   B   iqpi_weights_kernel   ilmlp_fit.h's launch B (weight_tile, dw_accumulate, meet_waves, tile_step,
+//                             gradnorm_partial) over the policy's weights: dW, weight decay, Adam, the
 //                             stepped value into param, the moments and the packed stream; the tile's sum of squared
 //                             gradients to a fixed slot.
 //   F   iqpi_fold_kernel      one workgroup: the four scalars, the critic's Standardizer += the rows.
@@ -164,17 +165,8 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_act_kernel(PiArgs a) {
     st[IN_MAX + tid] = sd;
   }
   __syncthreads();
-  for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
-    const int m = e / IN_MAX, k = e & (IN_MAX - 1);
-    float v = 0.f;
-    if (m < rows && k < in_dim) {
-      v = a.x[(size_t)(row0 + m) * in_dim + k];
-      // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
-      if (standardise) v = (float)(((double)v - st[k]) / st[IN_MAX + k]);
-    }
-    xT[act16_index(k, m)] = v;
-    ws[a.W.xs + ((size_t)((row0 + m) >> 2) * IN_MAX + k) * 4 + (m & 3)] = v;
-  }
+  stage_rows(xT, in_dim, standardise, st, [&](int m) { return m < rows; },
+             [&](int m, int k) { return a.x[(size_t)(row0 + m) * in_dim + k]; }, true, ws + a.W.xs, row0);
   __syncthreads();
   hidden_layer<Relu, G1, IN_MAX / 16, 4, P_W1, P_B1>(xT, P, hA, true, ws4, a.W.h1, quad);
   __syncthreads();
@@ -264,11 +256,9 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
 #pragma unroll
   for (int net = 0; net < (HB ? 2 : 1); ++net) {   // the critic, then (HB) H: the same rows, each net's own statistics
   const float* CPk = net ? a.hpacked : a.cpacked;
-  const float4* CP4 = reinterpret_cast<const float4*>(CPk);
   const float* cparam = net ? a.hparam : a.cparam;
   const double* ccol = net ? a.hcolstats : a.ccolstats;
   const float* nws = net ? a.hws : ws;             // where P left this net's cw2t and cw1a
-  float* zo = net ? zh : zq;
   const bool standardise = ccol != nullptr;
   if (tid < D) {   // Standardizer.update_mean_std with all Bp rows of (x | a_new) (networks.py:76-81): the tiles' slots in order
     const double* cp = reinterpret_cast<const double*>(ws + a.W.cpart);
@@ -288,36 +278,18 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
     st[IN_MAX + tid] = sd;
   }
   __syncthreads();
-  for (int e = tid; e < 16 * IN_MAX; e += RTHREADS) {
-    const int m = e / IN_MAX, k = e & (IN_MAX - 1);
-    float v = 0.f;
-    if (m < rows && k < D) {
-      const size_t row = (size_t)row0 + m;
-      v = k < in_dim ? a.x[row * in_dim + k] : a.action[row * A + (k - in_dim)];
-      if (standardise) v = (float)(((double)v - st[k]) / st[IN_MAX + k]);
-    }
-    xT[act16_index(k, m)] = v;
-  }
+  stage_rows(xT, D, standardise, st, [&](int m) { return m < rows; },
+             [&](int m, int k) {
+               const size_t row = (size_t)row0 + m;
+               return k < in_dim ? a.x[row * in_dim + k] : a.action[row * A + (k - in_dim)];
+             }, false, nullptr, 0);
   __syncthreads();
   // ---- the critic's forward: no activations kept (its parameters do not step)
   hidden_layer<Relu, GC, IN_MAX / 16, 4, P_W1, P_B1>(xT, CPk, hA, false, ws4, 0, quad);
   __syncthreads();
   hidden_layer<Relu, H1 / 16, H1 / 16, 2, P_W2, P_B2>(hA, CPk, hB, false, ws4, 0, quad);
   __syncthreads();
-  if (wave == 0) {  // ---- the output unit: one chain over k < 256, as the forward kernel
-    f32x4 acc[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
-    const float4* a4[1] = {reinterpret_cast<const float4*>(hB)};
-    tiles<H2 / 16, 1, 1>(a4, CP4 + P_W3 / 4, 0, lane, acc);
-    if (c == 0) {
-      const float bv = CPk[P_B3];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float q = acc[0][0][i] + bv;
-        zo[4 * h4 + i] = q;
-        (net ? a.hws : ws)[a.W.qv + row0 + 4 * h4 + i] = q;
-      }
-    }
-  }
+  output_unit(hB, CPk, net ? zh : zq, (net ? a.hws : ws) + a.W.qv + row0);
   {  // ---- the critic's dZ2 = (f32(-1 / Bp) W3) [h2 > 0], zero beyond the batch
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -426,67 +398,21 @@ __global__ __launch_bounds__(RTHREADS) void iqpi_grad_kernel(PiArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is (1 or 2) x 16), K24's with K26's gradient-norm partials.
+// Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is (1 or 2) x 16): ilmlp_fit.h's phases, the step Adam and the re-pack.
 __global__ __launch_bounds__(THREADS) void iqpi_weights_kernel(PiArgs a) {
   __shared__ float red[4 * 256];
   __shared__ float bred[4 * 64];
   __shared__ double dred[THREADS];
   __shared__ double bsq[16];
-  const int tid = threadIdx.x;
-  const WsL& W = a.W;
-  const ParamLayout& PL = a.P;
-  const int kt0 = (a.in_dim + 15) / 16;
-  int t = blockIdx.x, layer, nt, kt;
-  if (t < 32 * kt0) {
-    layer = 0, nt = t / kt0, kt = t % kt0;
-  } else if ((t -= 32 * kt0) < 512) {
-    layer = 1, nt = t / 32, kt = t % 32;
-  } else {
-    layer = 2, nt = (t - 512) / 16, kt = (t - 512) % 16;
-  }
-  const int dw = layer == 0 ? H1 : layer == 1 ? H2 : OUTP;
-  const int N = layer == 2 ? a.out_dim : dw;
-  const int aw = layer == 0 ? IN_MAX : layer == 1 ? H1 : H2;
-  const int K = layer == 0 ? a.in_dim : aw;
-  const float4* dl = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.dz1 : layer == 1 ? W.dz2 : W.dz3));
-  const float4* al = reinterpret_cast<const float4*>(a.ws + (layer == 0 ? W.xs : layer == 1 ? W.h1 : W.h2));
-  const int n0 = 16 * nt, k0 = 16 * kt;
+  const WeightTile T = weight_tile(a, a.in_dim, a.out_dim, OUTP);
   f32x4 acc;
   float bsum;
-  dw_accumulate(dl, al, dw, aw, n0, N, k0, K, (a.B + 15) / 16, acc, bsum);
+  dw_accumulate(T.dl, T.al, T.dw, T.aw, T.n0, T.N, T.k0, T.K, (a.B + 15) / 16, acc, bsum);
   meet_waves(red, bred, acc, bsum);
-  {
-    const int nn = tid >> 4, kk = tid & 15, ne = n0 + nn, ke = k0 + kk;
-    double g2 = 0.0;
-    if (ne < N && ke < K) {
-      const float g = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
-      g2 = (double)g * (double)g;
-      size_t i, pk;
-      if (layer == 0) i = PL.w1 + (size_t)ne * a.in_dim + ke, pk = pk_index(P_W1, IN_MAX / 16, ne, ke);
-      else if (layer == 1) i = PL.w2 + (size_t)ne * H1 + ke, pk = pk_index(P_W2, H1 / 16, ne, ke);
-      else i = PL.w3 + (size_t)ne * H2 + ke, pk = pk_index(P_W3, H2 / 16, ne, ke);
-      a.packed[pk] = adam1(a, i, g);
-    }
-    dred[tid] = g2;
-    if (tid < 16) bsq[tid] = 0.0;
-    if (kt == 0 && tid < 16 && n0 + tid < N) {   // the bias: the column sums of delta, lane groups then waves in order
-      const float gb = oly_fit::bias_colsum(bred, tid);
-      bsq[tid] = (double)gb * (double)gb;
-      const size_t pb = (layer == 0 ? PL.b1 : layer == 1 ? PL.b2 : PL.b3) + n0 + tid;
-      const size_t kb = (layer == 0 ? P_B1 : layer == 1 ? P_B2 : P_B3) + n0 + tid;
-      a.packed[kb] = adam1(a, pb, gb);
-    }
-  }
-  __syncthreads();
-  for (int h = THREADS / 2; h > 0; h >>= 1) {     // the tile's sum of squared gradients: a halving tree, then the biases
-    if (tid < h) dred[tid] += dred[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    double s = dred[0];
-    for (int j = 0; j < 16; ++j) s += bsq[j];
-    reinterpret_cast<double*>(a.ws + W.gnp)[blockIdx.x] = s;
-  }
+  double g2, b2;
+  tile_step(T, a, a.in_dim, red, bred, [&](int, int, int, size_t i, size_t pk, float g) { a.packed[pk] = adam1(a, i, g); },
+            g2, b2);
+  gradnorm_partial(dred, bsq, g2, b2, reinterpret_cast<double*>(a.ws + a.W.gnp));
 }
 
 // Launch F: one workgroup.  Thread j < 3 adds loss partial j of the tiles in order; thread t adds the gradient-norm
@@ -502,21 +428,11 @@ __global__ __launch_bounds__(THREADS) void iqpi_fold_kernel(PiArgs a, int tiles_
     for (int t = 0; t < tiles_a; ++t) s += lp[(size_t)t * 4 + tid];
     S[tid] = s;
   }
-  {
-    const double* gp = reinterpret_cast<const double*>(a.ws + a.W.gnp);
-    double s = 0.0;
-    for (int t = tid; t < tiles_b; t += THREADS) s += gp[t];
-    dred[tid] = s;
-  }
-  __syncthreads();
-  for (int h = THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) dred[tid] += dred[tid + h];
-    __syncthreads();
-  }
+  const double gn2 = gradnorm_total(dred, reinterpret_cast<const double*>(a.ws + a.W.gnp), tiles_b);
   if (tid == 0) {
     const double n = (double)a.B;
     a.out[0] = S[0] / n;           // Actor/Loss
-    a.out[1] = sqrt(dred[0]);      // the gradient's 2-norm
+    a.out[1] = sqrt(gn2);          // the gradient's 2-norm
     a.out[2] = S[1] / n;           // mean(log_prob)
     a.out[3] = S[2] / n;           // mean(Q), with H mean(Q + H)
   }
@@ -547,15 +463,10 @@ __global__ __launch_bounds__(THREADS) void iq_alpha_kernel(AlphaArgs a) {
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int i = tid; i < a.n; i += THREADS) s += (double)a.log_prob[i] + (double)a.target_entropy;
-  dred[tid] = s;
-  __syncthreads();
-  for (int h = THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) dred[tid] += dred[tid + h];
-    __syncthreads();
-  }
+  const double sum = tree_sum(dred, s);
   if (tid == 0) {
     float p = a.state[0], m = a.state[1], v = a.state[2];
-    const float g = (float)(-exp((double)p) * (dred[0] / (double)a.n));
+    const float g = (float)(-exp((double)p) * (sum / (double)a.n));
     const oly_fit::AdamK& k = a.ad;     // adam1's order (fit_common.h), no weight decay
     m = m + (g - m) * k.w1;
     v = v * k.beta2 + (k.w2 * g) * g;

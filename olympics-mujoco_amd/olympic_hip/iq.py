@@ -379,13 +379,10 @@ class DeviceIQLearn:
         (the noise is drawn from `generator` pass by pass) or a dict with `next` [B,A], `pi` [B,A] and, on a logging
         iteration, `expert` [B - n_policy, A].  Returns the [16] f64 device block of _abi.IQ_Q_TAGS; on a logging
         iteration the scalars also go to sw (which reads them back)."""
-        f32 = torch.float32
-        obs, next_obs = obs.to(f32).contiguous(), next_obs.to(f32).contiguous()
-        act, absorbing = act.to(f32).contiguous(), absorbing.to(f32).reshape(-1).contiguous()
-        B, n_policy = int(obs.shape[0]), int(n_policy)
-        eps = eps or {}
+        batch = obs, act, next_obs, absorbing = self._batch(obs, act, next_obs, absorbing)
+        n_policy, eps = int(n_policy), eps or {}
         logging = self._iter % self.logging_iter == 0
-        c, p = self.critic, self.policy
+        c = self.critic
         a_next, lp_next = self._policy_pass(next_obs, eps.get("next"), generator)
         a_pi = lp_pi = a_exp = None
 
@@ -399,23 +396,35 @@ class DeviceIQLearn:
         if logging and not before:
             a_exp = expert_pass()
         w_norm = torch.linalg.vector_norm(c.param.double()) if logging and self.sw is not None else None
-        cs, tcs = c._colstats(c.stand), c._colstats(c.target_stand)
-        out = self.eng.iq_q_update(obs, act, next_obs, absorbing, a_next, lp_next, a_pi, lp_pi, n_policy, cs, tcs, c.param,
-                                   c.exp_avg, c.exp_avg_sq, c.packed, c.target_param, c.target_packed, self._workspace(B),
-                                   c.step, c.lr, algo=self.ALGO, plcy_loss_mode=self.plcy_loss_mode,
-                                   regularizer_mode=self.regularizer_mode, treat_absorbing=self.treat_absorbing_states,
-                                   use_target=self.use_target, update_target=self._q_update_target(), gamma=self.gamma,
-                                   alpha=self._q_alpha(),
-                                   reg_mult=self.reg_mult, R_min=self.R_min, R_max=self.R_max, tau=c.tau,
-                                   beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, weight_decay=c.weight_decay,
-                                   **self._algo_block())
-        c.step += 1
-        if c.stand is not None:
-            c.stand._fresh = False
-            if self.use_target:
-                c.target_stand._fresh = False
+        out = self._net_update(c, batch, a_next, lp_next, a_pi, lp_pi, n_policy, self.use_target, algo=self.ALGO,
+                               plcy_loss_mode=self.plcy_loss_mode, regularizer_mode=self.regularizer_mode,
+                               treat_absorbing=self.treat_absorbing_states, update_target=self._q_update_target(),
+                               alpha=self._q_alpha(), R_min=self.R_min, R_max=self.R_max, tau=c.tau, **self._algo_block())
         if logging and self.sw is not None:
             self._log(out, act, a_exp, n_policy, w_norm)
+        return out
+
+    @staticmethod
+    def _batch(obs, act, next_obs, absorbing):
+        """A batch's four blocks as contiguous float32, absorbing flat."""
+        f32 = torch.float32
+        return (obs.to(f32).contiguous(), act.to(f32).contiguous(), next_obs.to(f32).contiguous(),
+                absorbing.to(f32).reshape(-1).contiguous())
+
+    def _net_update(self, net, batch, a_next, lp_next, a_pi, lp_pi, n_policy, use_target, **kw):
+        """One oly_iq_q_update on `net`, a DeviceSoftQCritic: its two Standardizers' sums, parameters, Adam moments, streams,
+        target, step count and optimiser are the call's network arguments; kw: the algorithm's.  Afterwards the
+        network's bookkeeping: one more step, and the Standardizers that took rows are no longer fresh."""
+        out = self.eng.iq_q_update(*batch, a_next, lp_next, a_pi, lp_pi, n_policy, net._colstats(net.stand),
+                                   net._colstats(net.target_stand), net.param, net.exp_avg, net.exp_avg_sq, net.packed,
+                                   net.target_param, net.target_packed, self._workspace(int(batch[0].shape[0])), net.step,
+                                   net.lr, use_target=use_target, gamma=self.gamma, reg_mult=self.reg_mult,
+                                   beta1=net.betas[0], beta2=net.betas[1], eps=net.eps, weight_decay=net.weight_decay, **kw)
+        net.step += 1
+        if net.stand is not None:
+            net.stand._fresh = False
+            if use_target:
+                net.target_stand._fresh = False
         return out
 
     def _log(self, out, act, a_exp, n_policy, w_norm):
@@ -450,11 +459,11 @@ class DeviceIQLearn:
         return torch.topk(keys, n, largest=False, sorted=True).indices
 
     @torch.no_grad()
-    def fit_Q(self, dataset, generator=None):
-        """IQ_SAC.fit (:373-406) with iq_update's critic part: the dataset goes into the replay memory; once that is
-        initialised, n_fits times a policy minibatch from it and as many demonstration rows make one batch for
-        update_Q_function (every delay_Q iterations).  Then _iter and policy.iter advance.  Returns the last update's
-        scalars, or None."""
+    def _fit(self, dataset, generator, step):
+        """IQ_SAC.fit's loop (:373-406): the dataset goes into the replay memory; once that is initialised, n_fits times a
+        policy minibatch from it and as many demonstration rows are drawn and step(batch, n_policy) runs, batch() making
+        the one batch (obs, act, next_obs, absorbing) of both.  Then _iter and policy.iter advance.  Returns what the
+        last step returned that was not None, or None."""
         self.replay.add(dataset)
         out = None
         if self.replay.initialized:
@@ -462,13 +471,21 @@ class DeviceIQLearn:
                 s, a, _r, ns, ab, _l = self.replay.get(self.batch_size, generator)
                 idx = self.draw_demo_idx(int(s.shape[0]), generator)
                 d = self.demo
-                if self._iter % self.delay_Q == 0:
-                    out = self.update_Q_function(torch.cat([s, d["states"][idx]]), torch.cat([a, d["actions"][idx]]),
-                                                 torch.cat([ns, d["next_states"][idx]]),
-                                                 torch.cat([ab, d["absorbing"][idx]]), int(s.shape[0]), generator=generator)
+                res = step(lambda: (torch.cat([s, d["states"][idx]]), torch.cat([a, d["actions"][idx]]),
+                                    torch.cat([ns, d["next_states"][idx]]), torch.cat([ab, d["absorbing"][idx]])),
+                           int(s.shape[0]))
+                out = out if res is None else res
         self._iter += 1
         self.policy.iter = getattr(self.policy, "iter", 0) + 1
         return out
+
+    def fit_Q(self, dataset, generator=None):
+        """IQ_SAC.fit with iq_update's critic part: update_Q_function on every delay_Q-th iteration's batches.  Returns
+        the last update's scalars, or None."""
+        def step(batch, n_policy):
+            if self._iter % self.delay_Q == 0:
+                return self.update_Q_function(*batch(), n_policy, generator=generator)
+        return self._fit(dataset, generator, step)
 
     # ---- checkpoint (il_checkpoint.save / load take this object as the agent)
     KIND = "iq_learn_critic"
@@ -634,11 +651,8 @@ class DeviceLSIQH(DeviceLSIQ):
         Standardizer taking the rows of both; then one oly_iq_q_update with algo "lsiq_h" on h_critic, which also makes
         H's soft target update; for LSIQ_HC last the Q critic's soft target update, deferred to here because the H
         update reads the target from before it."""
-        f32 = torch.float32
-        obs, next_obs = obs.to(f32).contiguous(), next_obs.to(f32).contiguous()
-        act, absorbing = act.to(f32).contiguous(), absorbing.to(f32).reshape(-1).contiguous()
-        B, eps = int(obs.shape[0]), eps or {}
-        h, c = self.h_critic, self.critic
+        batch = obs, act, next_obs, absorbing = self._batch(obs, act, next_obs, absorbing)
+        h, c, eps = self.h_critic, self.critic, eps or {}
         # the H call below shares the Q call's workspace: both run in order on the engine's stream and oly_iq_q_ws does
         # not depend on the algorithm; calls that could overlap would need a workspace each
         a_next, lp_next = self._policy_pass(next_obs, eps.get("h_next"), generator)
@@ -651,15 +665,8 @@ class DeviceLSIQH(DeviceLSIQ):
                      h=dict(loss=self._h_loss(), cost=self.H_COST, clip_expert=self.clip_expert_entropy_to_policy_max,
                             tau_up=self.max_H_policy_tau_up, tau_down=self.max_H_policy_tau_down,
                             max_state=self.h_max_state if self.clip_expert_entropy_to_policy_max else None, q_t=q_t, v_t=v_t))
-        out = self.eng.iq_q_update(obs, act, next_obs, absorbing, a_next, lp_next, None, None, int(n_policy),
-                                   h._colstats(h.stand), h._colstats(h.target_stand), h.param, h.exp_avg, h.exp_avg_sq,
-                                   h.packed, h.target_param, h.target_packed, self._workspace(B), h.step, h.lr,
-                                   algo="lsiq_h", use_target=True, update_target=True, gamma=self.gamma, alpha=self.alpha,
-                                   reg_mult=self.reg_mult, tau=self._h_tau(), beta1=h.betas[0], beta2=h.betas[1], eps=h.eps,
-                                   weight_decay=h.weight_decay, lsiq=block)
-        h.step += 1
-        if h.stand is not None:
-            h.stand._fresh = h.target_stand._fresh = False
+        out = self._net_update(h, batch, a_next, lp_next, None, None, int(n_policy), True, algo="lsiq_h", update_target=True,
+                               alpha=self.alpha, tau=self._h_tau(), lsiq=block)
         if not self._q_update_target():
             c.soft_update_target()
         if self._iter % self.logging_iter == 0 and self.sw is not None:
@@ -711,10 +718,17 @@ class DeviceLSIQHC(DeviceLSIQH):
 
 
 class _PolicySide:
-    """What DeviceIQSAC and DeviceSQILSAC add to their critic-side parents: update_policy, _update_alpha, iq_update, fit."""
+    """What the whole agents add to their critic-side parents: update_policy, _update_alpha, iq_update, fit.  The
+    constructor takes the parent's arguments and actor_optimizer: dict(lr, betas, eps, weight_decay) of torch.optim.Adam
+    (a `clipping` entry is refused); warmup_transitions, delay_pi, train_policy_only_on_own_states, learnable_alpha,
+    lr_alpha and target_entropy (None: -A) as the reference's; e_thres / e_reduc: the policy's entropy lower bound
+    (linear mode), logged only.  The policy's Adam moments and step count and the [3] device block (log_alpha, exp_avg,
+    exp_avg_sq) live here."""
 
-    def _init_policy_side(self, actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
-                          learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc):
+    def __init__(self, *args, actor_optimizer=None, warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False,
+                 learnable_alpha=False, lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5,
+                 **kw):
+        super().__init__(*args, init_alpha=init_alpha, learnable_alpha=False, **kw)
         who = type(self).__name__
         opt = dict(actor_optimizer or {})
         if "clipping" in opt:
@@ -836,24 +850,9 @@ class _PolicySide:
             out_pi = self.update_policy(obs, n_policy, eps=eps.get("pi"), generator=generator)
         return out_q, out_pi
 
-    @torch.no_grad()
     def fit(self, dataset, generator=None):
-        """IQ_SAC.fit (:373-406): the dataset goes into the replay memory; once that is initialised, n_fits times a
-        policy minibatch from it and as many demonstration rows make one batch for iq_update.  Then _iter and
-        policy.iter advance.  Returns the last iq_update's pair, or None."""
-        self.replay.add(dataset)
-        out = None
-        if self.replay.initialized:
-            for _ in range(self.n_fits):
-                s, a, _r, ns, ab, _l = self.replay.get(self.batch_size, generator)
-                idx = self.draw_demo_idx(int(s.shape[0]), generator)
-                d = self.demo
-                out = self.iq_update(torch.cat([s, d["states"][idx]]), torch.cat([a, d["actions"][idx]]),
-                                     torch.cat([ns, d["next_states"][idx]]), torch.cat([ab, d["absorbing"][idx]]),
-                                     int(s.shape[0]), generator=generator)
-        self._iter += 1
-        self.policy.iter = getattr(self.policy, "iter", 0) + 1
-        return out
+        """IQ_SAC.fit (:373-406): DeviceIQLearn._fit's loop around iq_update.  Returns the last iq_update's pair, or None."""
+        return self._fit(dataset, generator, lambda batch, n_policy: self.iq_update(*batch(), n_policy, generator=generator))
 
     def state_dict(self):
         d = super().state_dict()
@@ -875,21 +874,9 @@ class _PolicySide:
 
 class DeviceIQSAC(_PolicySide, DeviceIQLearn):
     """IQ_SAC whole (iq_sac.py:256-420, 431-465, 587-595): DeviceIQLearn's critic side with the policy and the
-    temperature trained on the device (K27).  actor_optimizer: dict(lr, betas, eps, weight_decay) of
-    torch.optim.Adam (a `clipping` entry is refused); warmup_transitions, delay_pi, train_policy_only_on_own_states,
-    learnable_alpha, lr_alpha and target_entropy (None: -A) as the reference's.  e_thres / e_reduc: the policy's entropy
-    lower bound (linear mode), logged only.  The policy's Adam moments and step count and the [3] device block
-    (log_alpha, exp_avg, exp_avg_sq) live here."""
+    temperature trained on the device (K27)."""
 
     KIND = "iq_sac"
-
-    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
-                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
-                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
-        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
-                         learnable_alpha=False, **kw)
-        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
-                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
 
 
 class DeviceSQILSAC(_PolicySide, DeviceSQIL):
@@ -897,28 +884,12 @@ class DeviceSQILSAC(_PolicySide, DeviceSQIL):
 
     KIND = "sqil_sac"
 
-    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
-                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
-                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
-        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
-                         learnable_alpha=False, **kw)
-        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
-                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
-
 
 class DeviceLSIQSAC(_PolicySide, DeviceLSIQ):
     """LSIQ whole (lsiq.py: an IQ_SAC that overrides _lossQ alone): DeviceLSIQ's critic side with DeviceIQSAC's policy
     side."""
 
     KIND = "lsiq_sac"
-
-    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
-                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
-                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
-        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
-                         learnable_alpha=False, **kw)
-        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
-                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
 
 
 class DeviceLSIQHSAC(_PolicySide, DeviceLSIQH):
@@ -928,27 +899,11 @@ class DeviceLSIQHSAC(_PolicySide, DeviceLSIQH):
 
     KIND = "lsiq_h_sac"
 
-    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
-                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
-                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
-        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
-                         learnable_alpha=False, **kw)
-        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
-                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
-
 
 class DeviceLSIQHCSAC(_PolicySide, DeviceLSIQHC):
     """LSIQ_HC whole (lsiq_hc.py): DeviceLSIQHC's critic side with DeviceLSIQHSAC's policy side."""
 
     KIND = "lsiq_hc_sac"
-
-    def __init__(self, engine, policy, critic, demonstrations, gamma, batch_size, use_target, actor_optimizer=None,
-                 warmup_transitions=0, delay_pi=1, train_policy_only_on_own_states=False, learnable_alpha=False,
-                 lr_alpha=3e-4, target_entropy=None, init_alpha=1e-3, e_thres=2.0, e_reduc=1e-5, **kw):
-        super().__init__(engine, policy, critic, demonstrations, gamma, batch_size, use_target, init_alpha=init_alpha,
-                         learnable_alpha=False, **kw)
-        self._init_policy_side(actor_optimizer, warmup_transitions, delay_pi, train_policy_only_on_own_states,
-                               learnable_alpha, lr_alpha, target_entropy, init_alpha, e_thres, e_reduc)
 
 
 __all__ = ["DeviceSoftQCritic", "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceLSIQH",
