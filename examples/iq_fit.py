@@ -7,6 +7,7 @@ transitions (olympic_hip.synthetic, as examples/iq_q_fit.py): DeviceIQSAC.fit ru
 policy that is trained does not collect them.
 
     python examples/iq_fit.py --algo iq|sqil|lsiq [--learnable-alpha] [--log] [--updates 200] [--batch 32] [--json FILE]
+    python examples/iq_fit.py --algo iqfo|lsiqfo|lsiqfo_h|lsiqfo_hc [--am-lr] [--am-batch] [--am-fits-per-step] [--interpolate C]
     python examples/iq_fit.py --algo lsiq_h|lsiq_hc --q-exp-loss MSE [--h-loss-mode MSE|Huber] [--h-tau 0.005]
         (LSIQ_H / LSIQ_HC, lsiq_h.py / lsiq_hc.py: a second critic H learns the entropy, the actor follows Q + H)
     python examples/iq_fit.py --algo lsiq --q-exp-loss MSE|Huber [--lossq-type iq_like|sqil_like]
@@ -37,7 +38,13 @@ class PrintingWriter:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq", "lsiq_h", "lsiq_hc"), default="iq")
+    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq", "lsiq_h", "lsiq_hc", "iqfo", "lsiqfo", "lsiqfo_h", "lsiqfo_hc"),
+                    default="iq", help="the *fo agents learn from (s, s') alone: an inverse action model draws the expert's actions")
+    ap.add_argument("--am-lr", type=float, default=1e-4, help="*fo: the action model's Adam learning rate")
+    ap.add_argument("--am-batch", type=int, default=64, help="*fo: rows of one action-model fit")
+    ap.add_argument("--am-fits-per-step", type=int, default=1, help="*fo: action-model fits per iteration")
+    ap.add_argument("--interpolate", type=float, default=None, metavar="C",
+                    help="*fo: interpolate_expert_states with interpolation_coef C")
     ap.add_argument("--h-loss-mode", choices=("MSE", "Huber"), default="Huber", help="lsiq_hc: H_loss_mode")
     ap.add_argument("--h-tau", type=float, default=0.005, help="lsiq_hc: H_tau, the H target's own rate")
     ap.add_argument("--lossq-type", choices=("iq_like", "sqil_like"), default="iq_like", help="lsiq: lossQ_type")
@@ -71,16 +78,30 @@ def main():
               warmup_transitions=1024, learnable_alpha=args.learnable_alpha, lr_alpha=3e-4, init_alpha=0.1)
     if args.plcy_loss_mode is not None:
         kw["plcy_loss_mode"] = args.plcy_loss_mode
-    if args.algo in ("lsiq_h", "lsiq_hc"):      # the second critic: the same shape, its own optimiser
+    fo = args.algo.endswith("fo") or "fo_" in args.algo
+    base = args.algo.replace("fo", "")
+    if base in ("lsiq_h", "lsiq_hc"):      # the second critic: the same shape, its own optimiser
         h_lins = [torch.nn.Linear(D + A, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
         kw["h_critic"] = DeviceSoftQCritic(eng, h_lins, standardizer=DeviceStandardizer(eng, D + A), lr=3e-4, tau=0.005)
-        if args.algo == "lsiq_hc":
+        if base == "lsiq_hc":
             kw.update(H_tau=args.h_tau, H_loss_mode=args.h_loss_mode)
-    if args.algo.startswith("lsiq"):
+    if base.startswith("lsiq"):
         kw.update(lossQ_type=args.lossq_type, loss_mode_exp=args.loss_mode_exp, Q_exp_loss=args.q_exp_loss, Q_min=args.q_min,
                   Q_max=args.q_max, target_clipping=not args.no_target_clipping)
-    agent = dict(iq=DeviceIQSAC, sqil=DeviceSQILSAC, lsiq=DeviceLSIQSAC, lsiq_h=DeviceLSIQHSAC,
-                 lsiq_hc=DeviceLSIQHCSAC)[args.algo](eng, policy, critic, demo, **kw)
+    classes = dict(iq=DeviceIQSAC, sqil=DeviceSQILSAC, lsiq=DeviceLSIQSAC, lsiq_h=DeviceLSIQHSAC, lsiq_hc=DeviceLSIQHCSAC)
+    if fo:      # the demonstrations lose their actions; the model on (s | s') draws them
+        from olympic_hip import iqfo
+        classes = dict(iq=iqfo.DeviceIQfOSAC, lsiq=iqfo.DeviceLSIQfOSAC, lsiq_h=iqfo.DeviceLSIQfOHSAC,
+                       lsiq_hc=iqfo.DeviceLSIQfOHCSAC)
+        demo = {k: v for k, v in demo.items() if k != "actions"}
+        a_lins = [torch.nn.Linear(2 * D, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 2 * A)]
+        kw["action_model"] = iqfo.DeviceGaussianInvActionModel(eng, a_lins, -np.ones(A), np.ones(A), args.am_lr,
+                                                               batch_size=args.am_batch,
+                                                               standardizer=DeviceStandardizer(eng, 2 * D))
+        kw["action_model_fit_params"] = dict(fits_per_step=args.am_fits_per_step, init_epochs=0)
+        if args.interpolate is not None:
+            kw.update(interpolate_expert_states=True, interpolation_coef=args.interpolate)
+    agent = classes[base](eng, policy, critic, demo, **kw)
     w0 = policy.param.clone()
     first_pi = last_q = last_pi = None
     for u in range(args.updates):

@@ -30,8 +30,16 @@
 //   oly_bc_fit_steps_log  the same with the whole of logging() (:82-94): on a logging step, after launch B,
 //   L  K25's kernel (k25_sg_act.hip) on the rows idx[s] with the stepped stream and the statistics that hold them twice
 //   F  bc_log_fold_kernel  -mean(log_prob) into the step's fourth scalar; colstats += minibatch s a second time.
+//
+// With oly_bc_fit.pair (K28: the inverse action model's fit on a replay ring) the rows are (states[i, :d1] | x2[i, :d2])
+// of two indexed tables and the target is un-squashed from the ring's raw actions in launch A.  The prologue and launch A
+// are then the instantiations of the templates below over PairFitArgs (bc_fit.h), launch B is k28_iam.hip's kernel and
+// launch L K25's over oly_sg::PairArgs; a call without a pair runs the FitArgs instantiations and bc_weights_kernel,
+// which compile to the code they had.
 #include <cstdlib>
+#include <type_traits>
 
+#include "bc_fit.h"
 #include "ilmlp_fit.h"
 #include "oly_common.h"
 #include "sg_act.h"
@@ -41,66 +49,21 @@ using namespace oly_ilfit;
 using oly_fit::adam1;
 using oly_fit::row_at;
 using oly_fit::stats_slice;
-static_assert(IN_MAX == oly_fit::MAX_IN, "fit_common.h's statistics arrays have this file's pitch");
-
-constexpr int MAX_BATCH = OLY_BC_MAX_BATCH;   // loss_tree folds at most THREADS = 256 tiles of 16 rows
-constexpr int MAX_ACT = OLY_BC_MAX_ACT;
-constexpr int OUTP = OUT_MAX;                 // pitch of the output layer's delta: two column tiles
-static_assert(MAX_BATCH <= 16 * THREADS && 2 * MAX_ACT <= OUTP, "one loss partial per thread; 2A output columns");
-
-// workspace (floats), BP = batch rounded up to 16 rows; [BP][W] arrays in row quads, element (row, col) at
-// ((row / 4) W + col) 4 + row % 4:
-//   xs [BP][64] standardised rows | h1 [BP][512] | h2 [BP][256] | dZ1 [BP][512] | dZ2 [BP][256] | dZ3 [BP][32] |
-//   loss partials [2][BP / 16][2] f64 ((nll, sum log_sigma), (squared error, 0)) | statistics partials [NSP][2][64] f64 |
-//   the minibatch's column sums [2][64] f64 | the transposed streams W2T, W3T
-struct WsL {
-  size_t xs, h1, h2, dz1, dz2, dz3, lossp, statp, delta, w2t, w3t, total;
-};
-__host__ __device__ inline WsL ws_layout(int batch) {
-  const size_t BP = (size_t)(batch + 15) / 16 * 16;
-  WsL W;
-  W.xs = 0;
-  W.h1 = W.xs + BP * IN_MAX;
-  W.h2 = W.h1 + BP * H1;
-  W.dz1 = W.h2 + BP * H2;
-  W.dz2 = W.dz1 + BP * H1;
-  W.dz3 = W.dz2 + BP * H2;
-  W.lossp = W.dz3 + BP * OUTP;
-  W.statp = W.lossp + BP / 16 * 8;
-  W.delta = W.statp + (size_t)NSP * 2 * IN_MAX * 2;
-  W.w2t = W.delta + 2 * IN_MAX * 2;
-  W.w3t = W.w2t + (size_t)H2 * H1;
-  W.total = W.w3t + (size_t)OUTP * H2;
-  return W;
-}
-
-// W2T / W3T are the B operands of the data gradients dH1 = dZ2 W2 (N = 256 outputs) and dH2 = dZ3 W3 (N = 32, rows
-// n >= 2A zero) in pt_index's layout (fit_common.h)
-struct FitArgs {
-  int in_dim, n_rows, act_dim, out_dim;
-  int ds, d2, std2, stride2;   // fit_common.h's two-source members: one source here (ds = in_dim, no x2)
-  const float* x2;
-  int R, Rn;                   // rows of step s / s+1 (0: none)
-  long off, off_next;          // first position of step s / s+1 in perm
-  const int32_t* perm;         // idx [n_steps, batch]
-  const float *x, *targets;
-  double* colstats;            // or NULL: the rows go in as they are
-  float *param, *m, *v, *packed, *ws;
-  float ls_min, ls_max, nll_eps;
-  oly_fit::AdamK ad;
-  float wd;                    // weight_decay
-  double* out;                 // + 3 s
-  ParamLayout P;
-  WsL W;
-};
+using namespace oly_bc;
 
 // grid PRO_BLOCKS: the transposed streams from param (grid-stride) and, workgroups 0 .. NSP-1, step 0's partials
-__global__ __launch_bounds__(THREADS) void bc_prologue_kernel(FitArgs a) {
+template <class KA>
+__global__ __launch_bounds__(THREADS) void bc_prologue_kernel(KA a) {
   __shared__ double part[8 * IN_MAX];
   build_w2t(a);
   for (int e = blockIdx.x * THREADS + threadIdx.x; e < OUTP * H2; e += PRO_BLOCKS * THREADS)
     a.ws[a.W.w3t + pt_index(OUTP, e / H2, e % H2)] = e / H2 < a.out_dim ? a.param[a.P.w3 + e] : 0.f;
-  if (a.colstats && blockIdx.x < NSP) stats_slice(a, a.off, a.R, blockIdx.x, part);
+  if (a.colstats && blockIdx.x < NSP) {
+    if constexpr (PAIRED<KA>)
+      pair_stats_slice(a, a.off, a.R, blockIdx.x, part);
+    else
+      stats_slice(a, a.off, a.R, blockIdx.x, part);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -112,8 +75,8 @@ constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16 + 2 * OUT
 constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (2 * IN_MAX + 3 * 256 + 48);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
 
-template <int G1>
-__global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
+template <int G1, class KA>
+__global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(KA a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xT = lds;                       // [64 x 16]   standardised input (act16 images, mlp_tiles.h)
   float* hA = xT + IN_MAX * 16;          // [512 x 16]  h1
@@ -151,8 +114,12 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
   }
   if (tid < 16) rows_x[tid] = row0 + tid < R ? row_at(a, a.off + row0 + tid) : -1;
   __syncthreads();
-  stage_rows(xT, in_dim, standardise, st, [&](int m) { return rows_x[m] >= 0; },
-             [&](int m, int k) { return a.x[(size_t)rows_x[m] * in_dim + k]; }, true, ws + a.W.xs, row0);
+  if constexpr (PAIRED<KA>)
+    stage_rows(xT, in_dim, standardise, st, [&](int m) { return rows_x[m] >= 0; },
+               [&](int m, int k) { return pair_at(a, (size_t)rows_x[m], k); }, true, ws + a.W.xs, row0);
+  else
+    stage_rows(xT, in_dim, standardise, st, [&](int m) { return rows_x[m] >= 0; },
+               [&](int m, int k) { return a.x[(size_t)rows_x[m] * in_dim + k]; }, true, ws + a.W.xs, row0);
   __syncthreads();
   {  // ---- layer 1: [16, in] x [in, 512]
     f32x4 acc[1][4];
@@ -222,7 +189,12 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
         const float raw = z3[m * OUTP + A + j];
         const float ls = fminf(fmaxf(raw, a.ls_min), a.ls_max);                 // iq_sac.py:146
         const double sg = exp((double)ls), var = sg * sg, vc = fmax(var, (double)a.nll_eps);
-        const double d = (double)z3[m * OUTP + j] - (double)a.targets[(size_t)row * A + j];
+        float target;
+        if constexpr (PAIRED<KA>)
+          target = pair_target(a, (size_t)row, A, j);
+        else
+          target = a.targets[(size_t)row * A + j];
+        const double d = (double)z3[m * OUTP + j] - (double)target;
         const double r = d * d / vc, invn = 1.0 / ((double)R * (double)A);
         if (col < A) {
           g = (float)(d / vc * invn);
@@ -292,7 +264,6 @@ __global__ __launch_bounds__(RTHREADS) void bc_rows_kernel(FitArgs a) {
 // Launch B (the tiles: weight_tiles, ilmlp_fit.h; W3 is (1 or 2) x 16).  The decode and the step keep their own text here,
 // which is ilmlp_fit.h's weight_tile and tile_step with the W2 / W3 mirrors in the step: through the two functions a step
 // of the fit ran 0.2 to 0.4 us (0.5 to 0.8 %) longer in each of three alternating runs at batch 32 and 256 (HIP events).
-constexpr double HALF_LOG_2PI_P1 = 0.5 + 0.5 * 1.8378770664093454835606594728112;   // 0.5 + 0.5 log(2 pi)
 __global__ __launch_bounds__(THREADS) void bc_weights_kernel(FitArgs a) {
   __shared__ float red[4 * 256];
   __shared__ float bred[4 * 64];
@@ -412,7 +383,11 @@ extern "C" int oly_bc_targets(oly_ctx* ctx, int64_t n, int act_dim, const float*
   return OLY_OK;
 }
 
-// What oly_bc_fit_steps and oly_bc_fit_steps_log share.  lg == NULL: oly_bc_fit_steps (out [n_steps, 3], its launches
+template <class KA>
+static int run_steps(oly_ctx* ctx, const oly_bc_fit* f, int n_steps, const oly_bc_fit_log* lg, oly_stream stream, KA a,
+                     unsigned bit);
+
+// What oly_bc_fit_steps and oly_bc_fit_steps_log share. lg == NULL: oly_bc_fit_steps (out [n_steps, 3], its launches
 // alone).  lg: out [n_steps, 4], and a step s with (iter0 + s) % logging_iter == 0 runs two more launches after launch B.
 static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_steps, const oly_bc_fit_log* lg,
                      oly_stream stream) {
@@ -422,7 +397,19 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
              "%s: supported: 0 < batch <= %d, 0 < in_dim <= %d, 0 < act_dim <= %d, n_rows > 0, n_steps >= 0 "
              "(got batch %d, in %d, act %d, n_rows %d, n_steps %d)",
              name, MAX_BATCH, IN_MAX, MAX_ACT, batch, in_dim, A, f->n_rows, n_steps);
-  if (!f->states || !f->targets || !f->idx || !f->param || !f->m || !f->v || !f->packed || !f->ws || !f->out)
+  if (const oly_bc_pair* pr = f->pair) {
+    if (f->targets)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: with pair the targets are formed from pair->actions (targets must be NULL)", name);
+    if (!pr->x2 || !pr->actions || !pr->central || !pr->delta)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL x2 / actions / central / delta in pair", name);
+    if (pr->d1 < 1 || pr->d2 < 1 || (long)pr->d1 + pr->d2 != in_dim)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: pair needs d1 >= 1, d2 >= 1, d1 + d2 == in_dim (got %d, %d, in %d)", name, pr->d1, pr->d2,
+               in_dim);
+    if (pr->stride1 < pr->d1 || pr->stride2 < pr->d2)
+      OLY_FAIL(ctx, OLY_EINVAL, "%s: a stride of pair below its width (stride1 %d, d1 %d; stride2 %d, d2 %d)", name,
+               pr->stride1, pr->d1, pr->stride2, pr->d2);
+  }
+  if (!f->states || (!f->targets && !f->pair) || !f->idx || !f->param || !f->m || !f->v || !f->packed || !f->ws || !f->out)
     OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL pointer in the argument block", name);
   if (!(f->log_std_min <= f->log_std_max) || !(f->nll_eps > 0.f))
     OLY_FAIL(ctx, OLY_EINVAL, "%s: log_std_min <= log_std_max and nll_eps > 0 are required", name);
@@ -441,7 +428,8 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
     if (first < n_steps && !lg->eps) OLY_FAIL(ctx, OLY_EINVAL, "%s: a step of the call logs and eps is NULL", name);
   }
   if (n_steps == 0) return OLY_OK;
-  FitArgs a{};
+  PairFitArgs pa{};
+  FitArgs& a = pa;
   a.in_dim = a.ds = in_dim;
   a.n_rows = f->n_rows;
   a.act_dim = A;
@@ -462,13 +450,32 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
   a.P = param_layout(in_dim, 2 * A);
   a.W = W;
   a.R = batch;
+  if (!f->pair) return run_steps<FitArgs>(ctx, f, n_steps, lg, stream, a, 1u);
+  pa.d1 = f->pair->d1;
+  pa.d2 = f->pair->d2;
+  pa.stride1 = f->pair->stride1;
+  pa.stride2 = f->pair->stride2;
+  pa.x2 = f->pair->x2;
+  pa.actions = f->pair->actions;
+  pa.central = f->pair->central;
+  pa.delta = f->pair->delta;
+  return run_steps<PairFitArgs>(ctx, f, n_steps, lg, stream, pa, 4u);
+}
+
+// The launches of a call over the argument block KA: FitArgs, or PairFitArgs with oly_bc_fit.pair (`bit`: the rows
+// kernel's first flag in the context's bcfit_attr_done).
+template <class KA>
+static int run_steps(oly_ctx* ctx, const oly_bc_fit* f, int n_steps, const oly_bc_fit_log* lg, oly_stream stream, KA a,
+                     unsigned bit) {
+  const int in_dim = f->in_dim, A = f->act_dim, batch = f->batch;
+  const WsL& W = a.W;
   const float* p = f->param;
   const ParamLayout& P = a.P;
-  rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 2 * A, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
+  int rc = oly_ilmlp_pack(ctx, in_dim, H1, H2, 2 * A, p + P.w1, p + P.b1, p + P.w2, p + P.b2, p + P.w3, p + P.b3, f->packed,
                       stream);
   if (rc != OLY_OK) return rc;
   a.off = 0;
-  hipLaunchKernelGGL(bc_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
+  hipLaunchKernelGGL(bc_prologue_kernel<KA>, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   const dim3 grid_a((unsigned)((batch + 15) / 16)), grid_b((unsigned)weight_tiles(in_dim, 2 * A));
   const size_t out_w = lg ? 4 : 3;
   long logged = 0;
@@ -478,14 +485,24 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
     a.Rn = s + 1 < n_steps ? batch : 0;
     a.ad = oly_fit::adam_scalars(f->beta1, f->beta2, f->eps, f->lr, (long)f->step + s + 1);
     a.out = f->out + out_w * (size_t)s;
-    rc = launch_rows(ctx, ctx->bcfit_attr_done, 1u, bc_rows_kernel<2>, bc_rows_kernel<4>, in_dim, grid_a, ROWS_LDS, stream, a);
+    rc = launch_rows(ctx, ctx->bcfit_attr_done, bit, bc_rows_kernel<2, KA>, bc_rows_kernel<4, KA>, in_dim, grid_a, ROWS_LDS,
+                     stream, a);
     if (rc != OLY_OK) return rc;
-    hipLaunchKernelGGL(bc_weights_kernel, grid_b, dim3(THREADS), 0, oly_s(stream), a);
+    if constexpr (PAIRED<KA>)
+      oly_bc::launch_weights_pair(a, grid_b, stream);
+    else
+      hipLaunchKernelGGL(bc_weights_kernel, grid_b, dim3(THREADS), 0, oly_s(stream), a);
     if (lg && ((long)lg->iter0 + s) % lg->logging_iter == 0) {
       // logging() (behavioral_cloning.py:82-94): compute_action_and_log_prob on the minibatch.  colstats holds idx[s] once
       // (launch B) and the workspace's delta its column sums (launch A): the forward standardises with colstats + delta,
       // the fold adds delta to colstats.
-      oly_sg::Args g{};
+      std::conditional_t<PAIRED<KA>, oly_sg::PairArgs, oly_sg::Args> g{};
+      if constexpr (PAIRED<KA>) {
+        g.d1 = a.d1;
+        g.stride1 = a.stride1;
+        g.stride2 = a.stride2;
+        g.x2 = a.x2;
+      }
       g.N = batch;
       g.in_dim = in_dim;
       g.act_dim = A;
@@ -502,7 +519,7 @@ static int fit_steps(oly_ctx* ctx, const char* name, const oly_bc_fit* f, int n_
       g.log_prob = f->ws + W.total;
       rc = oly_sg::launch(ctx, g, stream);
       if (rc != OLY_OK) return rc;
-      hipLaunchKernelGGL(bc_log_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), a);
+      hipLaunchKernelGGL(bc_log_fold_kernel, dim3(1), dim3(THREADS), 0, oly_s(stream), static_cast<const FitArgs&>(a));
       ++logged;
     }
   }

@@ -14,6 +14,12 @@
 // sample, the action and the two fp64 terms of the log-probability (in layer 1's image, dead after layer 2); after a
 // second barrier one thread per row adds the terms with j in order and all threads form the control rows from the
 // action tile (il_ctrl_kernel's expression, k1_il_step.hip).
+//
+// With oly_sg_act_args' trailing fields (the inverse action model's draw, K28) the kernel is instantiated over
+// oly_sg::PairArgs: the staging loop reads row i of two tables, i = idx[r] or r, and the action is clipped in fp64
+// before it is stored.  Everything else is the same text, so the outputs have the bits of the call on materialised rows.
+#include <type_traits>
+
 #include "ilmlp_common.h"
 #include "oly_common.h"
 #include "sg_act.h"
@@ -21,13 +27,15 @@
 namespace {
 using namespace oly_ilmlp;
 using oly_sg::Args;
+using oly_sg::PairArgs;
 
 constexpr int MAX_ACT = OLY_BC_MAX_ACT;
 constexpr double HALF_LOG_2PI = 0.5 * 1.8378770664093454835606594728112;
 static_assert(2 * MAX_ACT <= OUT_MAX, "2A output columns");
 
-template <int RS, int G1>
-__global__ __launch_bounds__(FWD_THREADS) void sg_act_kernel(Args p) {
+template <int RS, int G1, class KA>
+__global__ __launch_bounds__(FWD_THREADS) void sg_act_kernel(KA p) {
+  constexpr bool PAIR = std::is_same<KA, PairArgs>::value;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xT = lds;                                   // [RS][64 x 16]   input images; later raw outputs and the action tile
   float* hA = xT + (size_t)RS * IN_MAX * 16;         // [RS][512 x 16]  layer-1 images; later the log-probability's terms
@@ -71,7 +79,11 @@ __global__ __launch_bounds__(FWD_THREADS) void sg_act_kernel(Args p) {
         const int i = p.rows[row];
         src = i < 0 ? 0 : i >= p.n_rows ? p.n_rows - 1 : i;
       }
-      const float xv = p.x[src * in_dim + k];
+      float xv;
+      if constexpr (PAIR)
+        xv = k < p.d1 ? p.x[src * p.stride1 + k] : p.x2[src * p.stride2 + (k - p.d1)];
+      else
+        xv = p.x[src * in_dim + k];
       // f32((f64(x) - mean) / std): the reference subtracts fp64 statistics and narrows afterwards (networks.py:68-74)
       v = standardise ? (float)(((double)xv - s_mean[k]) / s_sd[k]) : xv;
     }
@@ -143,7 +155,15 @@ __global__ __launch_bounds__(FWD_THREADS) void sg_act_kernel(Args p) {
       a_raw = m + se;
     }
     const double th = tanh((double)a_raw);
-    const float act = p.delta ? (float)th * p.delta[j] + p.central[j] : 0.f;   // no bounds: the logged fit (no action)
+    float act = p.delta ? (float)th * p.delta[j] + p.central[j] : 0.f;   // no bounds: the logged fit (no action)
+    if constexpr (PAIR) {
+      if (p.clip_lo) {     // np.clip(action, low, high) against float64 bounds (lsiqfo.py:90); a NaN passes through
+        double v = (double)act;
+        v = v < p.clip_lo[j] ? p.clip_lo[j] : v;
+        v = v > p.clip_hi[j] ? p.clip_hi[j] : v;
+        act = (float)v;
+      }
+    }
     if (p.mu) p.mu[o] = m;
     if (p.log_sigma) p.log_sigma[o] = ls;
     if (p.action) p.action[o] = act;
@@ -185,21 +205,21 @@ __global__ __launch_bounds__(FWD_THREADS) void sg_act_kernel(Args p) {
   }
 }
 
-template <int RS>
-int launch_rs(oly_ctx* ctx, const Args& a, oly_stream stream) {
+template <int RS, class KA>
+int launch_rs(oly_ctx* ctx, const KA& a, oly_stream stream) {
   const int G = (a.in_dim + 15) / 16;
-  const unsigned bit = 1u << (4 * (RS - 1) + (G - 1));
+  const unsigned bit = 1u << ((std::is_same<KA, PairArgs>::value ? 8 : 0) + 4 * (RS - 1) + (G - 1));
   const dim3 grid((unsigned)((a.N + 16 * RS - 1) / (16 * RS)));
   const size_t lds = fwd_lds<RS>();
   switch (G) {
 #define OLY_SGACT_CASE(G)                                                                                             \
   case G:                                                                                                             \
     if (!(ctx->sgact_attr_done & bit)) {                                                                              \
-      OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sg_act_kernel<RS, G>),                           \
+      OLY_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sg_act_kernel<RS, G, KA>),                       \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
       ctx->sgact_attr_done |= bit;                                                                                    \
     }                                                                                                                 \
-    hipLaunchKernelGGL((sg_act_kernel<RS, G>), grid, dim3(FWD_THREADS), lds, oly_s(stream), a);                       \
+    hipLaunchKernelGGL((sg_act_kernel<RS, G, KA>), grid, dim3(FWD_THREADS), lds, oly_s(stream), a);                   \
     break;
     OLY_SGACT_CASE(1)
     OLY_SGACT_CASE(2)
@@ -210,14 +230,18 @@ int launch_rs(oly_ctx* ctx, const Args& a, oly_stream stream) {
   OLY_LAUNCH_CHECK(ctx, "sg_act_kernel");
   return OLY_OK;
 }
-}  // namespace
 
-int oly_sg::launch(oly_ctx* ctx, const Args& a, oly_stream stream) {
+template <class KA>
+int launch_any(oly_ctx* ctx, const KA& a, oly_stream stream) {
   // the row-tile choice of oly_ilmlp_forward: 16-row tiles while 32-row tiles would leave CUs without a second workgroup
   const long slots = 2L * (ctx->num_cu > 0 ? ctx->num_cu : 256);
   if ((a.N + 31) / 32 < slots) return launch_rs<1>(ctx, a, stream);
   return launch_rs<2>(ctx, a, stream);
 }
+}  // namespace
+
+int oly_sg::launch(oly_ctx* ctx, const Args& a, oly_stream stream) { return launch_any(ctx, a, stream); }
+int oly_sg::launch(oly_ctx* ctx, const PairArgs& a, oly_stream stream) { return launch_any(ctx, a, stream); }
 
 extern "C" int oly_sg_act(oly_ctx* ctx, const oly_sg_act_args* f, oly_stream stream) {
   if (!ctx) return OLY_EINVAL;
@@ -234,11 +258,24 @@ extern "C" int oly_sg_act(oly_ctx* ctx, const oly_sg_act_args* f, oly_stream str
   if (f->ctrl && ctx->il_host.n_act != f->act_dim)
     OLY_FAIL(ctx, OLY_EINVAL, "oly_sg_act: ctrl requested for act_dim %d, the configured model has n_act %d", f->act_dim,
              ctx->il_host.n_act);
-  if (f->update_stats) {   // Standardizer.update_mean_std before the forward (networks.py:70)
+  const bool paired = f->x2 || f->d2 || f->stride1 || f->stride2 || f->idx || f->clip_lo || f->clip_hi;
+  if (paired) {
+    const int d2 = f->d2, d1 = f->in_dim - d2;
+    if (d2 < 0 || d2 >= f->in_dim) OLY_FAIL(ctx, OLY_EINVAL, "oly_sg_act: d2 %d outside [0, in_dim %d)", d2, f->in_dim);
+    if ((d2 > 0) != (f->x2 != nullptr)) OLY_FAIL(ctx, OLY_EINVAL, "oly_sg_act: x2 and d2 > 0 go together (d2 %d)", d2);
+    if ((f->stride1 != 0 && f->stride1 < d1) || f->stride2 < d2)
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_sg_act: a stride below its width (stride1 %d, d1 %d; stride2 %d, d2 %d)", f->stride1, d1,
+               f->stride2, d2);
+    if (f->idx && f->n_rows < 1) OLY_FAIL(ctx, OLY_EINVAL, "oly_sg_act: idx with n_rows %d (>= 1)", f->n_rows);
+    if ((f->clip_lo != nullptr) != (f->clip_hi != nullptr))
+      OLY_FAIL(ctx, OLY_EINVAL, "oly_sg_act: one clip bound without the other");
+  }
+  if (f->update_stats && !paired) {   // Standardizer.update_mean_std before the forward (networks.py:70)
     const int rc = oly_col_stats(ctx, f->n, f->in_dim, f->x, f->colstats, 1, stream);
     if (rc != OLY_OK) return rc;
   }
-  Args a{};
+  PairArgs pa{};
+  Args& a = pa;
   a.N = f->n;
   a.in_dim = f->in_dim;
   a.act_dim = f->act_dim;
@@ -257,5 +294,18 @@ extern "C" int oly_sg_act(oly_ctx* ctx, const oly_sg_act_args* f, oly_stream str
   a.ctrl = f->ctrl;
   a.ctrl64 = f->ctrl && (f->out_flags & OLY_OUT_CTRL_F64);
   a.md = ctx->il_dev;
-  return oly_sg::launch(ctx, a, stream);
+  if (!paired) return oly_sg::launch(ctx, a, stream);
+  pa.rows = f->idx;
+  pa.n_rows = f->n_rows;
+  pa.d1 = f->in_dim - f->d2;
+  pa.stride1 = f->stride1 ? f->stride1 : pa.d1;
+  pa.stride2 = f->stride2;
+  pa.x2 = f->x2;
+  pa.clip_lo = f->clip_lo;
+  pa.clip_hi = f->clip_hi;
+  if (f->update_stats) {
+    const int rc = oly_sg::col_stats_pair(ctx, f->n, pa, f->colstats, stream);
+    if (rc != OLY_OK) return rc;
+  }
+  return oly_sg::launch(ctx, pa, stream);
 }

@@ -8,6 +8,7 @@
 // atomics.  stats live in device memory so that the multi-GPU path can all-gather them over
 // RCCL without a host round trip.  Bound: HBM, 4 B/element (stats), 8 B/element (normalise).
 #include "oly_common.h"
+#include "sg_act.h"
 
 namespace {
 
@@ -198,7 +199,56 @@ __global__ __launch_bounds__(64) void col_finish_kernel(int nblocks, int B, int 
   }
 }
 
+// col_partial_kernel / col_partial4_kernel on rows gathered from two tables (oly_sg::col_stats_pair): thread t owns
+// column c = t % D of the concatenated row and the rows rl, rl + lanes, ... of the block's slab, rl = t / D, as a thread
+// of either kernel does for each of its columns; the lanes' partials are then added in lane order.  With the same
+// `lanes` and slab the sums have that kernel's bits on the materialised rows (its first partial is added to +0).
+__global__ __launch_bounds__(1024) void col_partial_pair_kernel(int B, int D, int lanes, int rows_per_block, int d1,
+                                                                long stride1, long stride2, int n_rows,
+                                                                const float* __restrict__ x, const float* __restrict__ x2,
+                                                                const int32_t* __restrict__ rows, double* __restrict__ ws) {
+  extern __shared__ double shc[];  // [lanes][D][2]
+  const int c = threadIdx.x % D, rl = threadIdx.x / D;
+  const int r0 = blockIdx.x * rows_per_block;
+  const int r1 = min(B, r0 + rows_per_block);
+  double s = 0.0, ss = 0.0;
+  for (int r = r0 + rl; r < r1; r += lanes) {
+    long i = r;
+    if (rows) {
+      const int q = rows[r];
+      i = q < 0 ? 0 : q >= n_rows ? n_rows - 1 : q;
+    }
+    const double a = c < d1 ? x[i * stride1 + c] : x2[i * stride2 + (c - d1)];
+    s += a; ss += a * a;
+  }
+  shc[(rl * D + c) * 2] = s;
+  shc[(rl * D + c) * 2 + 1] = ss;
+  __syncthreads();
+  if (rl == 0) {
+    double ts = 0.0, tss = 0.0;
+    for (int l = 0; l < lanes; ++l) { ts += shc[(l * D + c) * 2]; tss += shc[(l * D + c) * 2 + 1]; }
+    ws[((size_t)blockIdx.x * D + c) * 2] = ts;
+    ws[((size_t)blockIdx.x * D + c) * 2 + 1] = tss;
+  }
+}
+
 }  // namespace
+
+int oly_sg::col_stats_pair(oly_ctx* ctx, int n, const PairArgs& a, double* colstats, oly_stream stream) {
+  const int D = a.in_dim;
+  // oly_col_stats' choice of kernel, lanes, grid and slab for [n, D] rows at a 16-byte aligned address
+  const bool four = (D & 3) == 0;
+  const int lanes = four ? THREADS / (D >> 2) : THREADS / D, per = four ? 8 : 64;
+  int nb = (n + per * lanes - 1) / (per * lanes);
+  if (nb < 1) nb = 1;
+  if (nb > OLY_STATS_MAX_BLOCKS) nb = OLY_STATS_MAX_BLOCKS;
+  const int rpb = (n + nb - 1) / nb;
+  hipLaunchKernelGGL(col_partial_pair_kernel, dim3(nb), dim3(lanes * D), sizeof(double) * 2 * lanes * D, oly_s(stream), n, D,
+                     lanes, rpb, a.d1, (long)a.stride1, (long)a.stride2, a.n_rows, a.x, a.x2, a.rows, ctx->stats_ws);
+  hipLaunchKernelGGL(col_finish_kernel, dim3(D), dim3(64), 0, oly_s(stream), nb, n, D, ctx->stats_ws, colstats, 1);
+  OLY_LAUNCH_CHECK(ctx, "paired col stats kernels");
+  return OLY_OK;
+}
 
 extern "C" int oly_adv_stats(oly_ctx* ctx, int64_t n, const float* x, double* stats3_out,
                              oly_stream stream) {

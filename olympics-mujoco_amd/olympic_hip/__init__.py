@@ -6,7 +6,8 @@ from . import _abi, specs  # noqa: F401
 
 __all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy", "DeviceSoftQCritic",
            "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceLSIQH", "DeviceLSIQHC", "DeviceIQSAC",
-           "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC"]
+           "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC", "DeviceGaussianInvActionModel",
+           "DeviceIQfOSAC", "DeviceLSIQfOSAC", "DeviceLSIQfOHSAC", "DeviceLSIQfOHCSAC"]
 
 
 def __getattr__(name):
@@ -19,4 +20,8 @@ def __getattr__(name):
                 "DeviceLSIQHC", "DeviceIQSAC", "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC"):
         from . import iq
         return getattr(iq, name)
+    # the inverse action model of the learning-from-observations agents (iqfo.py, K28)
+    if name in ("DeviceGaussianInvActionModel", "DeviceIQfOSAC", "DeviceLSIQfOSAC", "DeviceLSIQfOHSAC", "DeviceLSIQfOHCSAC"):
+        from . import iqfo
+        return getattr(iqfo, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

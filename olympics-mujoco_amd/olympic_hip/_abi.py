@@ -240,6 +240,12 @@ class TRPOStep(C.Structure):
                 ("ws_floats", C.c_int64), ("stepdir_out", vp), ("full_step_out", vp), ("scal_out", vp)]
 
 
+class BCPair(C.Structure):
+    """oly_bc_pair (K24): the two indexed tables and raw actions of a paired fit, the block oly_bc_fit.pair points to."""
+    _fields_ = [("d1", C.c_int32), ("d2", C.c_int32), ("stride1", C.c_int32), ("stride2", C.c_int32), ("x2", vp),
+                ("actions", vp), ("central", vp), ("delta", vp)]
+
+
 class BCFit(C.Structure):
     """oly_bc_fit (K24): the behavioural-cloning fit state for oly_bc_fit_steps."""
     _fields_ = [("in_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32), ("n_rows", C.c_int32),
@@ -247,7 +253,7 @@ class BCFit(C.Structure):
                 ("weight_decay", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
                 ("nll_eps", C.c_float), ("pad", C.c_int32), ("states", vp), ("targets", vp), ("idx", vp),
                 ("colstats", vp), ("param", vp), ("m", vp), ("v", vp), ("packed", vp), ("ws", vp),
-                ("ws_floats", C.c_int64), ("out", vp)]
+                ("ws_floats", C.c_int64), ("out", vp), ("pair", C.POINTER(BCPair))]
 
 
 OLY_BC_MAX_BATCH, OLY_BC_MAX_ACT = 4096, 16
@@ -267,7 +273,8 @@ class SGAct(C.Structure):
     _fields_ = [("n", C.c_int32), ("in_dim", C.c_int32), ("act_dim", C.c_int32), ("update_stats", C.c_int32), ("x", vp),
                 ("colstats", vp), ("packed", vp), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("central", vp),
                 ("delta", vp), ("eps", vp), ("action", vp), ("log_prob", vp), ("mu", vp), ("log_sigma", vp), ("ctrl", vp),
-                ("out_flags", C.c_int32), ("pad", C.c_int32)]
+                ("out_flags", C.c_int32), ("pad", C.c_int32), ("x2", vp), ("d2", C.c_int32), ("stride1", C.c_int32),
+                ("stride2", C.c_int32), ("n_rows", C.c_int32), ("idx", vp), ("clip_lo", vp), ("clip_hi", vp)]
 
 
 class LSIQ(C.Structure):

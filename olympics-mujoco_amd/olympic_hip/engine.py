@@ -982,23 +982,55 @@ class Engine:
                            f"{_abi.OLY_BC_MAX_BATCH}, in <= 64, act <= {_abi.OLY_BC_MAX_ACT})")
         return self._new((n,), torch.float32)
 
+    def _bc_rows(self, name, states, targets, pair):
+        """The row and target widths of a K24 fit and its oly_bc_pair: (in_dim, A, BCPair or None).  pair: None, or
+        dict(x2 [n,stride2] f32, actions [n,A] f32, central [A] f32, delta [A] f32, d1=stride1, d2=stride2): the rows are
+        (states[i, :d1] | x2[i, :d2]) and the targets are formed from the raw actions in the kernel (targets None)."""
+        f32, dv = torch.float32, self.device
+        if not isinstance(states, torch.Tensor) or states.dim() != 2:
+            raise OlyError(f"{name}: states is a [n,in] tensor")
+        n, s1 = (int(t) for t in states.shape)
+        _req(states, "states", (n, s1), f32, dv)
+        if pair is None:
+            if not isinstance(targets, torch.Tensor) or targets.dim() != 2:
+                raise OlyError(f"{name}: targets is a [n,A] tensor")
+            _req(targets, "targets", (n, int(targets.shape[1])), f32, dv)
+            return s1, int(targets.shape[1]), None
+        if targets is not None:
+            raise OlyError(f"{name}: with pair the targets are formed from pair['actions'] (targets must be None)")
+        unknown = set(pair) - {"x2", "actions", "central", "delta", "d1", "d2"}
+        if unknown:
+            raise OlyError(f"{name}: unknown pair entries {sorted(unknown)}")
+        x2, actions = pair.get("x2"), pair.get("actions")
+        if not isinstance(x2, torch.Tensor) or x2.dim() != 2 or not isinstance(actions, torch.Tensor) or actions.dim() != 2:
+            raise OlyError(f"{name}: pair needs x2 [n,stride2] and actions [n,A] tensors")
+        s2, A = int(x2.shape[1]), int(actions.shape[1])
+        d1, d2 = int(pair.get("d1") or s1), int(pair.get("d2") or s2)
+        if not (1 <= d1 <= s1 and 1 <= d2 <= s2):
+            raise OlyError(f"{name}: pair widths d1={d1} (1 .. {s1}), d2={d2} (1 .. {s2})")
+        _req(x2, "pair.x2", (n, s2), f32, dv)
+        _req(actions, "pair.actions", (n, A), f32, dv)
+        _req(pair.get("central"), "pair.central", (A,), f32, dv)
+        _req(pair.get("delta"), "pair.delta", (A,), f32, dv)
+        bp = _abi.BCPair(d1=d1, d2=d2, stride1=s1, stride2=s2, x2=x2.data_ptr(), actions=actions.data_ptr(),
+                         central=pair["central"].data_ptr(), delta=pair["delta"].data_ptr())
+        return d1 + d2, A, bp
+
     def bc_fit_steps(self, states, targets, idx, colstats, param, m, v, packed, ws, step, lr, beta1=0.9, beta2=0.999,
-                     eps=1e-8, weight_decay=0.0, log_std_min=-20.0, log_std_max=2.0, nll_eps=1e-6, out=None):
+                     eps=1e-8, weight_decay=0.0, log_std_min=-20.0, log_std_max=2.0, nll_eps=1e-6, out=None, pair=None):
         """oly_bc_fit_steps: idx.shape[0] iterations of BehavioralCloning.fit_offline in one call.  states [n,in] f32 raw
         rows, targets [n,A] f32 (bc_targets), idx [n_steps,batch] int32 the rows of every step, colstats [3,in] f64 the
         Standardizer's running sums or None (no Standardizer), param / m / v flat in torch order (W1 | b1 | W2 | b2 |
         W3 [2A,256] | b3), packed the ilmlp_pack stream (re-packed from param, then kept current); step = Adam steps
-        taken before.  Returns out [n_steps,3] f64: the loss, the Gaussian entropy, the mean squared error."""
+        taken before.  pair (see _bc_rows; targets None): the rows of two tables indexed by idx, in = d1 + d2, and the
+        targets from the raw actions, the fit of the inverse action model on a replay ring.
+        Returns out [n_steps,3] f64: the loss, the Gaussian entropy, the mean squared error."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(states, torch.Tensor) or states.dim() != 2:
-            raise OlyError("bc_fit_steps: states is a [n,in] tensor")
-        if not isinstance(targets, torch.Tensor) or targets.dim() != 2:
-            raise OlyError("bc_fit_steps: targets is a [n,A] tensor")
+        in_dim, A, bp = self._bc_rows("bc_fit_steps", states, targets, pair)
         if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
             raise OlyError("bc_fit_steps: idx is a [n_steps,batch] tensor")
-        n, in_dim = (int(t) for t in states.shape)
-        A = int(targets.shape[1])
+        n = int(states.shape[0])
         n_steps, batch = (int(t) for t in idx.shape)
         nws = int(lib().oly_bc_fit_ws(batch, in_dim, A))
         if nws < 0 or n < 1:
@@ -1007,8 +1039,6 @@ class Engine:
         if not float(log_std_min) <= float(log_std_max) or not float(nll_eps) > 0.0:
             raise OlyError("bc_fit_steps: log_std_min <= log_std_max and nll_eps > 0 are required")
         n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 2 * A * 256 + 2 * A
-        _req(states, "states", (n, in_dim), f32, dv)
-        _req(targets, "targets", (n, A), f32, dv)
         _req(idx, "idx", (n_steps, batch), torch.int32, dv)
         _req(colstats, "colstats", (3, in_dim), f64, dv, optional=True)
         for t, name in ((param, "param"), (m, "m"), (v, "v")):
@@ -1022,9 +1052,9 @@ class Engine:
         f = _abi.BCFit(in_dim=in_dim, act_dim=A, batch=batch, n_rows=n, step=int(step), lr=float(lr), beta1=float(beta1),
                        beta2=float(beta2), eps=float(eps), weight_decay=float(weight_decay),
                        log_std_min=float(log_std_min), log_std_max=float(log_std_max), nll_eps=float(nll_eps),
-                       states=states.data_ptr(), targets=targets.data_ptr(), idx=idx.data_ptr(), colstats=ptr(colstats),
+                       states=states.data_ptr(), targets=ptr(targets), idx=idx.data_ptr(), colstats=ptr(colstats),
                        param=param.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(),
-                       ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr())
+                       ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr(), pair=C.pointer(bp) if bp else None)
         self.ctx.call("oly_bc_fit_steps", C.byref(f), n_steps, self._s())
         return out
 
@@ -1044,21 +1074,18 @@ class Engine:
 
     def bc_fit_steps_log(self, states, targets, idx, colstats, param, m, v, packed, ws, step, lr, logging_iter, iter0, noise,
                          beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, log_std_min=-20.0, log_std_max=2.0,
-                         nll_eps=1e-6, out=None):
+                         nll_eps=1e-6, out=None, pair=None):
         """oly_bc_fit_steps_log: bc_fit_steps with the sampled second forward of BehavioralCloning.logging() on every
         step s with (iter0 + s) % logging_iter == 0.  noise [n_logged, batch, A] f32: the standard normal draws of the
         logging steps in order; ws from bc_fit_log_ws.  Returns out [n_steps,4] f64: bc_fit_steps' three scalars and
-        -mean(log_prob); column 3 of a step that does not log is not written (NaN in a buffer made here)."""
+        -mean(log_prob); column 3 of a step that does not log is not written (NaN in a buffer made here).  pair: as
+        bc_fit_steps'."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
-        if not isinstance(states, torch.Tensor) or states.dim() != 2:
-            raise OlyError("bc_fit_steps_log: states is a [n,in] tensor")
-        if not isinstance(targets, torch.Tensor) or targets.dim() != 2:
-            raise OlyError("bc_fit_steps_log: targets is a [n,A] tensor")
+        in_dim, A, bp = self._bc_rows("bc_fit_steps_log", states, targets, pair)
         if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
             raise OlyError("bc_fit_steps_log: idx is a [n_steps,batch] tensor")
-        n, in_dim = (int(t) for t in states.shape)
-        A = int(targets.shape[1])
+        n = int(states.shape[0])
         n_steps, batch = (int(t) for t in idx.shape)
         nws = int(lib().oly_bc_fit_log_ws(batch, in_dim, A))
         if nws < 0 or n < 1:
@@ -1070,8 +1097,6 @@ class Engine:
             raise OlyError(f"bc_fit_steps_log: logging_iter={logging_iter} (>= 1), iter0={iter0} (>= 0)")
         n_logged = len(self.bc_logged_steps(n_steps, logging_iter, iter0))
         n_par = 512 * in_dim + 512 + 256 * 512 + 256 + 2 * A * 256 + 2 * A
-        _req(states, "states", (n, in_dim), f32, dv)
-        _req(targets, "targets", (n, A), f32, dv)
         _req(idx, "idx", (n_steps, batch), torch.int32, dv)
         _req(colstats, "colstats", (3, in_dim), f64, dv, optional=True)
         for t, name in ((param, "param"), (m, "m"), (v, "v")):
@@ -1088,28 +1113,52 @@ class Engine:
         fit = _abi.BCFit(in_dim=in_dim, act_dim=A, batch=batch, n_rows=n, step=int(step), lr=float(lr), beta1=float(beta1),
                          beta2=float(beta2), eps=float(eps), weight_decay=float(weight_decay),
                          log_std_min=float(log_std_min), log_std_max=float(log_std_max), nll_eps=float(nll_eps),
-                         states=states.data_ptr(), targets=targets.data_ptr(), idx=idx.data_ptr(), colstats=ptr(colstats),
+                         states=states.data_ptr(), targets=ptr(targets), idx=idx.data_ptr(), colstats=ptr(colstats),
                          param=param.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), packed=packed.data_ptr(),
-                         ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr())
+                         ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr(), pair=C.pointer(bp) if bp else None)
         f = _abi.BCFitLog(fit=fit, logging_iter=int(logging_iter), iter0=int(iter0), eps=ptr(noise))
         self.ctx.call("oly_bc_fit_steps_log", C.byref(f), n_steps, self._s())
         return out
 
     # -------------------------------------------------------------- K25 (the squashed-Gaussian act and log-probability)
     def sg_act(self, x, packed, central, delta, colstats=None, eps=None, update_stats=True, log_std_min=-20.0,
-               log_std_max=2.0, want=("log_prob",), ctrl_f64=False, out=None):
+               log_std_max=2.0, want=("log_prob",), ctrl_f64=False, out=None, x2=None, idx=None, clip=None, d1=None,
+               d2=None):
         """oly_sg_act: compute_action_and_log_prob (iq_sac.py:102-151) on x [n,in] f32 in one call.  colstats [3,in] f64
         takes the rows first (update_stats) and standardises them, None: no Standardizer.  packed: ilmlp_pack's stream of
         the network in -> 512 -> 256 -> 2A; central / delta [A] f32; eps [n,A] f32 (None: the squashed mean).  want: which
         of "log_prob" [n], "mu" [n,A], "log_sigma" [n,A] (clamped), "ctrl" [n,nu] (il_ctrl of the action, from the
         configured model) to return beside "action" [n,A].  Returns a dict (absent outputs None); `out` may supply the
-        buffers.  No synchronisation."""
+        buffers.  No synchronisation.
+        x2 [rows,stride2] f32 / idx [n] int32 / clip (lo [A], hi [A]) f64 / d1 / d2: the inverse action model's draw.  Row r
+        is (x[i, :d1] | x2[i, :d2]), i = idx[r] (None: r), d1 / d2 default to the tables' widths, in = d1 + d2 and
+        colstats [3,in]; the action is clipped in float64, np.clip(action, lo, hi), before it is stored."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
         if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(central, torch.Tensor) or central.dim() != 1:
             raise OlyError("sg_act: x [n,in] and central [A] must be tensors")
         n, D = (int(v) for v in x.shape)
         A = int(central.shape[0])
+        paired = x2 is not None or idx is not None or clip is not None or d1 is not None or d2 is not None
+        rows, s1, s2, w2 = n, D, 0, 0
+        if paired:
+            if x2 is not None and (not isinstance(x2, torch.Tensor) or x2.dim() != 2 or x2.shape[0] != rows):
+                raise OlyError(f"sg_act: x2 is a [{rows},stride2] tensor")
+            if x2 is None and d2:
+                raise OlyError("sg_act: d2 without x2")
+            s2 = int(x2.shape[1]) if x2 is not None else 0
+            w1, w2 = int(d1 or s1), int(d2 or s2)
+            if not 1 <= w1 <= s1 or not (x2 is None or 1 <= w2 <= s2):
+                raise OlyError(f"sg_act: widths d1={w1} (1 .. {s1}), d2={w2} (1 .. {s2})")
+            D = w1 + w2
+            if idx is not None:
+                if not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+                    raise OlyError("sg_act: idx is a [n] int32 tensor")
+                n = int(idx.shape[0])
+                _req(idx, "idx", (n,), torch.int32, dv)
+            if clip is not None:
+                _req(clip[0], "clip lo", (A,), f64, dv)
+                _req(clip[1], "clip hi", (A,), f64, dv)
         if n < 1:
             raise OlyError(f"sg_act: n={n} rows (n >= 1)")
         if not 0 < D <= 64 or not 0 < A <= _abi.OLY_BC_MAX_ACT:
@@ -1122,7 +1171,8 @@ class Engine:
         if colstats is None and update_stats:
             update_stats = False
         npk = int(lib().oly_ilmlp_packed_floats(D, 512, 256, 2 * A))
-        _req(x, "x", (n, D), f32, dv)
+        _req(x, "x", (rows, s1), f32, dv)
+        _req(x2, "x2", (rows, s2), f32, dv, optional=True)
         _req(packed, "packed", (npk,), f32, dv)
         _req(central, "central", (A,), f32, dv)
         _req(delta, "delta", (A,), f32, dv)
@@ -1149,6 +1199,10 @@ class Engine:
                        action=o["action"].data_ptr(), log_prob=ptr(o["log_prob"]), mu=ptr(o["mu"]),
                        log_sigma=ptr(o["log_sigma"]), ctrl=ptr(o["ctrl"]),
                        out_flags=_abi.OUT_CTRL_F64 if ("ctrl" in want and ctrl_f64) else 0, pad=0)
+        if paired:
+            f.x2, f.d2, f.stride1, f.stride2 = ptr(x2), w2, s1, s2
+            f.idx, f.n_rows = ptr(idx), rows
+            f.clip_lo, f.clip_hi = (ptr(clip[0]), ptr(clip[1])) if clip is not None else (None, None)
         self.ctx.call("oly_sg_act", C.byref(f), self._s())
         return o
 

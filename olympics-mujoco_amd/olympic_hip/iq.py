@@ -242,6 +242,15 @@ class DeviceReplayMemory:
         idx = torch.randint(self.size, (int(n_samples),), device=self.eng.device, generator=generator)
         return tuple(self.blocks[k][idx] for k in self.KEYS)
 
+    @torch.no_grad()
+    def sample_idx(self, n_samples, generator=None):
+        """The indices get(n_samples) would draw from the generator's state, [n_samples] int32 rows of the blocks, for
+        the callers that hand the ring and an index to a kernel (olympic_hip.iqfo) and gather nothing."""
+        if self.size < 1:
+            raise OlyError("DeviceReplayMemory.sample_idx: the memory is empty")
+        idx = torch.randint(self.size, (int(n_samples),), device=self.eng.device, generator=generator)
+        return idx.to(torch.int32)
+
     def reset(self):
         self._idx, self._full = 0, False
 
