@@ -44,6 +44,7 @@ columns, so the model's rows from it are not masked again.
 import numpy as np
 import torch
 
+from . import _abi
 from ._ffi import OlyError
 from .bc import DeviceSquashedGaussianPolicy
 from .gail import _same
@@ -73,6 +74,8 @@ class DeviceGaussianInvActionModel(DeviceSquashedGaussianPolicy):
                          log_std_max=log_std_max, fused_act=True)
         if int(batch_size) < 1 or not float(nll_eps) > 0.0:
             raise OlyError("DeviceGaussianInvActionModel: batch_size >= 1 and nll_eps > 0 are required")
+        if int(batch_size) > _abi.OLY_BC_MAX_BATCH:
+            raise OlyError(f"DeviceGaussianInvActionModel: batch_size {int(batch_size)} > {_abi.OLY_BC_MAX_BATCH}")
         self.lr, self.betas = float(lr), (float(betas[0]), float(betas[1]))
         self.eps, self.weight_decay, self.nll_eps = float(eps), float(weight_decay), float(nll_eps)
         self.batch = int(batch_size)

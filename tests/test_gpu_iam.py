@@ -455,6 +455,8 @@ def test_model_refusals(eng):
         m.fit(S, NS, ACT, d(k["idx"])[:, :3].contiguous(), d1=c.d1, d2=c.d2)
     with pytest.raises(OlyError):
         _model(eng, c, k, nll_eps=0.0)
+    with pytest.raises(OlyError, match="batch_size 4097 > 4096"):            # the limit is named at construction, as
+        _model(eng, c._replace(batch=4097), k)                               # DeviceBehavioralCloning names it
     out = m.fit(S, NS, ACT, d(k["idx"]), d1=c.d1, d2=c.d2)   # the wide tables with their widths named
     assert out.shape == (ir.STEPS, 3) and bool(torch.isfinite(out).all())
 
