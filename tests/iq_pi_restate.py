@@ -55,13 +55,17 @@ class Policy:
         self.opt = torch.optim.Adam(self.p, lr=cfg.lr, betas=(0.9, 0.999), eps=cfg.adam_eps, weight_decay=cfg.wd)
         self.iter = 0
 
-    def mu_log_sigma(self, x):
-        """get_mu_log_sigma (:132-151): the network's forward (its Standardizer takes the rows), the split, the clamp."""
+    def heads(self, x):
+        """The network's forward (its Standardizer takes the rows): [n, 2A], mu | log_sigma before the clamp."""
         z = self.stand(x) if self.stand is not None else np.asarray(x, np.float32)
         z = torch.as_tensor(z).to(self.dtype)
         z = torch.relu(z @ self.p[0].T + self.p[1])
         z = torch.relu(z @ self.p[2].T + self.p[3])
-        y = z @ self.p[4].T + self.p[5]
+        return z @ self.p[4].T + self.p[5]
+
+    def mu_log_sigma(self, x):
+        """get_mu_log_sigma (:132-151): the forward, the split, the clamp."""
+        y = self.heads(x)
         return y[:, :self.A], torch.clamp(y[:, self.A:], self.cfg.ls_min, self.cfg.ls_max)
 
     def act(self, x, eps):
@@ -221,9 +225,13 @@ UPDATES, SWEEP_EPS = 3, 1e-5
 # Two configs per shape: both Standardizers and a weight decay; neither.  Adam's eps is 1e-5 here, as in
 # tests/iq_restate.py's sweep and for its reason (an entry whose gradient nearly cancels moves by lr / eps times a rounding
 # of the gradient; at 1e-8 torch's own float32 run cannot be held to TOL / 4); the fixtures keep torch's default 1e-8.
-# The clamp is [-3, -0.5] here (the fixtures keep [-20, 2]): a column clamped at log_std_max = 2 has sigma = 7.4, its tanh
-# saturates and 1 - a^2 + 1e-6 is then ill-conditioned in float32 (torch's own float32 run strays from float64 by 1e-3 on
-# a parameter), which would hide the kernel behind the rounding.  With sigma <= 0.61 no entry saturates.
+# The clamp is [-3, -0.5] here (the fixtures keep [-20, 2]), for the sake of this sweep's conditioning check, which is
+# torch's own all-float32 run (tests/test_iq_pi_cpu.py holds it within TOL / 4): a column clamped at log_std_max = 2 has
+# sigma = 7.4, its tanh saturates and 1 - a^2 + 1e-6 evaluated IN FLOAT32 strays from float64 by 1e-3 on a parameter, so
+# that run could not vouch for such a case.  With sigma <= 0.61 no entry saturates.  The kernels form that term in fp64
+# and are held at the agents' clamp [-20, 2] with saturated entries by the tables of tests/sg_saturation.py
+# (tests/test_sg_saturation_cpu.py, tests/test_gpu_sg_saturation.py), whose conditioning check is a float32 run with
+# the kernels' fp64 epilogue.
 SWEEP_LS = (-3.0, -0.5)
 CONFIGS = (PiCfg(standardizer=True, wd=1e-4, adam_eps=SWEEP_EPS, ls_min=SWEEP_LS[0], ls_max=SWEEP_LS[1]),
            PiCfg(standardizer=False, adam_eps=SWEEP_EPS, ls_min=SWEEP_LS[0], ls_max=SWEEP_LS[1]))
@@ -257,9 +265,13 @@ def case_inputs(in_dim, A, Bp, seed, updates=UPDATES):
                 delta=(0.5 * (max_a - min_a)).astype(np.float32))
 
 
-def run(case, cfg, dtype=torch.float64, alpha=ALPHA):
-    """The policy steps of `case` in order: (state after the last, out [updates, 4], a_new and log_prob of every step)."""
+def run(case, cfg, dtype=torch.float64, alpha=ALPHA, act=None):
+    """The policy steps of `case` in order: (state after the last, out [updates, 4], a_new and log_prob of every step).
+    act(policy, x, eps), if given, stands in for Policy.act (tests/sg_saturation.py's mixed-precision model and its wrong
+    readings)."""
     t = Twin(case["pparams"], case["cparams"], case["central"], case["delta"], cfg._replace(init_alpha=alpha), dtype=dtype)
+    if act is not None:
+        t.pi.act = lambda x, eps: act(t.pi, x, eps)
     outs, acts = [], []
     for s in case["steps"]:
         o, a, lp = t.policy_step(s["x"], s["eps"])

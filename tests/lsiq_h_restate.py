@@ -501,11 +501,14 @@ def actor_case(k):
     return _CACHE[("actor", k)]
 
 
-def run_actor(case, cfg, dtype=torch.float64, wrong=None):
-    """The policy steps of `case` in order: (state after the last, out [updates, 4], a_new and log_prob of every step)."""
+def run_actor(case, cfg, dtype=torch.float64, wrong=None, act=None):
+    """The policy steps of `case` in order: (state after the last, out [updates, 4], a_new and log_prob of every step).
+    act: as iq_pi_restate.run's."""
     import iq_pi_restate as P
     t = actor_twin(case["pparams"], case["cparams"], case["hparams"], case["central"], case["delta"],
                    cfg._replace(init_alpha=P.ALPHA), dtype, wrong)
+    if act is not None:
+        t.pi.act = lambda x, eps: act(t.pi, x, eps)
     outs, acts = [], []
     for s in case["steps"]:
         o, a, lp = t.policy_step(s["x"], s["eps"])

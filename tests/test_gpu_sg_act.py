@@ -6,8 +6,11 @@ DeviceBehavioralCloning(empirical_entropy=True), resume included.
 
 Tolerances.  mu and log_sigma are K16's kernel structure: bit-equal to Engine.ilmlp_forward, split and clamped.  ctrl is
 il_ctrl's expression on the action: bit-equal.  action and log_prob against float64: TOL = 2e-5 (log_prob relative to
-max(|log_prob|, 1)), on inputs where the reference's float32 formula is well conditioned (|a_raw| < 4, |log_sigma| < 1,
-asserted).  The sampled entropy: max(TOL max(1, |value|), 4 ent_spread), ent_spread the fixture's."""
+max(|log_prob|, 1)).  This file's cases stay where the reference's all-float32 formula is well conditioned too
+(|a_raw| < 4, |log_sigma| < 1, asserted), so that they can stand beside a float32 run; the kernel forms tanh, 1 - a^2
++ 1e-6 and its logarithm in fp64 and is held against float64 at saturated tanh, sigma up to exp(2) and the clamp
+[-20, 2] by tests/test_gpu_sg_saturation.py on the tables of tests/sg_saturation.py.  The sampled entropy:
+max(TOL max(1, |value|), 4 ent_spread), ent_spread the fixture's."""
 import gc
 import os
 import sys
@@ -59,9 +62,10 @@ def switch_rows():
     return 64 * cu - 32, 64 * cu - 31
 
 
-def sg_case(n, D, A, seed, standardizer=True):
+def sg_case(n, D, A, seed, standardizer=True, clip=2.0):
     """nn.Linear's default initialisation (log_sigma within -+0.5), columns of different scale and offset (unit columns
-    without a Standardizer), bounds of unequal widths, noise clipped to -+2 (|a_raw| < 4 at every shape of the table)."""
+    without a Standardizer), bounds of unequal widths, noise clipped to -+2 (|a_raw| < 4 at every shape of the table;
+    clip=None leaves the noise as drawn, for tests/sg_saturation.py's table)."""
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         lins = [torch.nn.Linear(D, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 2 * A)]
@@ -71,7 +75,8 @@ def sg_case(n, D, A, seed, standardizer=True):
     x = (rng.standard_normal((n, D)) * scale + shift).astype(np.float32)
     min_a, max_a = -rng.uniform(0.5, 2.0, A), rng.uniform(0.5, 3.0, A)
     central, delta = (0.5 * (max_a + min_a)).astype(np.float32), (0.5 * (max_a - min_a)).astype(np.float32)
-    eps = np.clip(rng.standard_normal((n, A)), -2.0, 2.0).astype(np.float32)
+    eps = rng.standard_normal((n, A))
+    eps = (eps if clip is None else np.clip(eps, -clip, clip)).astype(np.float32)
     return dict(params=params, x=x, central=central, delta=delta, eps=eps, standardizer=standardizer)
 
 
