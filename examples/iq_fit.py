@@ -12,6 +12,9 @@ policy that is trained does not collect them.
         (LSIQ_H / LSIQ_HC, lsiq_h.py / lsiq_hc.py: a second critic H learns the entropy, the actor follows Q + H)
     python examples/iq_fit.py --algo lsiq --q-exp-loss MSE|Huber [--lossq-type iq_like|sqil_like]
         [--loss-mode-exp fix|bootstrap] [--q-min -1] [--q-max 1] [--no-target-clipping] [--plcy-loss-mode MODE]
+    python examples/iq_fit.py --algo lsiq_offline --n-steps K --q-exp-loss MSE|Huber [--regularizer-mode off|exp|exp_and_plcy]
+        (LSIQ_Offline, imitation_lib/imitation/offline/lsiq_offline.py: DeviceLSIQOffline.fit_offline trains from the
+        demonstrations alone, K26 with plcy_loss_mode v0 on all-expert batches of --batch rows)
 """
 import argparse
 import json
@@ -38,7 +41,8 @@ class PrintingWriter:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq", "lsiq_h", "lsiq_hc", "iqfo", "lsiqfo", "lsiqfo_h", "lsiqfo_hc"),
+    ap.add_argument("--algo", choices=("iq", "sqil", "lsiq", "lsiq_h", "lsiq_hc", "iqfo", "lsiqfo", "lsiqfo_h", "lsiqfo_hc",
+                                       "lsiq_offline"),
                     default="iq", help="the *fo agents learn from (s, s') alone: an inverse action model draws the expert's actions")
     ap.add_argument("--am-lr", type=float, default=1e-4, help="*fo: the action model's Adam learning rate")
     ap.add_argument("--am-batch", type=int, default=64, help="*fo: rows of one action-model fit")
@@ -54,6 +58,8 @@ def main():
     ap.add_argument("--q-max", type=float, default=1.0, help="lsiq: Q_max")
     ap.add_argument("--no-target-clipping", action="store_true", help="lsiq: target_clipping=False")
     ap.add_argument("--plcy-loss-mode", default=None, help="plcy_loss_mode (default: the algorithm's)")
+    ap.add_argument("--n-steps", type=int, default=200, help="lsiq_offline: fit_offline's steps")
+    ap.add_argument("--regularizer-mode", choices=("off", "exp", "exp_and_plcy"), default="off", help="lsiq_offline")
     ap.add_argument("--updates", type=int, default=200)
     ap.add_argument("--batch", type=int, default=32, help="policy rows per update; as many expert rows are added")
     ap.add_argument("--in-dim", type=int, default=32)
@@ -73,6 +79,8 @@ def main():
     c_lins = [torch.nn.Linear(D + A, 512), torch.nn.Linear(512, 256), torch.nn.Linear(256, 1)]
     critic = DeviceSoftQCritic(eng, c_lins, standardizer=DeviceStandardizer(eng, D + A), lr=3e-4, tau=0.005)
     demo = il_synthetic_transitions(20000, D, A, seed=1)
+    if args.algo == "lsiq_offline":
+        return offline(args, eng, gen, policy, critic, demo)
     kw = dict(gamma=0.99, batch_size=args.batch, use_target=True, logging_iter=max(1, args.updates // 4),
               sw=PrintingWriter() if args.log else None, max_replay_size=50000, actor_optimizer=dict(lr=3e-4),
               warmup_transitions=1024, learnable_alpha=args.learnable_alpha, lr_alpha=3e-4, init_alpha=0.1)
@@ -127,6 +135,29 @@ def main():
             json.dump(dict(algo=args.algo, critic_updates=int(critic.step), policy_updates=int(agent.pi_step),
                            alpha=agent.alpha, first={t: float(v) for t, v in zip(_abi.IQ_PI_TAGS, first_pi)},
                            last={t: float(v) for t, v in zip(_abi.IQ_PI_TAGS, last_pi)},
+                           critic_last={t: float(v) for t, v in zip(_abi.IQ_Q_TAGS, last_q)}), f)
+
+
+def offline(args, eng, gen, policy, critic, demo):
+    from olympic_hip.iq_offline import DeviceLSIQOffline
+    agent = DeviceLSIQOffline(eng, policy, critic, demo, gamma=0.99, batch_size=args.batch, use_target=True, Q_max=args.q_max,
+                              Q_min=args.q_min, loss_mode_exp=args.loss_mode_exp, Q_exp_loss=args.q_exp_loss,
+                              regularizer_mode=args.regularizer_mode, actor_optimizer=dict(lr=3e-4),
+                              learnable_alpha=args.learnable_alpha, lr_alpha=3e-4, init_alpha=0.1,
+                              logging_iter=max(1, args.n_steps // 4), sw=PrintingWriter() if args.log else None)
+    w0 = policy.param.clone()
+    first_q, _ = agent.fit_offline(1, generator=gen)
+    first_q = first_q.cpu().numpy()
+    last_q, last_pi = agent.fit_offline(args.n_steps - 1, generator=gen) if args.n_steps > 1 else (None, None)
+    last_q = first_q if last_q is None else last_q.cpu().numpy()
+    moved = float((policy.param - w0).abs().max())
+    print(f"lsiq_offline: {critic.step} critic and {agent.pi_step} policy updates at batch {args.batch}; Loss1 "
+          f"{first_q[0]:.5f} -> {last_q[0]:.5f}; Q for expert {first_q[4]:.4f} -> {last_q[4]:.4f} (Q_max {args.q_max}); "
+          f"the policy moved by {moved:.4f}; alpha {agent.alpha:.5f} ({agent.alpha_step} temperature steps)")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(algo=args.algo, critic_updates=int(critic.step), policy_updates=int(agent.pi_step),
+                           alpha=agent.alpha, critic_first={t: float(v) for t, v in zip(_abi.IQ_Q_TAGS, first_q)},
                            critic_last={t: float(v) for t, v in zip(_abi.IQ_Q_TAGS, last_q)}), f)
 
 

@@ -33,6 +33,13 @@
 // passes 0 (live, a gradient) and 1 (target) run, the last workgroup of P also forms the batch's count of absorbing rows
 // and the running maximum of -log pi, launch A runs in instantiations of its own (iq_rows_kernel<G1, true>: the other
 // algorithms' code is compiled without the branch), and F commits the running maximum.
+// plcy_loss_mode v0 (iq_sac.py:508-510, lsiq.py:90-92; what LSIQ_Offline runs, imitation_lib/imitation/offline/
+// lsiq_offline.py:50-159) comes with the block oly_iq_v0: a fourth pass Q_v0 = critic(obs[expert] | a_v0) on the expert
+// rows, standardised with S + X0 (+ X1) + X2 + X3 and carrying the gradient of mean(f32(1 - gamma) (Q_v0 - alpha logp_v0)).
+// The pass on (obs | a_pi) then has no gradient and the v0 pass takes its workspace slot; P sums X3's columns in the
+// workgroups 3 NSP .. 4 NSP - 1, launch A runs in instantiations of its own (iq_rows_kernel<G1, false, true>, four passes),
+// F adds X3 to the Standardizer.  With the block's all_expert a batch may have no policy rows: the policy subset's means
+// come out as 0 / 0.
 // Every reduction has a fixed order and there are no atomics: two runs give identical bits.  The Standardizer's head, the
 // rows' staging, the hidden layers, dZ1, launch B's phases and the gradient norm's sums are ilmlp_fit.h's, shared with
 // K18, K24 and K27.
@@ -54,14 +61,15 @@ static_assert(MAX_BATCH <= 16 * THREADS, "the fold kernel's loops run over at mo
 
 // terms of a row: Q, Q^2, reward = Q - y, y, V, V - y, w reward^2, Q [absorbing], [absorbing],
 //                 SQIL (Q - (R + y))^2, SQIL (V - (R_min + y))^2, unused; LSIQ keeps the row's expert loss (term 1) in
-//                 T_SQ and its policy loss (sqil_like's term 2) in T_SV
-enum { T_Q, T_Q2, T_R, T_Y, T_V, T_VY, T_CHI, T_QABS, T_ABS, T_SQ, T_SV };
+//                 T_SQ and its policy loss (sqil_like's term 2) in T_SV; plcy_loss_mode v0 keeps f32(1 - gamma) V0 of an
+//                 expert row in T_V0
+enum { T_Q, T_Q2, T_R, T_Y, T_V, T_VY, T_CHI, T_QABS, T_ABS, T_SQ, T_SV, T_V0 };
 
 // workspace (floats), BP = batch rounded up to 16 rows, RP = NSLOT BP; [RP][W] arrays in row quads, element (row, col) at
 // ((row / 4) W + col) 4 + row % 4, slot s in rows [s BP, (s + 1) BP):
-//   xs [RP][64] | h1 [RP][512] | h2 [RP][256] | dZ1 [RP][512] | dZ2 [RP][256] | dZ3 [RP] | the raw outputs qv [3][BP] of
-//   the three passes | loss partials [BP / 16][2][NTERM] f64 | statistics partials [3][NSP][2][64] f64 | the inputs'
-//   column sums [3][2][64] f64 | gradient-norm partials [weight tiles] f64 | the transposed stream W2T | LSIQ_H's batch
+//   xs [RP][64] | h1 [RP][512] | h2 [RP][256] | dZ1 [RP][512] | dZ2 [RP][256] | dZ3 [RP] | the raw outputs qv [4][BP] of
+//   the passes (row 3: the v0 pass) | loss partials [BP / 16][2][NTERM] f64 | statistics partials [4][NSP][2][64] f64 | the
+//   inputs' column sums [4][2][64] f64 | gradient-norm partials [weight tiles] f64 | the transposed stream W2T | LSIQ_H's batch
 //   scalars [4]: the updated running maximum, the count of absorbing rows
 struct WsL {
   size_t xs, h1, h2, dz1, dz2, dz3, qv, lossp, statp, delta, gnp, w2t, hsc, total;
@@ -77,10 +85,10 @@ __host__ __device__ inline WsL ws_layout(int batch) {
   W.dz2 = W.dz1 + RP * H1;
   W.dz3 = W.dz2 + RP * H2;
   W.qv = W.dz3 + RP;
-  W.lossp = W.qv + 3 * BP;
+  W.lossp = W.qv + 4 * BP;
   W.statp = W.lossp + BP / 16 * 2 * NTERM * 2;
-  W.delta = W.statp + (size_t)3 * NSP * 2 * IN_MAX * 2;
-  W.gnp = W.delta + (size_t)3 * 2 * IN_MAX * 2;
+  W.delta = W.statp + (size_t)4 * NSP * 2 * IN_MAX * 2;
+  W.gnp = W.delta + (size_t)4 * 2 * IN_MAX * 2;
   W.w2t = W.gnp + (size_t)MAX_WTILES * 2;
   W.hsc = W.w2t + (size_t)H2 * H1;
   W.total = W.hsc + 4;
@@ -100,7 +108,7 @@ struct QArgs {
   float h_lo, h_hi, h_omg;     // LSIQ_H: the target's clip bounds; 1 - gamma in float32
   float* h_max;                // LSIQ_H: the block's h_max_state
   const float *h_q_t, *h_v_t;
-  int slot[3];                 // the workspace slot of each pass's gradient rows, -1: the pass has no gradient
+  int slot[4];                 // the workspace slot of each pass's gradient rows, -1: the pass has no gradient
   int n_slots;
   const float *obs, *act, *next_obs, *absorbing, *a_next, *logp_next, *a_pi, *logp_pi;
   double *colstats, *tcolstats;
@@ -111,6 +119,10 @@ struct QArgs {
   double* out;
   ParamLayout P;
   WsL W;
+  // plcy_loss_mode v0: the fourth pass Q_v0 = critic(obs[expert] | a_v0) on the n_v0 = B - n_policy expert rows
+  int v0, n_v0;
+  float omg;                   // 1 - gamma in float32
+  const float *a_v0, *logp_v0;
 };
 
 // column k < D of row `row` of critic input `src`
@@ -118,6 +130,11 @@ __device__ __forceinline__ float input_at(const QArgs& a, int src, size_t row, i
   const float* s = src == 1 ? a.next_obs : a.obs;
   const float* u = src == 0 ? a.act : src == 1 ? a.a_next : a.a_pi;
   return k < a.in_dim ? s[row * a.in_dim + k] : u[row * a.act_dim + (k - a.in_dim)];
+}
+
+// column k < D of row `row` >= n_policy of the v0 pass's input (obs | a_v0); a_v0's rows count from the first expert row
+__device__ __forceinline__ float v0_input_at(const QArgs& a, size_t row, int k) {
+  return k < a.in_dim ? a.obs[row * a.in_dim + k] : a.a_v0[(row - (size_t)a.n_policy) * a.act_dim + (k - a.in_dim)];
 }
 
 // LSIQ_H, one workgroup: n1 = the count of absorbing rows and cur = max(-logp_next[0, n_policy)), thread t over rows t,
@@ -157,22 +174,23 @@ __device__ __forceinline__ void h_batch_scalars(const QArgs& a, double* part) {
   __syncthreads();
 }
 
-// grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. 3 NSP - 1, slice b % NSP of input
-// b / NSP: four row-strided chains per column, met in a fixed order (fit_common.h's fold_chains)
-static_assert(3 * NSP <= PRO_BLOCKS, "one workgroup per statistics slice");
+// grid PRO_BLOCKS: the transposed stream from param (grid-stride) and, workgroups 0 .. 4 NSP - 1, slice b % NSP of input
+// b / NSP (input 3: the v0 pass's X3 = (obs[expert] | a_v0)): four row-strided chains per column, met in a fixed order
+// (fit_common.h's fold_chains)
+static_assert(4 * NSP <= PRO_BLOCKS, "one workgroup per statistics slice");
 __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
   __shared__ double part[8 * IN_MAX];
   build_w2t(a);
   if (a.algo == OLY_IQ_ALGO_LSIQ_H && blockIdx.x == PRO_BLOCKS - 1) h_batch_scalars(a, part);
   const int src = blockIdx.x / NSP, s = blockIdx.x % NSP;
-  if (src >= 3 || (src == 2 && !a.has_v) || (!a.colstats && !a.tcolstats)) return;
+  if (src >= 4 || (src == 2 && !a.has_v) || (src == 3 && !a.v0) || (!a.colstats && !a.tcolstats)) return;
   const int tid = threadIdx.x, k = tid & (IN_MAX - 1), grp = tid >> 6;
-  const int nb = src == 2 ? a.n_v : a.B;     // the rows of this pass
+  const int nb = src == 3 ? a.n_v0 : src == 2 ? a.n_v : a.B;     // the rows of this pass
   const int per = (nb + NSP - 1) / NSP, r0 = s * per, r1 = min(nb, r0 + per);
   double sum = 0.0, ss = 0.0;
   if (k < a.D)
     for (int r = r0 + grp; r < r1; r += 4) {
-      const double v = input_at(a, src, (size_t)r, k);
+      const double v = src == 3 ? v0_input_at(a, (size_t)(a.n_policy + r), k) : input_at(a, src, (size_t)r, k);
       sum += v;
       ss += v * v;
     }
@@ -185,7 +203,10 @@ __global__ __launch_bounds__(THREADS) void iq_prologue_kernel(QArgs a) {
 // output column by wave 0 as one chain over k < 256.  Backward: dZ2 = dQ W3 [h2 > 0] (one float32 product per element:
 // the output layer has one unit), dH1 = dZ2 W2 on the matrix cores (wave w -> tiles 4w .. 4w+3, the transposed stream).
 constexpr size_t ROWS_LDS_FLOATS = (size_t)(IN_MAX + H1 + 2 * H2) * 16;
-constexpr size_t ROWS_LDS = sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * (3 * 2 * IN_MAX + 16 * NTERM);
+constexpr size_t rows_lds(int passes) {
+  return sizeof(float) * ROWS_LDS_FLOATS + sizeof(double) * ((size_t)passes * 2 * IN_MAX + 16 * NTERM);
+}
+constexpr size_t ROWS_LDS = rows_lds(3), ROWS_LDS_V0 = rows_lds(4);
 static_assert(ROWS_LDS_FLOATS % 4 == 0, "the fp64 arrays must be 8-byte aligned");
 
 static_assert(OLY_LSIQ_VALUE == OLY_IQ_VALUE && OLY_LSIQ_VALUE_EXPERT == OLY_IQ_VALUE_EXPERT &&
@@ -328,17 +349,19 @@ __device__ __forceinline__ void sqil_row(const QArgs& a, int e, float Q, float y
   }
 }
 
-template <int G1, bool HB = false>
+// V0: the instantiations of plcy_loss_mode v0, with the fourth pass; the others are compiled without it (NP = 3).
+template <int G1, bool HB = false, bool V0 = false>
 __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
+  constexpr int NP = V0 ? 4 : 3;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xT = lds;                       // [64 x 16]   standardised input (act16 images, mlp_tiles.h)
   float* hA = xT + IN_MAX * 16;          // [512 x 16]  h1
   float* hB = hA + H1 * 16;              // [256 x 16]  h2
   float* gz = hB + H2 * 16;              // [256 x 16]  dZ2
-  double* st = reinterpret_cast<double*>(lds + ROWS_LDS_FLOATS);   // [3 passes][2][IN_MAX] mean, std
-  double* terms = st + 3 * 2 * IN_MAX;   // [16 rows][NTERM]
-  __shared__ float z[3][16];             // the raw outputs of the passes by row
-  __shared__ float coef[3][16];          // dL/d(output) of the passes by row
+  double* st = reinterpret_cast<double*>(lds + ROWS_LDS_FLOATS);   // [NP passes][2][IN_MAX] mean, std
+  double* terms = st + NP * 2 * IN_MAX;  // [16 rows][NTERM]
+  __shared__ float z[NP][16];            // the raw outputs of the passes by row
+  __shared__ float coef[NP][16];         // dL/d(output) of the passes by row
   __shared__ int sub[16];                // 0 policy row, 1 expert row, -1 beyond the batch
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, h4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -349,21 +372,21 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
 
   if (tid < D) {   // Standardizer.update_mean_std with each pass's rows (networks.py:76-81): the sums pass by pass
     const double* sp = reinterpret_cast<const double*>(ws + a.W.statp);
-    double s[3], ss[3];
-    for (int p = 0; p < 3; ++p) {
+    double s[NP], ss[NP];
+    for (int p = 0; p < NP; ++p) {
       s[p] = ss[p] = 0.0;
       if ((a.colstats || a.tcolstats) && (p < 2 || a.has_v)) slice_sums(sp + (size_t)p * NSP * 2 * IN_MAX, tid, s[p], ss[p]);
     }
     if (blockIdx.x == 0) {
       double* d = reinterpret_cast<double*>(ws + a.W.delta);
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < NP; ++p) {
         d[p * 2 * IN_MAX + tid] = s[p];
         d[p * 2 * IN_MAX + IN_MAX + tid] = ss[p];
       }
     }
     double cnt = 0.0, sum = 0.0, sq = 0.0;
     if (a.colstats) cnt = a.colstats[tid], sum = a.colstats[D + tid], sq = a.colstats[2 * D + tid];
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < NP; ++p) {
       double pc, ps, pq;
       bool have;
       if (p == 1 && a.use_target) {
@@ -373,7 +396,8 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
         pq = have ? a.tcolstats[2 * D + tid] + ss[1] : 0.0;
       } else {
         have = a.colstats != nullptr;
-        if (p < 2 || a.has_v) cnt += (double)(p == 2 ? a.n_v : B), sum += s[p], sq += ss[p];
+        if (V0 && p == 3) cnt += (double)a.n_v0, sum += s[p], sq += ss[p];
+        else if (p < 2 || a.has_v) cnt += (double)(p == 2 ? a.n_v : B), sum += s[p], sq += ss[p];
         pc = cnt, ps = sum, pq = sq;
       }
       double mean = 0.0, sd = 1.0;
@@ -386,7 +410,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
   __syncthreads();
 
   // ---- the forwards
-  for (int p = 0; p < 3; ++p) {
+  for (int p = 0; p < NP; ++p) {
     if (p == 2 && !a.has_v) break;
     const bool tgt = p == 1 && a.use_target;
     const bool standardise = tgt ? a.tcolstats != nullptr : a.colstats != nullptr;
@@ -395,8 +419,17 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
     const size_t srow0 = (size_t)(slot < 0 ? 0 : slot) * BP + row0;
     const size_t quad = (srow0 >> 2) + h4;           // this lane's accumulator rows: 4 h4 + i = one row quad
     stage_rows(xT, D, standardise, st + (p * 2) * IN_MAX,      // a row the pass does not take goes through as zeros
-               [&](int m) { return sub[m] >= 0 && (p < 2 || row0 + m < a.n_v); },
-               [&](int m, int k) { return input_at(a, p, (size_t)(row0 + m), k); }, slot >= 0, ws + a.W.xs, srow0);
+               [&](int m) {     // the v0 pass takes the expert rows
+                 if constexpr (V0)
+                   if (p == 3) return sub[m] == 1;
+                 return sub[m] >= 0 && (p < 2 || row0 + m < a.n_v);
+               },
+               [&](int m, int k) {
+                 if constexpr (V0)
+                   if (p == 3) return v0_input_at(a, (size_t)(row0 + m), k);
+                 return input_at(a, p, (size_t)(row0 + m), k);
+               },
+               slot >= 0, ws + a.W.xs, srow0);
     __syncthreads();
     // ---- layer 1: [16, D] x [D, 512], layer 2: [16, 512] x [512, 256]; a pass without a gradient keeps no activations
     hidden_layer<Relu, G1, IN_MAX / 16, 4, P_W1, P_B1>(xT, P, hA, slot >= 0, ws4, a.W.h1, quad);
@@ -429,6 +462,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
     double t[NTERM];
     for (int j = 0; j < NTERM; ++j) t[j] = 0.0;
     float cQ = 0.f, cN = 0.f, cV = 0.f;
+    [[maybe_unused]] float c0 = 0.f;
     if constexpr (HB) {
       if (e >= 0) cQ = h_row(a, (size_t)row0 + tid, e, z[0][tid], z[1][tid], t);
     } else if (e >= 0) {
@@ -463,10 +497,18 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
       cV = (float)dV;
       // y = cy clip(next_v) carries a gradient without a target, where the clip lets it through
       cN = a.use_target || !through ? 0.f : (float)((double)cy * (dy - dr));
+      if constexpr (V0) {
+        if (e == 1) {   // loss_term2 = mean(f32(1 - gamma) getV(obs[expert])) (iq_sac.py:508-510, lsiq.py:90-92)
+          const float v0 = z[3][tid] - a.alpha * a.logp_v0[i - (size_t)a.n_policy];
+          t[T_V0] = (double)(a.omg * v0);
+          c0 = (float)((double)a.omg / (double)(a.B - a.n_policy));
+        }
+      }
     }
     coef[0][tid] = cQ;
     coef[1][tid] = cN;
     coef[2][tid] = cV;
+    if constexpr (V0) coef[3][tid] = c0;
     for (int j = 0; j < NTERM; ++j) terms[tid * NTERM + j] = t[j];
   }
   __syncthreads();
@@ -479,7 +521,7 @@ __global__ __launch_bounds__(RTHREADS) void iq_rows_kernel(QArgs a) {
   }
 
   // ---- the backwards
-  for (int p = 0; p < 3; ++p) {
+  for (int p = 0; p < NP; ++p) {
     const int slot = a.slot[p];
     if (slot < 0) continue;
     const size_t srow0 = (size_t)slot * BP + row0;
@@ -577,7 +619,8 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
       }
     } else if (a.iq_like) {
       o[0] = lsiq && a.exp_mode == OLY_LSIQ_EXP_FIX ? Se[T_SQ] / n_e : -Se[T_R] / n_e;
-      o[1] = a.loss_mode == OLY_IQ_VALUE ? (Sp[T_VY] + Se[T_VY]) / n_all
+      o[1] = a.v0 ? Se[T_V0] / n_e
+             : a.loss_mode == OLY_IQ_VALUE ? (Sp[T_VY] + Se[T_VY]) / n_all
              : a.loss_mode == OLY_IQ_VALUE_EXPERT ? Se[T_VY] / n_e
              : a.loss_mode == OLY_IQ_VALUE_POLICY ? Sp[T_VY] / n_p
              : a.loss_mode == OLY_IQ_Q_OLD_POLICY ? Sp[T_R] / n_p
@@ -618,9 +661,9 @@ __global__ __launch_bounds__(THREADS) void iq_fold_kernel(QArgs a, int tiles_a, 
     const double Bd = (double)a.B;
     if (a.colstats) {
       double cnt = a.colstats[tid], sum = a.colstats[D + tid], sq = a.colstats[2 * D + tid];
-      for (int p = 0; p < 3; ++p) {
-        if ((p == 1 && a.use_target) || (p == 2 && !a.has_v)) continue;
-        cnt += p == 2 ? (double)a.n_v : Bd;
+      for (int p = 0; p < 4; ++p) {
+        if ((p == 1 && a.use_target) || (p == 2 && !a.has_v) || (p == 3 && !a.v0)) continue;
+        cnt += p == 3 ? (double)a.n_v0 : p == 2 ? (double)a.n_v : Bd;
         sum += d[p * 2 * IN_MAX + tid];
         sq += d[p * 2 * IN_MAX + IN_MAX + tid];
       }
@@ -654,10 +697,13 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
   if (!ctx) return OLY_EINVAL;
   if (!f) OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL argument", name);
   const int in_dim = f->in_dim, A = f->act_dim, B = f->batch, D = in_dim + A;
-  if (oly_iq_q_ws(B, in_dim, A) < 0 || f->n_policy < 1 || f->n_policy >= B)
+  // the block of plcy_loss_mode v0 and of all-expert batches: behind an argument block that says it is an oly_iq_q_ext
+  const oly_iq_v0* vb = f->pad == OLY_IQ_Q_EXT ? reinterpret_cast<const oly_iq_q_ext*>(f)->v0 : nullptr;
+  const bool all_expert = vb && vb->all_expert != 0;
+  if (oly_iq_q_ws(B, in_dim, A) < 0 || f->n_policy < (all_expert ? 0 : 1) || f->n_policy >= B)
     OLY_FAIL(ctx, OLY_EINVAL,
              "%s: supported: 2 <= batch <= %d, in_dim >= 1, 1 <= act_dim <= %d, in_dim + act_dim <= %d, 1 <= n_policy < "
-             "batch (got batch %d, in %d, act %d, n_policy %d)",
+             "batch, n_policy 0 with the v0 block's all_expert alone (got batch %d, in %d, act %d, n_policy %d)",
              name, MAX_BATCH, MAX_ACT, IN_MAX, B, in_dim, A, f->n_policy);
   const bool iq = f->algo == OLY_IQ_ALGO_IQ, sqil = f->algo == OLY_IQ_ALGO_SQIL, lsiq = f->algo == OLY_IQ_ALGO_LSIQ;
   const bool hb = f->algo == OLY_IQ_ALGO_LSIQ_H;
@@ -698,9 +744,18 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
       OLY_FAIL(ctx, OLY_EINVAL, "%s: sqil_like with plcy_loss_mode value needs as many policy rows as expert rows (n_policy %d of %d)",
                name, f->n_policy, B);
   }
-  if ((iq || (lsiq && iq_like)) && md == OLY_IQ_V0) OLY_FAIL(ctx, OLY_EINVAL, "%s: plcy_loss_mode v0 is not built", name);
+  const bool v0_family = iq || (lsiq && iq_like);
+  if (vb && !v0_family)
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: the v0 block goes with OLY_IQ_ALGO_IQ and LSIQ's iq_like alone", name);
+  const bool v0 = v0_family && md == OLY_IQ_V0;
+  if (v0 && !vb) OLY_FAIL(ctx, OLY_EINVAL, "%s: plcy_loss_mode v0 needs the v0 block (oly_iq_q_ext)", name);
+  if (v0 && (!vb->a_v0 || !vb->logp_v0)) OLY_FAIL(ctx, OLY_EINVAL, "%s: NULL a_v0 / logp_v0 in the v0 block", name);
+  if (all_expert && (f->regularizer_mode == OLY_IQ_REG_PLCY || md == OLY_IQ_VALUE_POLICY || md == OLY_IQ_Q_OLD_POLICY ||
+                     md == OLY_LSIQ_VALUE_Q_OLD_POLICY))
+    OLY_FAIL(ctx, OLY_EINVAL, "%s: all_expert leaves no policy rows for plcy_loss_mode %d / regularizer_mode %d", name, md,
+             f->regularizer_mode);
   if (hb     ? false
-      : iq   ? (md < OLY_IQ_VALUE || md > OLY_IQ_Q_OLD_POLICY)
+      : iq   ? (md < OLY_IQ_VALUE || md > OLY_IQ_V0)
       : sqil ? (md < OLY_SQIL_PLCY || md > OLY_SQIL_VALUE_PLCY)
       : iq_like ? (md < OLY_LSIQ_VALUE || md > OLY_LSIQ_OFF)
                 : (md < OLY_LSIQ_SQ_VALUE || md > OLY_LSIQ_SQ_Q_OLD_POLICY))
@@ -782,8 +837,14 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
   int ns = 0;
   a.slot[0] = ns++;
   a.slot[1] = a.use_target ? -1 : ns++;
-  a.slot[2] = has_v ? ns++ : -1;
+  a.slot[2] = has_v && !v0 ? ns++ : -1;    // v0: the pass on (obs | a_pi) feeds the Standardizer and the logged V alone
+  a.slot[3] = v0 ? ns++ : -1;
   a.n_slots = ns;
+  a.v0 = v0;
+  a.n_v0 = B - f->n_policy;
+  a.omg = 1.f - f->gamma;
+  a.a_v0 = v0 ? vb->a_v0 : nullptr;
+  a.logp_v0 = v0 ? vb->logp_v0 : nullptr;
   a.obs = f->obs;
   a.act = f->act;
   a.next_obs = f->next_obs;
@@ -818,6 +879,8 @@ extern "C" int oly_iq_q_update(oly_ctx* ctx, const oly_iq_q* f, oly_stream strea
   hipLaunchKernelGGL(iq_prologue_kernel, dim3(PRO_BLOCKS), dim3(THREADS), 0, oly_s(stream), a);
   rc = hb ? launch_rows(ctx, ctx->iqq_attr_done, 4u, iq_rows_kernel<2, true>, iq_rows_kernel<4, true>, D, dim3(tiles_a),
                         ROWS_LDS, stream, a)
+     : v0 ? launch_rows(ctx, ctx->iqq_attr_done, 16u, iq_rows_kernel<2, false, true>, iq_rows_kernel<4, false, true>, D,
+                        dim3(tiles_a), ROWS_LDS_V0, stream, a)
           : launch_rows(ctx, ctx->iqq_attr_done, 1u, iq_rows_kernel<2>, iq_rows_kernel<4>, D, dim3(tiles_a), ROWS_LDS, stream, a);
   if (rc != OLY_OK) return rc;
   hipLaunchKernelGGL(iq_weights_kernel, dim3(tiles_b), dim3(THREADS), 0, oly_s(stream), a);

@@ -7,7 +7,7 @@ from . import _abi, specs  # noqa: F401
 __all__ = ["_abi", "specs", "DeviceBehavioralCloning", "DeviceSquashedGaussianPolicy", "DeviceSoftQCritic",
            "DeviceReplayMemory", "DeviceIQLearn", "DeviceSQIL", "DeviceLSIQ", "DeviceLSIQH", "DeviceLSIQHC", "DeviceIQSAC",
            "DeviceSQILSAC", "DeviceLSIQSAC", "DeviceLSIQHSAC", "DeviceLSIQHCSAC", "DeviceGaussianInvActionModel",
-           "DeviceIQfOSAC", "DeviceLSIQfOSAC", "DeviceLSIQfOHSAC", "DeviceLSIQfOHCSAC"]
+           "DeviceIQfOSAC", "DeviceLSIQfOSAC", "DeviceLSIQfOHSAC", "DeviceLSIQfOHCSAC", "DeviceLSIQOffline"]
 
 
 def __getattr__(name):
@@ -24,4 +24,8 @@ def __getattr__(name):
     if name in ("DeviceGaussianInvActionModel", "DeviceIQfOSAC", "DeviceLSIQfOSAC", "DeviceLSIQfOHSAC", "DeviceLSIQfOHCSAC"):
         from . import iqfo
         return getattr(iqfo, name)
+    # offline LS-IQ (iq_offline.py: K26's v0 pass on all-expert batches)
+    if name == "DeviceLSIQOffline":
+        from . import iq_offline
+        return iq_offline.DeviceLSIQOffline
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

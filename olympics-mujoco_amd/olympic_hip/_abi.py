@@ -302,6 +302,19 @@ class IQQ(C.Structure):
                 ("lsiq", C.POINTER(LSIQ))]
 
 
+class IQV0(C.Structure):
+    """oly_iq_v0 (K26): plcy_loss_mode v0's own policy draw on the expert rows, and the all-expert flag."""
+    _fields_ = [("a_v0", vp), ("logp_v0", vp), ("all_expert", C.c_int32), ("pad", C.c_int32)]
+
+
+OLY_IQ_Q_EXT = 0x69717630       # oly_iq_q.pad of an oly_iq_q_ext's head
+
+
+class IQQExt(C.Structure):
+    """oly_iq_q_ext (K26): oly_iq_q with the trailing pointer to oly_iq_v0; q.pad = OLY_IQ_Q_EXT says so."""
+    _fields_ = [("q", IQQ), ("v0", C.POINTER(IQV0))]
+
+
 class IQPi(C.Structure):
     """oly_iq_pi (K27): one policy update of IQ-Learn / SQIL for oly_iq_pi_update."""
     _fields_ = [("in_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32), ("step", C.c_int32),

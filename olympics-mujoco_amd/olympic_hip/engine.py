@@ -1220,7 +1220,8 @@ class Engine:
                     target_colstats, param, m, v, packed, target_param, target_packed, ws, step, lr, algo="iq",
                     plcy_loss_mode="value", regularizer_mode="exp_and_plcy", treat_absorbing=False, use_target=True,
                     update_target=True, gamma=0.99, alpha=1e-3, reg_mult=0.5, R_min=0.0, R_max=1.0, tau=0.005, beta1=0.9,
-                    beta2=0.999, eps=1e-8, weight_decay=0.0, gradient_penalty_lambda=0.0, out=None, lsiq=None):
+                    beta2=0.999, eps=1e-8, weight_decay=0.0, gradient_penalty_lambda=0.0, out=None, lsiq=None, v0=None,
+                    all_expert=False):
         """oly_iq_q_update: one update_Q_function and _update_all_targets of IQ_SAC (algo "iq"), SQIL ("sqil") or LSIQ
         ("lsiq").  obs /
         next_obs [B,in] f32, act / a_next / a_pi [B,A] f32, absorbing / logp_next / logp_pi [B] f32; rows [0, n_policy)
@@ -1239,6 +1240,12 @@ class Engine:
         clip_expert, tau_up, tau_down, max_state [2] f32 (the running maximum and its flag, on the device; needed with
         clip_expert), q_t / v_t [B] f32 (Q_target(obs | act), Q_target(obs | a_pi); needed with cost)); out holds
         _abi.LSIQ_H_TAGS in its first nine slots.
+        v0=(a_v0 [B - n_policy, A], logp_v0 [B - n_policy]) f32, the policy's OWN draw on the expert rows' obs, goes with
+        plcy_loss_mode "v0" (algo "iq", or "lsiq" with iq_like) and is required there: the fourth pass
+        Q_v0 = critic(obs[expert] | a_v0) carries Loss2 = mean(f32(1 - gamma) (Q_v0 - alpha logp_v0)), the pass on
+        (obs | a_pi) feeds the Standardizer and the logged V alone.  all_expert=True (same algorithms) permits
+        n_policy == 0, the offline agents' batches; the modes that average over policy rows are refused with it and the
+        policy subset's scalars come out NaN.
         Returns out [16] f64 (_abi.IQ_Q_TAGS).  No synchronisation."""
         from ._ffi import lib
         f32, f64, dv = torch.float32, torch.float64, self.device
@@ -1250,8 +1257,8 @@ class Engine:
         if nws < 0:
             raise OlyError(f"iq_q_update: unsupported batch={B} in={in_dim} act={A} (2 <= batch <= "
                            f"{_abi.OLY_BC_MAX_BATCH}, act <= {_abi.OLY_BC_MAX_ACT}, in + act <= 64)")
-        if not 1 <= int(n_policy) < B:
-            raise OlyError(f"iq_q_update: n_policy={n_policy} outside [1, {B})")
+        if not (0 if all_expert else 1) <= int(n_policy) < B:
+            raise OlyError(f"iq_q_update: n_policy={n_policy} outside [1, {B}) (0 takes all_expert=True)")
         if algo not in _abi.IQ_ALGO:
             raise OlyError(f"iq_q_update: unknown algorithm {algo!r}")
         modes = _abi.IQ_PLCY_LOSS_MODES if algo == "iq" else _abi.SQIL_PLCY_LOSS_MODES
@@ -1311,9 +1318,19 @@ class Engine:
                 block.h_max_state, block.h_q_t, block.h_v_t = ptr(hd["max_state"]), ptr(hd["q_t"]), ptr(hd["v_t"])
         elif lsiq is not None:
             raise OlyError(f"iq_q_update: the lsiq block goes with algo 'lsiq', not {algo!r}")
-        if plcy_loss_mode not in modes or (not sqil_like and algo != "sqil" and plcy_loss_mode == "v0"):
+        v0_family = algo == "iq" or (algo == "lsiq" and not sqil_like)
+        if (v0 is not None or all_expert) and not v0_family:
+            raise OlyError("iq_q_update: v0 and all_expert go with algo 'iq' and with 'lsiq' / iq_like alone")
+        if plcy_loss_mode not in modes or (v0_family and plcy_loss_mode == "v0" and v0 is None):
             raise OlyError(f"iq_q_update: plcy_loss_mode {plcy_loss_mode!r} is not one of "
-                           f"{[k for k in modes if k != 'v0']} (v0 is not built)")
+                           f"{[k for k in modes if k != 'v0']} (v0 is not built without v0=(a_v0, logp_v0))")
+        is_v0 = v0_family and plcy_loss_mode == "v0"
+        if is_v0 and (not isinstance(v0, (tuple, list)) or len(v0) != 2):
+            raise OlyError("iq_q_update: v0 must be the pair (a_v0, logp_v0)")
+        if all_expert and (regularizer_mode == "plcy" or plcy_loss_mode in ("value_policy", "q_old_policy",
+                                                                            "value_q_old_policy")):
+            raise OlyError(f"iq_q_update: all_expert leaves no policy rows for plcy_loss_mode {plcy_loss_mode!r} / "
+                           f"regularizer_mode {regularizer_mode!r}")
         if regularizer_mode not in _abi.IQ_REGULARIZER_MODES:
             raise OlyError(f"iq_q_update: unknown regularizer_mode {regularizer_mode!r}")
         if float(gradient_penalty_lambda) > 0.0:
@@ -1334,6 +1351,10 @@ class Engine:
         _req(logp_next, "logp_next", (B,), f32, dv)
         _req(a_pi, "a_pi", (n_pi, A), f32, dv, optional=not need_pi)
         _req(logp_pi, "logp_pi", (n_pi,), f32, dv, optional=not need_pi)
+        a_v0, logp_v0 = v0 if is_v0 else (None, None)
+        if is_v0:
+            _req(a_v0, "a_v0", (B - int(n_policy), A), f32, dv)
+            _req(logp_v0, "logp_v0", (B - int(n_policy),), f32, dv)
         _req(colstats, "colstats", (3, D), f64, dv, optional=True)
         _req(target_colstats, "target_colstats", (3, D), f64, dv, optional=True)
         for t, name in ((param, "param"), (m, "m"), (v, "v")):
@@ -1357,6 +1378,12 @@ class Engine:
                      target_packed=ptr(target_packed), packed_floats=npk, target_packed_floats=npk if need_target else 0,
                      ws=ws.data_ptr(), ws_floats=nws, out=out.data_ptr(),
                      lsiq=C.pointer(block) if block is not None else None)
+        if is_v0 or all_expert:        # the block hangs behind an oly_iq_q whose pad says so (oly_iq_q_ext)
+            f.pad = _abi.OLY_IQ_Q_EXT
+            vblock = _abi.IQV0(a_v0=ptr(a_v0), logp_v0=ptr(logp_v0), all_expert=int(bool(all_expert)), pad=0)
+            ext = _abi.IQQExt(q=f, v0=C.pointer(vblock))
+            self.ctx.call("oly_iq_q_update", C.cast(C.pointer(ext), C.POINTER(_abi.IQQ)), self._s())
+            return out
         self.ctx.call("oly_iq_q_update", C.byref(f), self._s())
         return out
 

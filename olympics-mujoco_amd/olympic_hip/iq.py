@@ -34,7 +34,8 @@ DeviceIQLearn and DeviceSQIL are the critic side alone and refuse learnable_alph
 DeviceIQSAC and DeviceSQILSAC are the whole agents; DeviceLSIQ and DeviceLSIQSAC are the same pair for LSIQ; DeviceLSIQH
 and DeviceLSIQHC are the critic sides of LSIQ_H and LSIQ_HC, DeviceLSIQHSAC and DeviceLSIQHCSAC the whole agents, whose
 actor loss takes the sum of the two critics (K27 with its second critic).  Not built, each refused by the constructors: the gradient penalty
-(gradient_penalty_lambda > 0), plcy_loss_mode "v0" and gradient clipping of the actor.
+(gradient_penalty_lambda > 0), plcy_loss_mode "v0" and gradient clipping of the actor.  v0 runs in olympic_hip.iq_offline
+(DeviceLSIQOffline) and through Engine.iq_q_update(..., v0=); these classes keep refusing it.
 
 The cost of a learnable temperature: K25, K26 and K27 take alpha by value, so with learnable_alpha the `alpha` property
 reads log_alpha back from its device block, four bytes, once per iteration.  The default path has no read-back.
